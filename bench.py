@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the cqs hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W        (N=1 default; N>1 under torch.distributed.run)
+  python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]   (N=1 default; N>1 under torch.distributed.run)
 
 N = 1 (BASELINE.json configs[1], what the metric is quoted on): synthetic 1 000 000 x 768 fp32 unit vectors
 resident in HBM, single-query brute-force cosine top-20.  A "step" = one query scanned against the corpus
@@ -13,9 +13,15 @@ of the per-shard k x u64 candidates, host merge (north_star).  "scaling": "stron
 variant (1M rows per GPU, N queries per step) for comparison.
 
 Inputs (corpus, queries) are resident in HBM before the timed region.  Rank 0 prints ONE JSON line with the
-driver's contract fields plus `roofline`, `cpu_baseline`, `latency_host_api`, `other_configs` (the remaining
-BASELINE / SURVEY §8d configurations, each CHECKED outside its timed region), `embed` (index-build leg, with its
-own cpu_baseline) and `e2e` (configs[3]: chunks -> embed -> index -> k-NN with R@K against the CPU oracle).
+driver's contract fields.  A plain run does only what that headline needs: set-up, warm-up, the K timed steps, the
+outputs of the last step (`--dump-outputs DIR`) and the line.  `--full` adds, as before, the check of the last step's
+answer, `roofline`, `cpu_baseline`, `latency_host_api`, `other_configs` (the remaining BASELINE / SURVEY §8d
+configurations, each CHECKED outside its timed region), `embed` (index-build leg, with its own cpu_baseline) and `e2e`
+(configs[3]: chunks -> embed -> index -> k-NN with R@K against the CPU oracle); without it those keys are null.
+
+`--dump-outputs DIR` writes what the timed path returned for its last step, on rank 0: `DIR/topk_rows.npy` (float64,
+[queries, k], -1 past the count), `DIR/topk_scores.npy` (float32, NaN past the count) and `DIR/counts.npy` (float64,
+[queries]).  The inputs are seeded: the same arguments give the same inputs in every run.
 
 Every leg beside the headline lives in its own module under `bench_legs/` and runs under `Legs.run`: an exception in a leg
 becomes `{"error": ...}` under that leg's key (and a `leg_errors` entry), a leg that would start past `--budget-s` becomes
@@ -73,7 +79,14 @@ def parse():
     ap.add_argument("--strict", type=int, default=0, help="1: exit with status 3 AFTER printing the line when any leg errored "
                     "(what tests/test_bench_modes_gpu.py runs); default 0 keeps status 0 so that a measured headline is never "
                     "discarded over an auxiliary leg - the errors are in the line (`leg_errors`) either way")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also check the last step's answer and run the roofline pass and every "
+                    "auxiliary leg (CPU baselines, other configurations, embedding, end to end, ...); off: the headline alone")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR", help="after the timed steps, write the last step's "
+                    "top-k rows / scores / counts as DIR/<name>.npy (rank 0)")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 from bench_legs.common import HBM_PEAK_GBS, MFMA_F32_PEAK_TF, check_topk, file_sha256, make_unit_rows  # noqa: E402
 
@@ -367,78 +380,98 @@ def main():
     if dist is not None:
         elapsed = all_reduce_max(elapsed)
 
-    # ---- the last step's answer, checked outside the timed region ----
     i = W + K - 1
-    q_last = queries[i, 0]
-    if mode == "single":
-        check_topk(torch, np, rows, q_last, out_keys[i, 0].cpu().numpy().view(np.uint64), int(out_counts[i, 0].item()), k,
-                   what="headline")
-    else:
-        r, s = unpack_keys(merged[i][0])
-        assert len(r) == k and np.all(np.diff(s) <= 0), "merged top-k not sorted / short"
-        mine = [(int(x) - row_base, float(sv)) for x, sv in zip(r, s) if row_base <= int(x) < row_base + n]
-        if mine:
-            loc = torch.tensor([m[0] for m in mine], device=dev)
-            direct = (rows[loc].double() @ q_last.double()).cpu().numpy()
-            err = float(np.max(np.abs(direct - np.array([m[1] for m in mine]))))
-            assert err <= 1e-5, "rank %d: merged scores differ from a direct fp64 dot by %g" % (rank, err)
-        # exhaustive over ALL shards: at most k-1 rows of the whole corpus beat the merged k-th score of each rank's
-        # query (strong mode: every rank holds the same query; weak mode: one query per rank)
-        q_all = torch.empty((world, dim), dtype=torch.float32, device=dev)
-        kth_all = torch.empty((world,), dtype=torch.float32, device=dev)
-        all_gather_dev(q_all, q_last.contiguous())
-        all_gather_dev(kth_all, torch.tensor([float(s[-1])], dtype=torch.float32, device=dev))
-        beat = ((rows @ q_all.T) > (kth_all + 2e-6)[None, :]).sum(dim=0).to(torch.float64)
-        if dist is not None:
-            bt = beat.cpu() if rehearsal else beat
-            dist.all_reduce(bt, op=dist.ReduceOp.SUM)
-            beat = bt
-        assert float(beat[rank].item()) <= k - 1, "%d rows of the sharded corpus beat the merged k-th score" % int(beat[rank].item())
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed path receives for the last step: the packed top-k keys and the counts, unpacked
+        if mode == "single":
+            keys = out_keys[i].cpu().numpy().view(np.uint64)
+            cnt = out_counts[i].cpu().numpy().astype(np.int64)
+        else:
+            keys = np.zeros((len(merged[i]), k), dtype=np.uint64)
+            cnt = np.array([len(m) for m in merged[i]], dtype=np.int64)
+            for j, m in enumerate(merged[i]):
+                keys[j, :len(m)] = m
+        r, s = unpack_keys(keys)
+        valid = np.arange(k)[None, :] < cnt[:, None]
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        np.save(os.path.join(a.dump_outputs, "topk_rows.npy"), np.where(valid, r.astype(np.float64), -1.0))
+        np.save(os.path.join(a.dump_outputs, "topk_scores.npy"), np.where(valid, s, np.float32(np.nan)).astype(np.float32))
+        np.save(os.path.join(a.dump_outputs, "counts.npy"), cnt.astype(np.float64))
 
-    # ---- roofline: the scan kernel's own duration, HIP events on the launch stream ----
-    idx.set_timing(True)
-    for i in range(W, W + K):
-        scan_only(i)
-    torch.cuda.synchronize()
-    launches, scan_ms = idx.scan_time()
-    idx.set_timing(False)
-    avg_s = scan_ms / max(launches, 1) / 1e3
-    alg_bytes = n * dim * 4  # algorithmic bytes per launch = shard rows x dim x 4 B (corpus read once)
-    achieved = alg_bytes / avg_s / 1e9
-    if nq_scan >= 9 and dim % 32 == 0:
-        # query blocks >= 9 run on the f32 matrix cores: compute-bound (2*B*n*dim flops per launch)
-        flops = 2.0 * nq_scan * n * dim
-        tf = flops / avg_s / 1e12
-        roofline = {"bound": "mfma", "kernel": "scan_mfma_kernel", "achieved": round(tf, 2), "peak": MFMA_F32_PEAK_TF,
-                    "unit": "TFLOP/s", "frac": round(tf / MFMA_F32_PEAK_TF, 4), "traffic": None,
-                    "alg_flops_per_launch": flops, "avg_launch_ms": round(avg_s * 1e3, 5), "launches": launches}
-    else:
-        # traffic: NOT measured in this run (PMC needs rocprofv3 passes of their own).  The committed counter
-        # summary for this exact workload, if any, is quoted with its source; otherwise null.
-        traffic, traffic_src = None, None
-        tpath = os.path.join(ROOT, "profiles", "scan_traffic.json")
-        if os.path.exists(tpath):
-            try:
-                tj = json.load(open(tpath))
-                if tj.get("alg_bytes_per_launch") == alg_bytes and nq_scan == 1:
-                    # NOT measured in this run: the committed PMC summary, with the commit it was measured at and the
-                    # kernel instantiation it measured - a scan-kernel change after that commit invalidates it
-                    traffic = tj.get("hbm_bytes_per_launch")
-                    traffic_src = {"file": "profiles/scan_traffic.json", "how": tj.get("source"),
-                                   "measured_at_commit": tj.get("commit"), "kernel": tj.get("kernel"),
-                                   "scan_kernels_hip_sha256_then": tj.get("scan_kernels_sha256"),
-                                   "scan_kernels_hip_sha256_now": file_sha256(os.path.join(ROOT, "cqs_amd", "csrc", "scan_kernels.hip")),
-                                   "measured_in_this_run": False}
-            except Exception:
-                traffic = None
-        roofline = {"bound": "hbm", "kernel": "scan_gemv_kernel", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
-                    "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
-                    "traffic_source": traffic_src, "alg_bytes_per_launch": alg_bytes,
-                    "avg_launch_ms": round(avg_s * 1e3, 5), "launches": launches}
+    roofline = None
+    if a.full:
+        # ---- the last step's answer, checked outside the timed region ----
+        q_last = queries[i, 0]
+        if mode == "single":
+            check_topk(torch, np, rows, q_last, out_keys[i, 0].cpu().numpy().view(np.uint64), int(out_counts[i, 0].item()), k,
+                       what="headline")
+        else:
+            r, s = unpack_keys(merged[i][0])
+            assert len(r) == k and np.all(np.diff(s) <= 0), "merged top-k not sorted / short"
+            mine = [(int(x) - row_base, float(sv)) for x, sv in zip(r, s) if row_base <= int(x) < row_base + n]
+            if mine:
+                loc = torch.tensor([m[0] for m in mine], device=dev)
+                direct = (rows[loc].double() @ q_last.double()).cpu().numpy()
+                err = float(np.max(np.abs(direct - np.array([m[1] for m in mine]))))
+                assert err <= 1e-5, "rank %d: merged scores differ from a direct fp64 dot by %g" % (rank, err)
+            # exhaustive over ALL shards: at most k-1 rows of the whole corpus beat the merged k-th score of each rank's
+            # query (strong mode: every rank holds the same query; weak mode: one query per rank)
+            q_all = torch.empty((world, dim), dtype=torch.float32, device=dev)
+            kth_all = torch.empty((world,), dtype=torch.float32, device=dev)
+            all_gather_dev(q_all, q_last.contiguous())
+            all_gather_dev(kth_all, torch.tensor([float(s[-1])], dtype=torch.float32, device=dev))
+            beat = ((rows @ q_all.T) > (kth_all + 2e-6)[None, :]).sum(dim=0).to(torch.float64)
+            if dist is not None:
+                bt = beat.cpu() if rehearsal else beat
+                dist.all_reduce(bt, op=dist.ReduceOp.SUM)
+                beat = bt
+            assert float(beat[rank].item()) <= k - 1, "%d rows of the sharded corpus beat the merged k-th score" % int(beat[rank].item())
+
+        # ---- roofline: the scan kernel's own duration, HIP events on the launch stream ----
+        idx.set_timing(True)
+        for i in range(W, W + K):
+            scan_only(i)
+        torch.cuda.synchronize()
+        launches, scan_ms = idx.scan_time()
+        idx.set_timing(False)
+        avg_s = scan_ms / max(launches, 1) / 1e3
+        alg_bytes = n * dim * 4  # algorithmic bytes per launch = shard rows x dim x 4 B (corpus read once)
+        achieved = alg_bytes / avg_s / 1e9
+        if nq_scan >= 9 and dim % 32 == 0:
+            # query blocks >= 9 run on the f32 matrix cores: compute-bound (2*B*n*dim flops per launch)
+            flops = 2.0 * nq_scan * n * dim
+            tf = flops / avg_s / 1e12
+            roofline = {"bound": "mfma", "kernel": "scan_mfma_kernel", "achieved": round(tf, 2), "peak": MFMA_F32_PEAK_TF,
+                        "unit": "TFLOP/s", "frac": round(tf / MFMA_F32_PEAK_TF, 4), "traffic": None,
+                        "alg_flops_per_launch": flops, "avg_launch_ms": round(avg_s * 1e3, 5), "launches": launches}
+        else:
+            # traffic: NOT measured in this run (PMC needs rocprofv3 passes of their own).  The committed counter
+            # summary for this exact workload, if any, is quoted with its source; otherwise null.
+            traffic, traffic_src = None, None
+            tpath = os.path.join(ROOT, "profiles", "scan_traffic.json")
+            if os.path.exists(tpath):
+                try:
+                    tj = json.load(open(tpath))
+                    if tj.get("alg_bytes_per_launch") == alg_bytes and nq_scan == 1:
+                        # NOT measured in this run: the committed PMC summary, with the commit it was measured at and the
+                        # kernel instantiation it measured - a scan-kernel change after that commit invalidates it
+                        traffic = tj.get("hbm_bytes_per_launch")
+                        traffic_src = {"file": "profiles/scan_traffic.json", "how": tj.get("source"),
+                                       "measured_at_commit": tj.get("commit"), "kernel": tj.get("kernel"),
+                                       "scan_kernels_hip_sha256_then": tj.get("scan_kernels_sha256"),
+                                       "scan_kernels_hip_sha256_now": file_sha256(os.path.join(ROOT, "cqs_amd", "csrc", "scan_kernels.hip")),
+                                       "measured_in_this_run": False}
+                except Exception:
+                    traffic = None
+            roofline = {"bound": "hbm", "kernel": "scan_gemv_kernel", "achieved": round(achieved, 1), "peak": HBM_PEAK_GBS,
+                        "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4), "traffic": traffic,
+                        "traffic_source": traffic_src, "alg_bytes_per_launch": alg_bytes,
+                        "avg_launch_ms": round(avg_s * 1e3, 5), "launches": launches}
 
 
     # ---- the auxiliary legs: N = 1 only, each in its own module, each under legs.run ----
-    n1 = rank == 0 and world == 1 and mode == "single"
+    n1 = a.full and rank == 0 and world == 1 and mode == "single"
+    embed_on = a.full and a.embed_steps > 0
     latency = clients = other = abi = strong_n1 = sparse = aux = e2e = cpu = None
     embed = eng = ecfg = eweights = None
 
@@ -471,6 +504,7 @@ def main():
             "vs_baseline": None,
             "dtype": "f32",
             "data": "synthetic",
+            "full": a.full,                          # False: the check, roofline and auxiliary legs did not run (null keys)
             "config": {"workload": workload, "mode": mode, "rows_per_gpu": n, "total_rows": total_rows, "dim": dim, "k": k,
                        "queries_per_step": bq * (world if mode == "weak" else 1),
                        "parallelism": ("row-sharded x%d, %s all-gather of per-shard candidates, host merge"
@@ -536,7 +570,7 @@ def main():
     # which the ticketed embedding leg measured 3 % lower (6 072 against 6 198-6 242 chunks/s, same box, four orders tried,
     # round 4) - a baseline must not move the thing it is the baseline of.
     cpu_inputs = None
-    if rank == 0 and world == 1 and a.cpu_seconds > 0:
+    if a.full and rank == 0 and world == 1 and a.cpu_seconds > 0:
         cpu_inputs = (rows.cpu().numpy(), make_unit_rows(torch, 8, dim, 0xC950033, dev).cpu().numpy())
 
     if n1 and a.extras:
@@ -555,13 +589,13 @@ def main():
             a, torch, np, rows, make_unit_rows(torch, 200, dim, 0xC950034, dev).view(200, 1, dim), k, dim))
     # N > 1 under RCCL: the C ABI's single-process sharded handle (what the Rust daemon binds) gets its first
     # multi-device run here, on rank 0, after every rank has let go of its shard and left the group - see below.
-    abi_after_group = dist is not None and not rehearsal and a.abi_after and torch.cuda.device_count() >= world
+    abi_after_group = a.full and dist is not None and not rehearsal and a.abi_after and torch.cuda.device_count() >= world
 
     if n1 and a.extras and a.sparse_chunks > 0:
         from bench_legs.sparse import sparse_index_leg
         sparse = legs.run("sparse_index", sparse_index_leg, a, np, idx)
 
-    if a.embed_steps > 0:
+    if embed_on:
         from bench_legs.embed import embed_cpu_baseline, embed_leg
         idx.close()
         del rows
@@ -596,7 +630,7 @@ def main():
         # devices 0..N-1 with a corpus of its own (250k rows per device), checks it against the single-device answer
         # and times it through the blocking host API - in a watchdog thread: whatever happens in there (an RCCL clique
         # that cannot form, a hang), the line above is still printed.
-        if a.embed_steps <= 0:               # (the embed leg has closed the index and dropped the rows already)
+        if not embed_on:                     # (the embed leg has closed the index and dropped the rows already)
             idx.close()
             del rows
         del queries
@@ -613,7 +647,7 @@ def main():
             if not printed[0]:
                 printed[0] = True
                 print(json.dumps(build_line()), flush=True)
-    if a.embed_steps <= 0 and not abi_after_group:
+    if not embed_on and not abi_after_group:
         idx.close()
     if dist is not None:
         dist.barrier()

@@ -11,7 +11,8 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-COMMON = ["--steps", "6", "--warmup", "2", "--embed-steps", "0", "--cpu-seconds", "0", "--extras", "0", "--e2e-chunks", "0"]
+# --full: the answer checks, the roofline and the after-group legs these tests read run only under it
+COMMON = ["--steps", "6", "--warmup", "2", "--embed-steps", "0", "--cpu-seconds", "0", "--extras", "0", "--e2e-chunks", "0", "--full"]
 
 
 def _run(nproc, port, extra, env_extra):
@@ -87,10 +88,10 @@ def _errors_in(x, path=""):
 
 
 def test_the_drivers_command_with_every_leg_on(hip):
-    """VERDICT r04 #1c: `bench.py --gpus 1 --steps 20 --warmup 5` with extras ON (round 4's line died in a leg that no test
+    """VERDICT r04 #1c: `bench.py --gpus 1 --steps 20 --warmup 5 --full` with extras ON (round 4's line died in a leg that no test
     ran at the driver's --steps).  Sizes are scaled by flags only; every top-level key must be there, non-null, error-free."""
     scale = ["--rows", "200000", "--sparse-chunks", "200000", "--e2e-chunks", "2000", "--embed-steps", "2", "--cpu-seconds", "0.5",
-             "--strict", "1"]
+             "--strict", "1", "--full"]
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + DRIVER_CMD + scale, cwd=ROOT, env=dict(os.environ),
                        capture_output=True, text=True, timeout=900)
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -112,7 +113,7 @@ def test_a_failing_leg_does_not_cost_the_line(hip):
     env = dict(os.environ)
     env["CQS_BENCH_FAIL_LEG"] = "concurrent_clients"          # test hook of Legs.run: that leg raises before it starts
     args = ["--rows", "100000", "--embed-steps", "0", "--e2e-chunks", "0", "--sparse-chunks", "0", "--cpu-seconds", "0.3",
-            "--abi-devices", ""]
+            "--abi-devices", "", "--full"]
     for strict, rc in (("0", 0), ("1", 3)):
         p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + DRIVER_CMD + args + ["--strict", strict], cwd=ROOT, env=env,
                            capture_output=True, text=True, timeout=600)
@@ -131,7 +132,7 @@ def test_a_hanging_leg_does_not_cost_the_line_either(hip):
     subprocess.run([sys.executable, "-c", "import torch"], env=env, timeout=600)      # (the limit counts from process start: page torch in first)
     env["CQS_BENCH_HANG_LEG"] = "other_configs"              # test hook of Legs.run: that leg sleeps forever
     args = ["--rows", "100000", "--embed-steps", "0", "--e2e-chunks", "0", "--sparse-chunks", "0", "--cpu-seconds", "0.3",
-            "--abi-devices", "", "--hard-limit-s", "45"]
+            "--abi-devices", "", "--hard-limit-s", "45", "--full"]
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + DRIVER_CMD + args, cwd=ROOT, env=env,
                        capture_output=True, text=True, timeout=300)
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -140,3 +141,40 @@ def test_a_hanging_leg_does_not_cost_the_line_either(hip):
     assert "other_configs" in d["incomplete"] and "other_configs" in d["leg_errors"]
     assert d["value"] > 0 and d["roofline"]["frac"] > 0 and d["latency_host_api"]["ms_per_query"] > 0
     assert d["concurrent_clients"]["native_threads"]["8"]["checked"] and d["other_configs"] is None
+
+
+def test_a_plain_run_is_the_headline_alone_and_dumps_its_outputs(hip, tmp_path):
+    """Without --full the line carries the headline and nothing else runs (no answer check, roofline or leg);
+    `--dump-outputs` writes the last timed step's answer - the same in two runs with the same arguments, and the exact
+    top-k of the seeded corpus for the seeded last query."""
+    import numpy as np
+    import torch
+    from bench_legs.common import make_unit_rows
+    n, steps, warmup, k = 200000, 7, 3, 20
+    outs = []
+    for j in range(2):
+        out = tmp_path / ("run%d" % j)
+        p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                            "--rows", str(n), "--dump-outputs", str(out)], cwd=ROOT, env=dict(os.environ),
+                           capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, p.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == steps and d["warmup"] == warmup and d["ms_per_step"] > 0 and d["value"] > 0 and d["full"] is False
+        assert d["unit"] == "queries/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert all(d[key] is None for key in TOP_LEVEL) and d["leg_seconds"] == {}, d
+        outs.append({name: np.load(out / (name + ".npy")) for name in ("topk_rows", "topk_scores", "counts")})
+    for name, arr in outs[0].items():
+        assert arr.dtype in (np.float32, np.float64), name
+        assert np.array_equal(arr, outs[1][name], equal_nan=True), name
+    o = outs[0]
+    assert o["topk_rows"].shape == (1, k) and o["counts"].tolist() == [k]
+    # the seeded inputs bench.py draws (single mode, rank 0): corpus seed 0xC950001, one query per step from 0xC950002
+    dev = torch.device("cuda", 0)
+    rows = make_unit_rows(torch, n, 768, 0xC950001, dev)
+    q = make_unit_rows(torch, steps + warmup, 768, 0xC950002, dev)[steps + warmup - 1]
+    direct = (rows.double() @ q.double()).cpu().numpy()
+    got, scores = o["topk_rows"][0].astype(np.int64), o["topk_scores"][0]
+    assert np.all(np.diff(scores) <= 0) and np.max(np.abs(direct[got] - scores)) <= 1e-5
+    assert int((direct > float(scores[-1]) + 2e-6).sum()) <= k - 1

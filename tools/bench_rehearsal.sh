@@ -4,7 +4,7 @@
 set -e
 OUT=${1:-gpurun_out/rehearsal}
 mkdir -p $OUT
-COMMON="--steps 6 --warmup 2 --embed-steps 0 --cpu-seconds 0 --extras 0 --e2e-chunks 0"
+COMMON="--steps 6 --warmup 2 --embed-steps 0 --cpu-seconds 0 --extras 0 --e2e-chunks 0 --full"
 CQS_BENCH_REHEARSAL=1 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 \
   bench.py --gpus 2 --total-rows 400000 $COMMON > $OUT/strong2.json 2> $OUT/strong2.err
 CQS_BENCH_REHEARSAL=1 timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29612 \
