@@ -30,6 +30,7 @@
 #include "roctx.h"
 #include "index_internal.h"
 #include "persist_util.h"
+#include "scan_bf16.h"
 
 using cqs::kMaxK;
 using cqs::kRowsPerBlock;
@@ -222,6 +223,61 @@ int32_t create_common(uint64_t n, uint32_t dim, uint32_t metric, int32_t device,
     return CQS_HIP_OK;
 }
 
+// ---- bf16 shadow (cqs_hip_index_set_bf16_scan) ---------------------------------------------------------------------
+void shadow_free(cqs_hip_index* x) {
+    hipFree(x->d_shadow); hipFree(x->d_shadow_stats); hipFree(x->d_akeys); hipFree(x->d_acounts); hipFree(x->d_ekeys);
+    hipFree(x->d_cert); hipHostFree(x->h_cert);
+    x->d_shadow = nullptr; x->d_shadow_stats = nullptr; x->d_akeys = nullptr; x->d_acounts = nullptr; x->d_ekeys = nullptr;
+    x->d_cert = nullptr; x->h_cert = nullptr; x->h_cert_dev = nullptr;
+    x->shadow_cap = 0; x->shadow_r = 0.0; x->shadow_norm = 0.0;
+}
+
+// Convert rows [row0, x->n) into the shadow and fold them into R.  Caller holds mu, the stream is idle.  *outlier: a finite
+// row has a component of magnitude >= 2^64 (the shadow cannot certify against it).
+static int32_t shadow_convert(cqs_hip_index* x, uint64_t row0, bool* outlier) {
+    HIP_TRY(x, hipMemsetAsync(x->d_shadow_stats + 2, 0, sizeof(unsigned long long), x->stream));
+    HIP_TRY(x, cqs::launch_shadow_build(x->d_rows, x->d_shadow, row0, x->n - row0, x->dim, cqs::shadow_gamma(x->dim),
+                                        x->d_shadow_stats, x->stream));
+    unsigned long long st[3];
+    HIP_TRY(x, hipMemcpyAsync(st, x->d_shadow_stats, sizeof st, hipMemcpyDeviceToHost, x->stream));
+    HIP_TRY(x, hipStreamSynchronize(x->stream));
+    double r, m;
+    memcpy(&r, &st[0], sizeof r);
+    memcpy(&m, &st[1], sizeof m);
+    x->shadow_r = r * (1.0 + 0x1p-30);      // (f64 sums of <= 2048 squares and three square roots: relative error < 2^-40)
+    x->shadow_norm = m * (1.0 + 0x1p-30);
+    *outlier = st[2] != 0;
+    return CQS_HIP_OK;
+}
+
+// extend() on a handle with the shadow on: grow it with cap_rows, convert rows [n_old, n).  A failure here (no memory,
+// an outlier row) turns the shadow off and leaves the f32 index as extended: the call still succeeds.
+int32_t shadow_extend(cqs_hip_index* x, uint64_t n_old) {
+    if (x->cap_rows > x->shadow_cap) {
+        uint16_t* nd = nullptr;
+        if (hipMalloc(&nd, (size_t)x->cap_rows * x->dim * sizeof(uint16_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            shadow_free(x);
+            x->last_error = "extend: no device memory to grow the bf16 shadow; shadow turned off";
+            return CQS_HIP_OK;
+        }
+        hipError_t e = hipMemcpyAsync(nd, x->d_shadow, (size_t)n_old * x->dim * sizeof(uint16_t), hipMemcpyDeviceToDevice, x->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(x->stream);
+        if (e != hipSuccess) { hipFree(nd); return fail(x, CQS_HIP_ERR_DEVICE, "extend: shadow copy", e); }
+        hipFree(x->d_shadow);
+        x->d_shadow = nd;
+        x->shadow_cap = x->cap_rows;
+    }
+    bool outlier = false;
+    const int32_t rc = shadow_convert(x, n_old, &outlier);
+    if (rc != CQS_HIP_OK) return rc;
+    if (outlier) {
+        shadow_free(x);
+        x->last_error = "extend: a new row has a component of magnitude >= 2^64; bf16 shadow turned off";
+    }
+    return CQS_HIP_OK;
+}
+
 }  // namespace cqs_idx
 
 using namespace cqs_idx;
@@ -319,7 +375,9 @@ int32_t cqs_hip_index_extend(cqs_hip_index* x, const float* rows, uint64_t n_new
     }
     HIP_TRY(x, hipMemcpyAsync(x->d_rows + x->n * x->dim, rows, n_new * row_bytes, hipMemcpyHostToDevice, x->stream));
     HIP_TRY(x, hipStreamSynchronize(x->stream));
+    const uint64_t n_old = x->n;
     x->n += n_new;
+    if (x->d_shadow) return shadow_extend(x, n_old);
     return CQS_HIP_OK;
 } CQS_ABI_CATCH(x)
 
@@ -522,6 +580,7 @@ void cqs_hip_index_destroy(cqs_hip_index* x) CQS_ABI_TRY {
     hipSetDevice(x->device);
     (void)quiesce(x);  // src/cagra.rs:289-302 (incl. searches enqueued on caller streams)
     free_scratch(x);
+    shadow_free(x);
     hipFree(x->d_keep);
     hipFree(x->d_dbg);
     if (!x->borrow) hipFree(x->d_rows);
@@ -647,10 +706,121 @@ struct HostQuery {
     uint32_t* out_count;
 };
 
+// Scan + select for the nq queries staged in h_q[0, nq) (query i answers qs[map[i]]), wait, unpack.  Caller holds mu.
+static int32_t f32_block(cqs_hip_index* x, const HostQuery* qs, const uint32_t* map, const uint8_t* bad, uint32_t nq,
+                         uint32_t k_eff, const uint32_t* d_keep, uint32_t mode, float threshold, bool gemv_only) {
+    HIP_TRY(x, hipMemcpyAsync(x->d_q, x->h_q, (size_t)nq * x->dim * sizeof(float), hipMemcpyHostToDevice, x->stream));
+    // Small blocks: the select kernel writes keys and counts straight into the pinned host buffers (device-visible
+    // addresses): no copy calls behind the kernels, one wait.  Large blocks keep the device buffers + two copies
+    // (hundreds of KB of scattered 8-byte stores over PCIe would cost more than the copies).
+    const bool direct = x->h_out_keys_dev && x->h_out_counts_dev && (size_t)nq * k_eff <= kDirectOutKeys;
+    int32_t rc = enqueue_search(x, x->d_q, nq, k_eff, d_keep, mode, threshold, direct ? x->h_out_keys_dev : x->d_out_keys,
+                                direct ? x->h_out_counts_dev : x->d_out_counts, x->stream, gemv_only);
+    if (rc != CQS_HIP_OK) return rc;
+    if (!direct) {
+        HIP_TRY(x, hipMemcpyAsync(x->h_out_keys, x->d_out_keys, (size_t)nq * k_eff * sizeof(uint64_t), hipMemcpyDeviceToHost, x->stream));
+        HIP_TRY(x, hipMemcpyAsync(x->h_out_counts, x->d_out_counts, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, x->stream));
+    }
+    HIP_TRY(x, hipStreamSynchronize(x->stream));
+    if (x->d_dbg) print_debug_stamps(x);
+    for (uint32_t i = 0; i < nq; ++i) {
+        const uint32_t qi = map[i];
+        if (bad[qi]) continue;
+        uint32_t c = x->h_out_counts[i];
+        if (c > k_eff) c = k_eff;
+        cqs_hip_unpack_keys(x->h_out_keys + (size_t)i * k_eff, c, qs[qi].out_rows, qs[qi].out_scores);
+        *qs[qi].out_count = c;
+    }
+    return CQS_HIP_OK;
+}
+
+// The same block through the bf16 shadow (scan_bf16.h): shadow scan -> select k' + 1 -> rescore + certify -> one wait.
+// Certified answers are unpacked; the block-relative indices of the others go to `redo` (the caller runs them on the f32
+// scan).  Caller holds mu; h_q[0, nb) holds the staged queries of qs[q0, q0 + nb).
+static int32_t shadow_block(cqs_hip_index* x, const HostQuery* qs, uint32_t q0, const uint8_t* bad, uint32_t nb, uint32_t k_eff,
+                            const uint32_t* d_keep, uint32_t mode, float threshold, std::vector<uint32_t>& redo) {
+    const uint32_t kp = cqs::shadow_kprime(k_eff);
+    float bq[cqs::kShadowMaxQ];
+    for (uint32_t i = 0; i < nb; ++i) {
+        const float* q = x->h_q + (size_t)i * x->dim;
+        double s2 = 0.0;
+        for (uint32_t d = 0; d < x->dim; ++d) s2 += (double)q[d] * (double)q[d];
+        bq[i] = cqs::shadow_query_bound(s2, x->shadow_r, x->shadow_norm, x->dim);
+    }
+    hipStream_t st = x->stream;
+    HIP_TRY(x, hipMemcpyAsync(x->d_q, x->h_q, (size_t)nb * x->dim * sizeof(float), hipMemcpyHostToDevice, st));
+    cqs::ScanArgs a;
+    a.rows = x->d_rows;
+    a.n = (uint32_t)x->n;
+    a.n_pad = (uint32_t)pad_rows(x->n);
+    a.dim = x->dim;
+    a.q = x->d_q;
+    a.b = nb;
+    a.scores = x->d_scores;
+    a.keep = d_keep;
+    a.mode = mode;
+    a.threshold = threshold;
+    a.nontemporal = x->n * x->dim * sizeof(uint16_t) > kNtBytes;
+    a.linear_bins = (x->metric == CQS_HIP_METRIC_COSINE) || (mode == CQS_HIP_MODE_PIPELINE);
+    a.k = kp + 1u;
+    a.gmax = x->d_gmax;
+    a.gaux = a.k >= kGauxMinK ? x->d_gaux : nullptr;
+    a.work = x->d_work;
+    a.n_cu = x->n_cu;
+    a.dbg = nullptr;
+    a.gemv_only = true;
+    a.tiers = cqs::plan_tiers(a.n_pad, x->n_cu, false);
+    const bool timed = x->timing && x->ev_used + 2 <= kMaxTimingEvents;
+    if (timed) {
+        while (x->ev.size() < x->ev_used + 2) {
+            hipEvent_t e = nullptr;
+            HIP_TRY(x, hipEventCreate(&e));
+            x->ev.push_back(e);
+        }
+        HIP_TRY(x, hipEventRecord(x->ev[x->ev_used], st));
+    }
+    HIP_TRY(x, cqs::launch_scan_bf16(a, x->d_shadow, bq, st));
+    if (timed) {
+        HIP_TRY(x, hipEventRecord(x->ev[x->ev_used + 1], st));
+        x->ev_used += 2;
+    }
+    HIP_TRY(x, cqs::launch_select(a, (uint32_t)x->row_base, x->d_akeys, x->d_acounts, st));
+    const bool direct = x->h_out_keys_dev && x->h_out_counts_dev && (size_t)nb * k_eff <= kDirectOutKeys;
+    HIP_TRY(x, cqs::launch_rescore_certify(x->d_rows, x->dim, x->d_q, nb, k_eff, kp, mode, threshold, (uint32_t)x->row_base, bq,
+                                           x->d_akeys, x->d_acounts, x->d_ekeys, direct ? x->h_out_keys_dev : x->d_out_keys,
+                                           direct ? x->h_out_counts_dev : x->d_out_counts,
+                                           x->h_cert_dev ? x->h_cert_dev : x->d_cert, st));
+    HIP_TRY(x, hipEventRecord(x->done, st));
+    x->done_stream = st;
+    x->done_valid = true;
+    if (!direct) {
+        HIP_TRY(x, hipMemcpyAsync(x->h_out_keys, x->d_out_keys, (size_t)nb * k_eff * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+        HIP_TRY(x, hipMemcpyAsync(x->h_out_counts, x->d_out_counts, (size_t)nb * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    }
+    if (!x->h_cert_dev) HIP_TRY(x, hipMemcpyAsync(x->h_cert, x->d_cert, (size_t)nb * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(x, hipStreamSynchronize(st));
+    uint64_t certified = 0;
+    for (uint32_t i = 0; i < nb; ++i) {
+        const uint32_t qi = q0 + i;
+        if (bad[qi]) continue;
+        if (!x->h_cert[i]) { redo.push_back(i); continue; }
+        uint32_t c = x->h_out_counts[i];
+        if (c > k_eff) c = k_eff;
+        cqs_hip_unpack_keys(x->h_out_keys + (size_t)i * k_eff, c, qs[qi].out_rows, qs[qi].out_scores);
+        *qs[qi].out_count = c;
+        ++certified;
+    }
+    x->stat_certified.fetch_add(certified, std::memory_order_relaxed);
+    x->stat_fallbacks.fetch_add(redo.size(), std::memory_order_relaxed);
+    return CQS_HIP_OK;
+}
+
 // The host-buffer search proper: `b` queries with one (k, mode, threshold, bitset), scanned in blocks the scratch
 // budget allows.  Caller holds mu, has checked the arguments and zeroed the counts.  `gemv_only`: every block goes
 // through the HBM-streaming passes of <= 8 queries, whose scores do not depend on how many queries share a pass (same
 // per-lane FMA chain, same butterfly) - what the combining queue needs to hand each caller the bits it would have got alone.
+// With the bf16 shadow on, blocks that run as gemv passes go through it first (shadow_block); the matrix-core blocks keep
+// their path (their scores are not the gemv kernel's).
 static int32_t search_host_locked(cqs_hip_index* x, const HostQuery* qs, uint32_t b, uint32_t k, const uint32_t* keep_bitset,
                                   uint32_t mode, float threshold, bool gemv_only) {
     if (x->inject_fail.exchange(0, std::memory_order_acq_rel) != 0)
@@ -681,6 +851,7 @@ static int32_t search_host_locked(cqs_hip_index* x, const HostQuery* qs, uint32_
 
     const uint32_t blk = max_query_block(x);
     std::vector<uint8_t> bad(b, 0);
+    std::vector<uint32_t> map, redo;
     for (uint32_t done = 0; done < b;) {
         const uint32_t nb = (b - done) < blk ? (b - done) : blk;
         int32_t rc = ensure_scratch(x, nb, k_eff);
@@ -695,27 +866,24 @@ static int32_t search_host_locked(cqs_hip_index* x, const HostQuery* qs, uint32_
             if (ok) memcpy(dst, src, (size_t)x->dim * sizeof(float));
             else memset(dst, 0, (size_t)x->dim * sizeof(float));
         }
-        HIP_TRY(x, hipMemcpyAsync(x->d_q, x->h_q, (size_t)nb * x->dim * sizeof(float), hipMemcpyHostToDevice, x->stream));
-        // Small blocks: the select kernel writes keys and counts straight into the pinned host buffers (device-visible
-        // addresses): no copy calls behind the kernels, one wait.  Large blocks keep the device buffers + two copies
-        // (hundreds of KB of scattered 8-byte stores over PCIe would cost more than the copies).
-        const bool direct = x->h_out_keys_dev && x->h_out_counts_dev && (size_t)nb * k_eff <= kDirectOutKeys;
-        rc = enqueue_search(x, x->d_q, nb, k_eff, d_keep, mode, threshold, direct ? x->h_out_keys_dev : x->d_out_keys,
-                            direct ? x->h_out_counts_dev : x->d_out_counts, x->stream, gemv_only);
-        if (rc != CQS_HIP_OK) return rc;
-        if (!direct) {
-            HIP_TRY(x, hipMemcpyAsync(x->h_out_keys, x->d_out_keys, (size_t)nb * k_eff * sizeof(uint64_t), hipMemcpyDeviceToHost, x->stream));
-            HIP_TRY(x, hipMemcpyAsync(x->h_out_counts, x->d_out_counts, (size_t)nb * sizeof(uint32_t), hipMemcpyDeviceToHost, x->stream));
+        map.clear();
+        const bool shadow = x->d_shadow && (gemv_only || !cqs::use_mfma(nb, x->dim)) && nb <= cqs::kShadowMaxQ &&
+                            cqs::shadow_kprime(k_eff) >= k_eff;
+        if (shadow) {
+            redo.clear();
+            rc = shadow_block(x, qs, done, bad.data(), nb, k_eff, d_keep, mode, threshold, redo);
+            if (rc != CQS_HIP_OK) return rc;
+            // the queries the certificate did not cover: same call, f32 scan (redo is ascending: rows only move down)
+            for (uint32_t j = 0; j < (uint32_t)redo.size(); ++j) {
+                if (redo[j] != j) memcpy(x->h_q + (size_t)j * x->dim, x->h_q + (size_t)redo[j] * x->dim, (size_t)x->dim * sizeof(float));
+                map.push_back(done + redo[j]);
+            }
+        } else {
+            for (uint32_t i = 0; i < nb; ++i) map.push_back(done + i);
         }
-        HIP_TRY(x, hipStreamSynchronize(x->stream));
-        if (x->d_dbg) print_debug_stamps(x);
-        for (uint32_t i = 0; i < nb; ++i) {
-            const uint32_t qi = done + i;
-            if (bad[qi]) continue;
-            uint32_t c = x->h_out_counts[i];
-            if (c > k_eff) c = k_eff;
-            cqs_hip_unpack_keys(x->h_out_keys + (size_t)i * k_eff, c, qs[qi].out_rows, qs[qi].out_scores);
-            *qs[qi].out_count = c;
+        if (!map.empty()) {
+            rc = f32_block(x, qs, map.data(), bad.data(), (uint32_t)map.size(), k_eff, d_keep, mode, threshold, gemv_only);
+            if (rc != CQS_HIP_OK) return rc;
         }
         done += nb;
     }
@@ -890,6 +1058,60 @@ int32_t cqs_hip_index_search(cqs_hip_index* x, const float* queries, uint32_t b,
 void cqs_hip_index_combine_stats(const cqs_hip_index* x, uint64_t* passes, uint64_t* queries) CQS_ABI_TRY {
     if (passes) *passes = x ? x->stat_passes.load(std::memory_order_relaxed) : 0;
     if (queries) *queries = x ? x->stat_queries.load(std::memory_order_relaxed) : 0;
+} CQS_ABI_CATCH_VOID
+
+// bf16 shadow of the corpus for `VectorIndex::search` (src/index.rs:146; the reference's GPU backend keeps its f32
+// dataset resident, src/cagra.rs:255-277): host searches that run as gemv passes scan n x dim x 2 B instead of x 4 and
+// return the f32 scan's bytes (scan_bf16.h).  Owned single-device handles only.
+int32_t cqs_hip_index_set_bf16_scan(cqs_hip_index* x, int32_t enable) CQS_ABI_TRY {
+    if (!x) return CQS_HIP_ERR_INVALID;
+    if (x->sh) return CQS_HIP_ERR_INVALID;   // a row-sharded parent: out of scope (header)
+    std::lock_guard<std::mutex> g(x->mu);
+    if (x->poisoned.load(std::memory_order_acquire)) return CQS_HIP_ERR_POISONED;
+    HIP_TRY(x, hipSetDevice(x->device));
+    HIP_TRY(x, quiesce(x));   // a search enqueued on a caller stream may still read the shadow
+    if (!enable) { shadow_free(x); return CQS_HIP_OK; }
+    if (x->borrow) return fail(x, CQS_HIP_ERR_INVALID, "set_bf16_scan: index borrows its rows (they may change under the bound)");
+    if (x->dim % 8u != 0u || x->dim > cqs::kShadowMaxDim)
+        return fail(x, CQS_HIP_ERR_INVALID, "set_bf16_scan: dim must be a multiple of 8 and <= 2048");
+    if (x->d_shadow) return CQS_HIP_OK;
+    const uint64_t cap = x->cap_rows ? x->cap_rows : 1;
+    auto oom = [&](hipError_t e) { (void)hipGetLastError(); shadow_free(x); return fail(x, CQS_HIP_ERR_NOMEM, "set_bf16_scan: allocation", e); };
+    hipError_t e;
+    if ((e = hipMalloc(&x->d_shadow, (size_t)cap * x->dim * sizeof(uint16_t))) != hipSuccess) return oom(e);
+    x->shadow_cap = cap;
+    if ((e = hipMalloc(&x->d_shadow_stats, 3 * sizeof(unsigned long long))) != hipSuccess) return oom(e);
+    if ((e = hipMalloc(&x->d_akeys, (size_t)cqs::kShadowMaxQ * kMaxK * sizeof(uint64_t))) != hipSuccess) return oom(e);
+    if ((e = hipMalloc(&x->d_acounts, (size_t)cqs::kShadowMaxQ * sizeof(uint32_t))) != hipSuccess) return oom(e);
+    if ((e = hipMalloc(&x->d_ekeys, (size_t)cqs::kShadowMaxQ * (kMaxK - 1) * sizeof(uint64_t))) != hipSuccess) return oom(e);
+    if ((e = hipMalloc(&x->d_cert, (size_t)cqs::kShadowMaxQ * sizeof(uint32_t))) != hipSuccess) return oom(e);
+    if ((e = hipHostMalloc(&x->h_cert, (size_t)cqs::kShadowMaxQ * sizeof(uint32_t), hipHostMallocDefault)) != hipSuccess) return oom(e);
+    if (hipHostGetDevicePointer((void**)&x->h_cert_dev, x->h_cert, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        x->h_cert_dev = nullptr;
+    }
+    if ((e = hipMemsetAsync(x->d_shadow_stats, 0, 3 * sizeof(unsigned long long), x->stream)) != hipSuccess) { shadow_free(x); HIP_TRY(x, e); }
+    bool outlier = false;
+    const int32_t rc = shadow_convert(x, 0, &outlier);
+    if (rc != CQS_HIP_OK) { shadow_free(x); return rc; }
+    if (outlier) {
+        shadow_free(x);
+        return fail(x, CQS_HIP_ERR_INVALID, "set_bf16_scan: a finite row has a component of magnitude >= 2^64");
+    }
+    return CQS_HIP_OK;
+} CQS_ABI_CATCH(x)
+
+void cqs_hip_index_bf16_stats(const cqs_hip_index* x, uint64_t* bytes, uint64_t* certified, uint64_t* fallbacks) CQS_ABI_TRY {
+    uint64_t by = 0, c = 0, f = 0;
+    if (x && !x->sh) {
+        std::lock_guard<std::mutex> g(x->mu);
+        by = x->d_shadow ? x->shadow_cap * x->dim * sizeof(uint16_t) : 0;
+        c = x->stat_certified.load(std::memory_order_relaxed);
+        f = x->stat_fallbacks.load(std::memory_order_relaxed);
+    }
+    if (bytes) *bytes = by;
+    if (certified) *certified = c;
+    if (fallbacks) *fallbacks = f;
 } CQS_ABI_CATCH_VOID
 
 // `find_neighbors` (src/cli/commands/search/neighbors.rs:86-132) for a row of this index: the query is the

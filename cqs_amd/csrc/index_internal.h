@@ -98,6 +98,21 @@ struct cqs_hip_index {
     std::chrono::steady_clock::time_point last_pass_end{};   // guarded by cmu (epoch until the first pass: nobody waits)
     std::atomic<uint64_t> stat_passes{0}, stat_queries{0};   // combined passes run / queries they carried
     std::atomic<int32_t> inject_fail{0};  // test hook (cqs_hip_debug_index_fail_next): the next host search fails as a device error
+
+    // bf16 shadow (cqs_hip_index_set_bf16_scan; null = off): host searches of gemv blocks scan it first, rescore the
+    // candidates from d_rows and fall back to the f32 scan for any query the certificate does not cover (scan_bf16.h).
+    uint16_t* d_shadow = nullptr;         // [shadow_cap, dim] bf16
+    uint64_t shadow_cap = 0;              // rows the shadow buffer holds (follows cap_rows)
+    double shadow_r = 0.0;                // max over the finite rows of ||x - x~|| + gamma (||x|| + ||x~||)
+    double shadow_norm = 0.0;             // max over the finite rows of max(||x||, ||x~||)
+    unsigned long long* d_shadow_stats = nullptr;   // [3] the build pass's maxima (f64 bits) and outlier flag
+    uint64_t* d_akeys = nullptr;          // [kShadowMaxQ, kMaxK] approximate keys of the select
+    uint32_t* d_acounts = nullptr;        // [kShadowMaxQ]
+    uint64_t* d_ekeys = nullptr;          // [kShadowMaxQ, kMaxK - 1] rescored keys
+    uint32_t* d_cert = nullptr;           // [kShadowMaxQ] certified flags (device copy; used when h_cert is not mappable)
+    uint32_t* h_cert = nullptr;           // pinned [kShadowMaxQ]
+    uint32_t* h_cert_dev = nullptr;       // its device-visible address (null: not mappable)
+    std::atomic<uint64_t> stat_certified{0}, stat_fallbacks{0};
 };
 
 namespace cqs_idx {
@@ -118,6 +133,9 @@ int32_t enqueue_search(cqs_hip_index* x, const float* d_q, uint32_t b, uint32_t 
                        uint32_t mode, float thr, uint64_t* d_out_keys, uint32_t* d_out_counts, hipStream_t st,
                        bool gemv_only = false);
 hipError_t quiesce(cqs_hip_index* x);
+// bf16 shadow (index.hip).  Caller holds mu.
+void shadow_free(cqs_hip_index* x);
+int32_t shadow_extend(cqs_hip_index* x, uint64_t n_old);
 int32_t stage_keep(cqs_hip_index* x, const uint32_t* host_words, uint64_t words);
 int32_t create_common(uint64_t n, uint32_t dim, uint32_t metric, int32_t device, uint64_t row_base,
                       cqs_hip_index** out, cqs_hip_index** made);

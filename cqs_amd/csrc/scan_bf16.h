@@ -1,0 +1,74 @@
+// scan_bf16.h — the bf16 shadow of a dense index: build, scan, rescore + certify (scan_bf16.hip), and the host-side
+// arithmetic of its error bound (header-only, so a CPU test can check it).  Internal to libcqs_hip.so.
+//
+// A search over the shadow is exact: the approximate scan picks k' + 1 candidates, their f32 rows are rescored with the
+// f32 gemv kernel's own arithmetic, and the answer is kept only when no row outside the first k' candidates can enter
+// the top k.  Otherwise the host re-runs the query on the f32 scan.
+#pragma once
+#include <math.h>
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#include "scan_kernels.h"
+#endif
+
+namespace cqs {
+
+constexpr uint32_t kShadowMaxQ = 32;         // queries per shadow block (the combining queue's block cap)
+constexpr uint32_t kShadowMaxDim = 2048;     // (bf16 chunk = 512 components: up to 4 chunks per row)
+constexpr uint32_t kShadowKMax = 1024;       // = kMaxK (scan_kernels.h; checked in scan_bf16.hip)
+
+// Candidates rescored from the f32 rows for a top-k search: k' = min(2k + 32, kMaxK - 1); the select then returns k' + 1
+// approximate keys (<= kMaxK).  k' < k (only k = kMaxK) means the shadow cannot answer and the f32 scan runs.
+inline uint32_t shadow_kprime(uint32_t k) {
+    const uint32_t kp = 2u * k + 32u;
+    return kp < kShadowKMax - 1u ? kp : kShadowKMax - 1u;
+}
+
+// Relative f32 error of a `dim`-term dot product computed by FMA chains and a butterfly whose longest path rounds at most
+// dim times: gamma_dim = dim u / (1 - dim u), u = 2^-24 (IEEE fma and add, subnormals kept).
+inline double shadow_gamma(uint32_t dim) {
+    const double du = (double)dim * 0x1p-24;
+    return du / (1.0 - du);
+}
+
+// Smallest f32 >= v (v >= 0, finite; +inf if v is past the f32 range).
+inline float round_up_f32(double v) {
+    float f = (float)v;
+    if ((double)f < v) f = nextafterf(f, INFINITY);
+    return f;
+}
+
+// Per-query bound B_q = ||q||_2 * R (plus an absolute term for underflow in the dim roundings of either chain), rounded
+// up, so that |s - s~| <= B_q for every finite row.  q_norm2 = sum of q_i^2 in f64.  +inf (no certificate for this
+// query) when ||q|| * max(||x||, ||x~||) could reach the f32 overflow range, where one path could overflow and the other not.
+inline float shadow_query_bound(double q_norm2, double r_max, double norm_max, uint32_t dim) {
+    const double qn = sqrt(q_norm2) * (1.0 + 0x1p-40);            // f64 sum + sqrt: relative error far below 2^-40
+    if (!(qn * norm_max * (1.0 + shadow_gamma(dim)) < 0x1p100)) return INFINITY;
+    return round_up_f32(qn * r_max * (1.0 + 0x1p-40) + (double)dim * 0x1p-140);
+}
+
+#if defined(__HIPCC__)
+// Build: one pass over rows [row0, row0 + rows) of the f32 corpus -> bf16 rows (round to nearest even, NaN stays NaN),
+// and over the rows whose components are all finite the maxima of r = ||x - x~|| + gamma (||x|| + ||x~||) and of
+// max(||x||, ||x~||), as f64 bits (both >= 0, so the bits order like the values).  stats[0] / stats[1] must be zero (or
+// hold the maxima of earlier rows) on entry; stats[2] |= 1 if a finite row has a component with |x_i| >= 2^64.
+hipError_t launch_shadow_build(const float* rows, uint16_t* shadow, uint64_t row0, uint64_t n_rows, uint32_t dim,
+                               double gamma, unsigned long long* stats, hipStream_t st);
+
+// Approximate scan of the shadow: the scores / gmax / gaux layout of launch_scan (gemv passes of <= 8 queries), so the
+// unchanged launch_select picks each query's top k' + 1.  a.rows is ignored; bq[b] = B_q of query b (a.b <= kShadowMaxQ).
+hipError_t launch_scan_bf16(const ScanArgs& a, const uint16_t* shadow, const float* bq, hipStream_t st);
+
+// Rescore the first min(count, k') approximate keys of each query from the f32 rows (the gemv kernel's arithmetic and
+// epilogue), take the top k by the select's rank sort, write out_keys [b, k] / out_counts [b] as launch_select does, and
+// cert[b] = 1 when that answer is provably the f32 scan's (else the caller re-runs the query on the f32 scan).
+// akeys [b, k' + 1] / acounts [b]: the select's output; ekeys: [b, k'] scratch.
+hipError_t launch_rescore_certify(const float* rows, uint32_t dim, const float* q, uint32_t b, uint32_t k, uint32_t kprime,
+                                  uint32_t mode, float thr, uint32_t row_base, const float* bq, const uint64_t* akeys,
+                                  const uint32_t* acounts, uint64_t* ekeys, uint64_t* out_keys, uint32_t* out_counts,
+                                  uint32_t* cert, hipStream_t st);
+#endif
+
+}  // namespace cqs

@@ -1,0 +1,456 @@
+// scan_bf16.hip — gfx950 kernels of the dense index's bf16 shadow.
+//
+//  shadow_build_kernel   one pass over the f32 rows: bf16 copy (v_cvt_pk_bf16_f32: round to nearest even, NaN stays NaN)
+//                        and the index-wide error bound R.
+//  scan_bf16_kernel      HBM-streaming dot of every bf16 row with 1..8 f32 queries: half the bytes of scan_gemv_kernel.
+//                        Same tasks / work queue / score + gmax (+ gaux) layout, so the unchanged select_finish_kernel
+//                        takes each query's top k' + 1 approximate keys.
+//  rescore_kernel        one wave per candidate: the exact f32 score, bit for bit what scan_gemv_kernel computes.
+//  certify_kernel        one workgroup per query: top k of the rescored candidates (the select's rank sort) and the
+//                        certificate that no row outside them can enter the top k.
+//
+// Wave = 64 lanes.  gfx950 only.
+#include "scan_bf16.h"
+#include "launch_util.h"
+#include "rank_sort.h"
+#include "scan_device.h"
+
+namespace cqs {
+
+static_assert(kShadowKMax == kMaxK, "shadow k' policy and the select agree on max k");
+
+typedef float f4 __attribute__((ext_vector_type(4)));
+typedef float f2 __attribute__((ext_vector_type(2)));
+typedef unsigned u4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }          // component 2i
+__device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 0xFFFF0000u); }  // component 2i + 1
+__device__ __forceinline__ float key_score(uint64_t key) {                                        // inverse of okey
+    const uint32_t ok = (uint32_t)(key >> 32);
+    return __uint_as_float((ok & 0x80000000u) ? (ok ^ 0x80000000u) : ~ok);
+}
+
+// ---- build ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void shadow_build_kernel(const float* __restrict__ rows, uint16_t* __restrict__ shadow,
+                                                           uint64_t row0, uint64_t n_rows, uint32_t dim, double gamma,
+                                                           unsigned long long* __restrict__ stats) {
+    const int lane = threadIdx.x & 63;
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    for (uint64_t r = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); r < n_rows; r += waves) {
+        const float* xp = rows + (row0 + r) * dim;
+        uint16_t* op = shadow + (row0 + r) * dim;
+        double d2 = 0.0, n2 = 0.0, t2 = 0.0;
+        bool fin = true, big = false;
+        for (uint32_t i = (uint32_t)lane * 2u; i < dim; i += 128u) {   // dim % 8 == 0: pairs never straddle the row end
+            const f2 v = *(const f2*)(xp + i);
+            const bf2 h = __builtin_convertvector(v, bf2);
+            const uint32_t w = __builtin_bit_cast(uint32_t, h);
+            *(uint32_t*)(op + i) = w;
+            const float t0 = bf_lo(w), t1 = bf_hi(w);
+            fin = fin && __builtin_isfinite(v.x) && __builtin_isfinite(v.y);
+            big = big || __builtin_fabsf(v.x) >= 0x1p64f || __builtin_fabsf(v.y) >= 0x1p64f;
+            const double e0 = (double)v.x - (double)t0, e1 = (double)v.y - (double)t1;   // exact in f64
+            d2 += e0 * e0 + e1 * e1;
+            n2 += (double)v.x * (double)v.x + (double)v.y * (double)v.y;
+            t2 += (double)t0 * (double)t0 + (double)t1 * (double)t1;
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            d2 += __shfl_xor(d2, m, 64);
+            n2 += __shfl_xor(n2, m, 64);
+            t2 += __shfl_xor(t2, m, 64);
+        }
+        const bool all_fin = __ballot(!fin) == 0ull;
+        const bool any_big = __ballot(big) != 0ull;
+        if (lane == 0 && all_fin) {   // rows with a non-finite component score non-finite in both paths: no part in R
+            const double nx = sqrt(n2), nt = sqrt(t2);
+            const double rb = sqrt(d2) + gamma * (nx + nt);
+            atomicMax(&stats[0], (unsigned long long)__double_as_longlong(rb));
+            atomicMax(&stats[1], (unsigned long long)__double_as_longlong(nx > nt ? nx : nt));
+            if (any_big) atomicMax(&stats[2], 1ull);
+        }
+    }
+}
+
+hipError_t launch_shadow_build(const float* rows, uint16_t* shadow, uint64_t row0, uint64_t n_rows, uint32_t dim,
+                               double gamma, unsigned long long* stats, hipStream_t st) {
+    if (n_rows == 0) return hipSuccess;
+    const uint64_t blocks = (n_rows + 3u) / 4u;
+    hipLaunchKernelGGL(shadow_build_kernel, dim3((uint32_t)(blocks < 8192u ? blocks : 8192u)), dim3(256), 0, st, rows,
+                       shadow, row0, n_rows, dim, gamma, stats);
+    return hipGetLastError();
+}
+
+// ---- approximate scan -------------------------------------------------------------------------------------------
+struct Bf16ScanParams {
+    const uint16_t* rows;   // [n, dim] bf16
+    uint32_t n, n_pad, dim;
+    const float* q;
+    float* scores;
+    const uint32_t* keep;
+    uint32_t mode;
+    float thr;
+    uint32_t nq;            // queries present (<= BQ)
+    uint32_t* work;
+    TaskTiers tiers;
+    uint32_t n_tasks;
+    float* gmax;
+    uint64_t* gaux;         // nullable
+    float bq[kMaxGemvQ];    // B_q of each query of the pass
+};
+
+// NCH = ceil(dim / 512): 1-KiB bf16 chunks per row; lane owns components [c*512 + lane*8, +8) of chunk c (one 16-byte load).
+// A partial last chunk (FULL = false, 768-d: lanes 32..63 of chunk 1) reads a clamped in-row address against a zero query
+// fragment, as scan_gemv_kernel does.  Batch by batch (loads, then math); occupancy keeps the HBM busy.
+template <int NCH, int BQ, int RI, bool NT, bool FULL>
+__global__ __launch_bounds__(256) void scan_bf16_kernel(const Bf16ScanParams p) {
+    constexpr int NV = RI * BQ;
+    constexpr int LPV = 64 / NV;
+    const int lane = threadIdx.x & 63;
+    const uint32_t n = p.n, dim = p.dim;
+
+    uint32_t coff[NCH];
+    f4 qa[BQ][NCH], qb[BQ][NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        const uint32_t idx = (uint32_t)c * 512u + (uint32_t)lane * 8u;
+        const bool in = FULL || idx < dim;
+        coff[c] = in ? idx : dim - 8u;
+#pragma unroll
+        for (int b = 0; b < BQ; ++b) {
+            const float* qp = p.q + (size_t)((uint32_t)b < p.nq ? b : 0) * dim + coff[c];
+            const f4 va = *(const f4*)qp, vb = *(const f4*)(qp + 4);
+            qa[b][c] = in ? va : (f4)(0.f);
+            qb[b][c] = in ? vb : (f4)(0.f);
+        }
+    }
+
+    const uint32_t last = n - 1u;
+    const uint32_t nwords = (n + 31u) / 32u;
+    const uint32_t n_tasks = p.n_tasks;
+    const uint32_t wpb = blockDim.x >> 6;
+    const uint32_t total_waves = gridDim.x * wpb;
+    const uint32_t wave_id = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * wpb + (threadIdx.x >> 6)));
+    const bool use_queue = n_tasks > total_waves;
+    uint32_t opaque_zero;   // (see scan_gemv_kernel: keeps the dequeue a plain returning atomic)
+    asm volatile("v_mov_b32 %0, 0" : "=v"(opaque_zero));
+
+    const char* const rows_b = (const char*)p.rows;
+    const uint32_t row_bytes = dim * 2u;
+    auto load_rows = [&](uint32_t base, int j, u4 (&x)[RI][NCH]) {
+#pragma unroll
+        for (int r = 0; r < RI; ++r) {
+            uint32_t row = base + (uint32_t)(RI * j + r);
+            row = row > last ? last : row;
+            const char* rp = rows_b + (uint64_t)row * row_bytes;
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) {
+                const u4* src = (const u4*)(rp + coff[c] * 2u);
+                if (NT) x[r][c] = __builtin_nontemporal_load(src);
+                else x[r][c] = *src;
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto reduce_rows = [&](int j, u4 (&x)[RI][NCH], float (&sc)[BQ]) {
+        f2 acc2[NV];
+#pragma unroll
+        for (int i = 0; i < NV; ++i) acc2[i] = (f2)(0.f);
+#pragma unroll
+        for (int r = 0; r < RI; ++r)
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) {
+                const u4 w = x[r][c];
+                const f2 x0 = {bf_lo(w.x), bf_hi(w.x)}, x1 = {bf_lo(w.y), bf_hi(w.y)};
+                const f2 x2 = {bf_lo(w.z), bf_hi(w.z)}, x3 = {bf_lo(w.w), bf_hi(w.w)};
+#pragma unroll
+                for (int b = 0; b < BQ; ++b) {
+                    f2 a = acc2[b * RI + r];
+                    a = __builtin_elementwise_fma(x0, __builtin_shufflevector(qa[b][c], qa[b][c], 0, 1), a);
+                    a = __builtin_elementwise_fma(x1, __builtin_shufflevector(qa[b][c], qa[b][c], 2, 3), a);
+                    a = __builtin_elementwise_fma(x2, __builtin_shufflevector(qb[b][c], qb[b][c], 0, 1), a);
+                    a = __builtin_elementwise_fma(x3, __builtin_shufflevector(qb[b][c], qb[b][c], 2, 3), a);
+                    acc2[b * RI + r] = a;
+                }
+            }
+        float acc[NV];
+#pragma unroll
+        for (int i = 0; i < NV; ++i) acc[i] = acc2[i].x + acc2[i].y;
+        treduce<NV>(acc, lane);
+#pragma unroll
+        for (int b = 0; b < BQ; ++b) {
+            const float t = __shfl(acc[0], (b * RI + (lane % RI)) * LPV, 64);
+            if (lane / RI == j) sc[b] = t;
+        }
+    };
+    // The f32 epilogue's drop rules, made one-sided: a row is dropped only if its exact score is dropped too.  No clamp on
+    // the stored score (bin_of clamps; the select only needs a monotone map).
+    auto epilogue = [&](uint32_t cur, uint32_t base, uint32_t trows, uint64_t mask, float (&sc)[BQ]) {
+        const uint32_t row = base + (uint32_t)lane;
+        const bool live = (uint32_t)lane < trows && ((mask >> lane) & 1ull);
+#pragma unroll
+        for (int b = 0; b < BQ; ++b) {
+            float s = sc[b];
+            if (!live || !(__builtin_fabsf(s) <= 3.4028234664e38f)) s = -INFINITY;
+            else if (p.mode == 1u) {
+                // s <= s~ + B_q, rounding is monotone and the clamp too: clamp(s) >= thr implies clamp(s~ + B_q) >= thr
+                float t = s + p.bq[b];
+                t = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);
+                if (!(t >= p.thr)) s = -INFINITY;
+            }
+            if ((uint32_t)b >= p.nq) continue;
+            if ((uint32_t)lane < trows && row < p.n_pad) p.scores[(size_t)b * p.n_pad + row] = s;
+            const float gm = wave_max64(s);
+            if (lane == 0) p.gmax[(size_t)b * n_tasks + cur] = gm;
+            if (p.gaux) {
+                const uint32_t arg = (uint32_t)__builtin_ctzll(__ballot(s == gm));
+                const float sec = wave_max64(((uint32_t)lane == arg) ? -INFINITY : s);
+                if (lane == 0) p.gaux[(size_t)b * n_tasks + cur] = ((uint64_t)arg << 32) | (uint64_t)__float_as_uint(sec);
+            }
+        }
+    };
+    auto task_mask = [&](uint32_t base, uint32_t trows) -> uint64_t {
+        const uint64_t all = trows == 64u ? ~0ull : ((1ull << trows) - 1ull);
+        uint64_t mask = all;
+        if (base + trows > n) mask = (base >= n) ? 0ull : (all >> (trows - (n - base)));
+        if (p.keep) {
+            const uint32_t w = base / 32u;
+            const uint32_t w0 = (w < nwords) ? p.keep[w] : 0u;
+            const uint32_t w1 = (w + 1u < nwords) ? p.keep[w + 1u] : 0u;
+            mask &= (((uint64_t)w1 << 32) | (uint64_t)w0) >> (base & 31u);
+        }
+        const uint32_t mlo = __builtin_amdgcn_readfirstlane((uint32_t)mask);
+        const uint32_t mhi = __builtin_amdgcn_readfirstlane((uint32_t)(mask >> 32));
+        return ((uint64_t)mhi << 32) | mlo;
+    };
+
+    u4 x[RI][NCH];
+    uint32_t cur = wave_id;
+    while (cur < n_tasks) {
+        uint32_t trows;
+        const uint32_t base = p.tiers.locate(cur, trows);
+        const uint64_t mask = task_mask(base, trows);
+        uint32_t ticket = 0;
+        if (use_queue && lane == 0) ticket = atomicAdd(p.work + opaque_zero, 1u);
+        float sc[BQ];
+#pragma unroll
+        for (int b = 0; b < BQ; ++b) sc[b] = -INFINITY;
+        const int nb = (int)(trows / (uint32_t)RI);
+        for (int j = 0; j < nb; ++j) {
+            const uint32_t m = (uint32_t)(mask >> (RI * j)) & ((1u << RI) - 1u);
+            if (m == 0u) continue;   // all RI rows filtered out / past the end: skip their reads
+            load_rows(base, j, x);
+            reduce_rows(j, x, sc);
+        }
+        epilogue(cur, base, trows, mask, sc);
+        cur = use_queue ? total_waves + (uint32_t)__builtin_amdgcn_readfirstlane(ticket) : n_tasks;
+    }
+}
+
+#ifndef CQS_BF16_ONE_SHOT
+#define CQS_BF16_ONE_SHOT 24u   // one task per wave up to this many tasks per SIMD; beyond: persistent grid + queue
+#endif
+#ifndef CQS_BF16_BLOCKS_PER_CU
+#define CQS_BF16_BLOCKS_PER_CU 2u
+#endif
+
+template <int NCH, int BQ, int RI>
+static hipError_t launch_bf16(const ScanArgs& a, const uint16_t* shadow, const float* bq, uint32_t q0, uint32_t nq,
+                              uint32_t work_slot, hipStream_t st) {
+    Bf16ScanParams p;
+    p.rows = shadow; p.n = a.n; p.n_pad = a.n_pad; p.dim = a.dim;
+    p.q = a.q + (size_t)q0 * a.dim;
+    p.scores = a.scores + (size_t)q0 * a.n_pad;
+    p.keep = a.keep; p.mode = a.mode; p.thr = a.threshold;
+    p.nq = nq;
+    p.work = a.work + work_slot;
+    p.tiers = a.tiers;
+    p.n_tasks = a.tiers.total();
+    p.gmax = a.gmax + (size_t)q0 * p.n_tasks;
+    p.gaux = a.gaux ? a.gaux + (size_t)q0 * p.n_tasks : nullptr;
+    for (uint32_t b = 0; b < kMaxGemvQ; ++b) p.bq[b] = b < nq ? bq[q0 + b] : 0.f;
+    const bool one_shot = p.n_tasks <= a.n_cu * 4u * CQS_BF16_ONE_SHOT;
+    const uint32_t wpb = 4u;
+    const uint32_t blocks = one_shot ? (p.n_tasks + wpb - 1u) / wpb : a.n_cu * CQS_BF16_BLOCKS_PER_CU;
+    const dim3 grid(blocks), block(64u * wpb);
+    const bool full = (a.dim == (uint32_t)NCH * 512u);
+    if (a.nontemporal) {
+        if (full) hipLaunchKernelGGL((scan_bf16_kernel<NCH, BQ, RI, true, true>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((scan_bf16_kernel<NCH, BQ, RI, true, false>), grid, block, 0, st, p);
+    } else {
+        if (full) hipLaunchKernelGGL((scan_bf16_kernel<NCH, BQ, RI, false, true>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((scan_bf16_kernel<NCH, BQ, RI, false, false>), grid, block, 0, st, p);
+    }
+    return hipGetLastError();
+}
+
+template <int NCH>
+static hipError_t launch_bf16_groups(const ScanArgs& a, const uint16_t* shadow, const float* bq, hipStream_t st) {
+    uint32_t done = 0, slot = 0;
+    while (done < a.b) {
+        const uint32_t left = a.b - done;
+        hipError_t e;
+        uint32_t g;
+        if constexpr (NCH <= 2) {   // (5..7 queries ride the 8-query pass, as in the f32 scan)
+            if (left >= 5) { g = left < 8u ? left : 8u; e = launch_bf16<NCH, 8, 2>(a, shadow, bq, done, g, slot, st); }
+            else if (left >= 4) { g = 4; e = launch_bf16<NCH, 4, 4>(a, shadow, bq, done, g, slot, st); }
+            else if (left >= 2) { g = 2; e = launch_bf16<NCH, 2, 8>(a, shadow, bq, done, g, slot, st); }
+            else { g = 1; e = launch_bf16<NCH, 1, 16>(a, shadow, bq, done, g, slot, st); }
+        } else {
+            if (left >= 2) { g = 2; e = launch_bf16<NCH, 2, 4>(a, shadow, bq, done, g, slot, st); }
+            else { g = 1; e = launch_bf16<NCH, 1, 8>(a, shadow, bq, done, g, slot, st); }
+        }
+        if (e != hipSuccess) return e;
+        done += g;
+        slot = (slot + 1u) % kWorkWords;   // (<= 32 queries: at most 32 passes, the heads never wrap)
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_scan_bf16(const ScanArgs& a, const uint16_t* shadow, const float* bq, hipStream_t st) {
+    if (a.b == 0 || a.n == 0) return hipSuccess;
+    if (a.b > kShadowMaxQ || a.dim % 8u != 0u || a.dim > kShadowMaxDim) return hipErrorInvalidValue;
+    switch ((a.dim + 511u) / 512u) {
+        case 1: return launch_bf16_groups<1>(a, shadow, bq, st);
+        case 2: return launch_bf16_groups<2>(a, shadow, bq, st);
+        case 3: return launch_bf16_groups<3>(a, shadow, bq, st);
+        case 4: return launch_bf16_groups<4>(a, shadow, bq, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+// ---- rescore + certify ------------------------------------------------------------------------------------------
+struct RescoreParams {
+    const float* rows;
+    const float* q;
+    uint32_t dim, kprime, mode, row_base;
+    float thr;
+    const uint64_t* akeys;     // [b, k' + 1]
+    const uint32_t* acounts;   // [b]
+    uint64_t* ekeys;           // [b, k']: exact key of candidate i, 0 = dropped by the f32 epilogue
+};
+
+// One wave per candidate, 4 per workgroup; blockIdx.y = query.  The score is scan_gemv_kernel's for this (row, query):
+// lane owns floats [c*256 + lane*4, +4) of chunk c (clamped address and zero query fragment past a partial last chunk),
+// an (even, odd) packed-FMA chain over the chunks in order, even + odd, then the xor butterfly at distances 32 -> 1 - the
+// tree treduce builds for every RI x BQ (each node adds the same two partial sums; IEEE addition commutes).
+template <int NCH>
+__global__ __launch_bounds__(256) void rescore_kernel(const RescoreParams p) {
+    const int lane = threadIdx.x & 63;
+    const uint32_t qi = blockIdx.y;
+    const uint32_t i = blockIdx.x * 4u + (threadIdx.x >> 6);
+    const uint32_t ac = p.acounts[qi];
+    const uint32_t cnt = ac < p.kprime ? ac : p.kprime;
+    if (i >= cnt) return;   // (wave-uniform)
+    const uint64_t key = p.akeys[(size_t)qi * (p.kprime + 1u) + i];
+    const uint32_t grow = 0xFFFFFFFFu - (uint32_t)key;
+    const uint32_t dim = p.dim;
+    const float* rp = p.rows + (size_t)(grow - p.row_base) * dim;
+    const float* qp = p.q + (size_t)qi * dim;
+    f4 x[NCH], qv[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        const uint32_t idx = (uint32_t)c * 256u + (uint32_t)lane * 4u;
+        const bool in = idx < dim;
+        const uint32_t off = in ? idx : dim - 4u;
+        x[c] = *(const f4*)(rp + off);
+        const f4 v = *(const f4*)(qp + off);
+        qv[c] = in ? v : (f4)(0.f);
+    }
+    f2 acc2 = (f2)(0.f);
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        const f2 xlo = __builtin_shufflevector(x[c], x[c], 0, 1);
+        const f2 xhi = __builtin_shufflevector(x[c], x[c], 2, 3);
+        acc2 = __builtin_elementwise_fma(xlo, __builtin_shufflevector(qv[c], qv[c], 0, 1), acc2);
+        acc2 = __builtin_elementwise_fma(xhi, __builtin_shufflevector(qv[c], qv[c], 2, 3), acc2);
+    }
+    float s = acc2.x + acc2.y;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+    // scan_gemv_kernel's epilogue: non-finite dropped; PIPELINE: clamp(0, 1) then `>= threshold`
+    bool keep = __builtin_fabsf(s) <= 3.4028234664e38f;
+    if (keep && p.mode == 1u) {
+        s = s < 0.f ? 0.f : (s > 1.f ? 1.f : s);
+        keep = s >= p.thr;
+    }
+    if (lane == 0) p.ekeys[(size_t)qi * p.kprime + i] = keep ? pack_key(okey(s), grow) : 0ull;
+}
+
+struct CertifyParams {
+    const uint64_t* ekeys;
+    const uint64_t* akeys;
+    const uint32_t* acounts;
+    uint32_t k, kprime, mode;
+    uint64_t* out_keys;        // [b, k]
+    uint32_t* out_counts;      // [b]
+    uint32_t* cert;            // [b]
+    float bq[kShadowMaxQ];
+};
+
+__global__ __launch_bounds__(1024) void certify_kernel(const CertifyParams p) {
+    __shared__ uint64_t s_keys[kShadowKMax];
+    __shared__ uint64_t s_sorted[kShadowKMax];
+    __shared__ __attribute__((aligned(16))) uint32_t s_ok[kShadowKMax + 4];
+    __shared__ uint32_t s_cnt, s_flag;
+    const uint32_t qi = blockIdx.x;
+    const uint32_t ac = p.acounts[qi];
+    const uint32_t nc = ac < p.kprime ? ac : p.kprime;
+    if (threadIdx.x == 0) s_cnt = 0u;
+    __syncthreads();
+    if (threadIdx.x < nc) {
+        const uint64_t key = p.ekeys[(size_t)qi * p.kprime + threadIdx.x];
+        if (key != 0ull) s_keys[atomicAdd(&s_cnt, 1u)] = key;
+    }
+    __syncthreads();
+    const uint32_t m = s_cnt;
+    rank_sort_keys(s_keys, m, s_sorted, s_ok, &s_flag);
+    const uint32_t k = p.k;
+    const uint32_t outc = m < k ? m : k;
+    for (uint32_t i = threadIdx.x; i < k; i += 1024u) p.out_keys[(size_t)qi * k + i] = (i < outc) ? s_sorted[i] : 0ull;
+    if (threadIdx.x == 0) {
+        p.out_counts[qi] = outc;
+        const float bq = p.bq[qi];
+        bool ok = false;
+        if (__builtin_fabsf(bq) <= 3.4028234664e38f) {
+            if (ac <= p.kprime) ok = true;   // (a) every row the approximate rules keep was rescored
+            else if (m >= k) {               // (b) every outsider j: s_j <= s~_j + B_q <= s~_(k'+1) + B_q < s_(k)
+                float t = key_score(p.akeys[(size_t)qi * (p.kprime + 1u) + p.kprime]) + bq;
+                if (p.mode == 1u) t = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);
+                ok = t < key_score(s_sorted[k - 1u]);
+            }
+        }
+        p.cert[qi] = ok ? 1u : 0u;
+    }
+}
+
+hipError_t launch_rescore_certify(const float* rows, uint32_t dim, const float* q, uint32_t b, uint32_t k, uint32_t kprime,
+                                  uint32_t mode, float thr, uint32_t row_base, const float* bq, const uint64_t* akeys,
+                                  const uint32_t* acounts, uint64_t* ekeys, uint64_t* out_keys, uint32_t* out_counts,
+                                  uint32_t* cert, hipStream_t st) {
+    if (b == 0) return hipSuccess;
+    if (b > kShadowMaxQ || k == 0 || kprime < k || kprime >= kShadowKMax || dim % 8u != 0u || dim > kShadowMaxDim)
+        return hipErrorInvalidValue;
+    RescoreParams rp{rows, q, dim, kprime, mode, row_base, thr, akeys, acounts, ekeys};
+    const dim3 grid((kprime + 3u) / 4u, b), block(256);
+    switch ((dim + 255u) / 256u) {
+        case 1: hipLaunchKernelGGL(rescore_kernel<1>, grid, block, 0, st, rp); break;
+        case 2: hipLaunchKernelGGL(rescore_kernel<2>, grid, block, 0, st, rp); break;
+        case 3: hipLaunchKernelGGL(rescore_kernel<3>, grid, block, 0, st, rp); break;
+        case 4: hipLaunchKernelGGL(rescore_kernel<4>, grid, block, 0, st, rp); break;
+        case 5: hipLaunchKernelGGL(rescore_kernel<5>, grid, block, 0, st, rp); break;
+        case 6: hipLaunchKernelGGL(rescore_kernel<6>, grid, block, 0, st, rp); break;
+        case 7: hipLaunchKernelGGL(rescore_kernel<7>, grid, block, 0, st, rp); break;
+        case 8: hipLaunchKernelGGL(rescore_kernel<8>, grid, block, 0, st, rp); break;
+        default: return hipErrorInvalidValue;
+    }
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    CertifyParams cp{ekeys, akeys, acounts, k, kprime, mode, out_keys, out_counts, cert, {}};
+    for (uint32_t i = 0; i < b; ++i) cp.bq[i] = bq[i];
+    hipLaunchKernelGGL(certify_kernel, dim3(b), dim3(1024), 0, st, cp);
+    return hipGetLastError();
+}
+
+}  // namespace cqs

@@ -21,26 +21,14 @@
 // Wave = 64 lanes.  gfx950 only.
 #include "scan_kernels.h"
 #include "launch_util.h"
+#include "rank_sort.h"
+#include "scan_device.h"
 
 namespace cqs {
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(1))) uint32_t gu32;
-
-// ---- ordered keys ----------------------------------------------------------
-// f32 -> u32 preserving IEEE total order (what Rust's f32::total_cmp sorts by).
-__device__ __forceinline__ uint32_t okey(float x) {
-    uint32_t b = __float_as_uint(x);
-    return b ^ ((b >> 31) ? 0xFFFFFFFFu : 0x80000000u);
-}
-// Dropped entries are stored as -inf: okey(-inf) = 0x007FFFFF.  Every finite
-// score has a larger key; +inf / NaN never reach the score rows.
-constexpr uint32_t kInvalidKey = 0x007FFFFFu;
-
-__device__ __forceinline__ uint64_t pack_key(uint32_t ok, uint32_t global_row) {
-    return ((uint64_t)ok << 32) | (uint64_t)(0xFFFFFFFFu - global_row);
-}
 
 // Histogram bin of a valid score; monotone non-decreasing in the score.
 // linear: 4096 bins of width 2^-11 over [-1,1] (cosine / clamped scores: fine
@@ -66,33 +54,6 @@ __device__ __forceinline__ uint32_t bin_of_range(float s, float lo, float scale)
 }
 __device__ __forceinline__ uint32_t bin_any(float s, uint32_t mode, float lo, float scale) {
     return mode == 2u ? bin_of_range(s, lo, scale) : bin_of(s, mode != 0u);
-}
-
-// ---- transposed butterfly reduction ---------------------------------------
-// v[0..NV) hold per-lane partial sums of NV independent dot products.  After
-// the call v[0] of lane L is the complete sum of product number L / (64/NV).
-// Cost: NV-1 + log2(64/NV) cross-lane ops instead of 6*NV.
-template <int N, int M, int NV>
-__device__ __forceinline__ void treduce_level(float (&v)[NV], int lane) {
-    // Compile-time level (N live values, exchange distance M): a runtime loop over the levels makes
-    // v[i + n/2] a variable index, which hipcc lowers to an NV-way v_cmp/v_cndmask chain per element.
-    if constexpr (N > 1) {
-        const bool hi = (lane & M) != 0;
-#pragma unroll
-        for (int i = 0; i < N / 2; ++i) {
-            const float keep = hi ? v[i + N / 2] : v[i];
-            const float send = hi ? v[i] : v[i + N / 2];
-            v[i] = keep + __shfl_xor(send, M, 64);
-        }
-        treduce_level<N / 2, M / 2, NV>(v, lane);
-    } else if constexpr (M >= 1) {
-        v[0] += __shfl_xor(v[0], M, 64);
-        treduce_level<1, M / 2, NV>(v, lane);
-    }
-}
-template <int NV>
-__device__ __forceinline__ void treduce(float (&v)[NV], int lane) {
-    treduce_level<NV, 32, NV>(v, lane);
 }
 
 // ---- block-wide "find the bin holding the k-th largest" ---------------------
@@ -644,46 +605,9 @@ __global__ __launch_bounds__(1024) void select_finish_kernel(const float* __rest
     if (dbg && threadIdx.x == 0 && blockIdx.x == 0) { dbg[8] = ng; dbg[9] = count; }
     const uint64_t* sorted = s_keys;
     if (count <= 1024u) {
-        // Rank sort: the keys are distinct, so rank(i) = #{j : key[j] > key[i]} is a permutation.
-        // One key per thread, count broadcast LDS reads, no barriers inside the loop.
-        // Round 5: the ranks are taken on the keys' TOP HALVES (the ordered score bits), four per 16-byte LDS read:
-        // 1 read + 4 compares + 4 adds per four keys instead of 4 reads + 4 64-bit compares + 8 (7 -> ~3 us at 510 keys).
-        // Two equal scores among the candidates get the same rank and leave a hole in the output - detected below, and
-        // only then are the ranks retaken on the full keys (exact: scores equal in all 32 bits are duplicates or ties).
         uint64_t* s_sorted = reinterpret_cast<uint64_t*>(s_groups);  // group list is dead by now
         uint32_t* s_ok = s_hist;                                      // histogram is dead by now (slow_select included)
-        __syncthreads();
-        const uint32_t cpad = (count + 3u) & ~3u;
-        if (threadIdx.x < cpad) s_ok[threadIdx.x] = threadIdx.x < count ? (uint32_t)(s_keys[threadIdx.x] >> 32) : 0u;
-        if (threadIdx.x < count) s_sorted[threadIdx.x] = 0ull;       // (no valid key is 0)
-        if (threadIdx.x == 0) s_res[0] = 0u;
-        __syncthreads();
-        if (threadIdx.x < count) {
-            const uint64_t mine = s_keys[threadIdx.x];
-            const uint32_t mh = (uint32_t)(mine >> 32);
-            uint32_t rank = 0;
-#pragma unroll 8
-            for (uint32_t j = 0; j < cpad; j += 4u) {                 // (unrolled: eight 16-byte reads in flight, not one)
-                const uint4 o = *reinterpret_cast<const uint4*>(&s_ok[j]);
-                rank += (o.x > mh) ? 1u : 0u;
-                rank += (o.y > mh) ? 1u : 0u;
-                rank += (o.z > mh) ? 1u : 0u;
-                rank += (o.w > mh) ? 1u : 0u;
-            }
-            s_sorted[rank] = mine;
-        }
-        __syncthreads();
-        if (threadIdx.x < count && s_sorted[threadIdx.x] == 0ull) s_res[0] = 1u;   // a hole: two candidates share their score bits
-        __syncthreads();
-        if (s_res[0] != 0u) {
-            if (threadIdx.x < count) {
-                const uint64_t mine = s_keys[threadIdx.x];
-                uint32_t rank = 0;
-                for (uint32_t j = 0; j < count; ++j) rank += (s_keys[j] > mine) ? 1u : 0u;
-                s_sorted[rank] = mine;
-            }
-            __syncthreads();
-        }
+        rank_sort_keys(s_keys, count, s_sorted, s_ok, s_res);         // (rank_sort.h, shared with the bf16 certify kernel)
         sorted = s_sorted;
     } else {
         // Bitonic sort, descending (slow path sizes: up to kCandCap).

@@ -452,6 +452,20 @@ class HipIndex(VectorIndex):
         self._lib.cqs_hip_index_combine_stats(self._h, C.byref(p), C.byref(q))
         return int(p.value), int(q.value)
 
+    def set_bf16_scan(self, enable: bool) -> None:
+        """Build / free the bf16 shadow of the corpus (`cqs_hip_index_set_bf16_scan`).  Answers stay byte-identical; host
+        searches that run as gemv passes read half the bytes.  Raises HipError (INVALID: sharded or borrowed handle,
+        dim % 8 != 0, dim > 2048, a finite row with a component >= 2^64; NOMEM); the index stays usable either way."""
+        rc = self._lib.cqs_hip_index_set_bf16_scan(self._h, 1 if enable else 0)
+        if rc != _lib.OK:
+            raise HipError(rc, self.last_error())
+
+    def bf16_stats(self) -> Tuple[int, int, int]:
+        """(shadow bytes, 0 = off; queries answered by the certified path; queries that fell back to the f32 scan)."""
+        b, c, f = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._lib.cqs_hip_index_bf16_stats(self._h, C.byref(b), C.byref(c), C.byref(f))
+        return int(b.value), int(c.value), int(f.value)
+
     def set_timing(self, on: bool) -> None:
         self._lib.cqs_hip_index_set_timing(self._h, 1 if on else 0)
 

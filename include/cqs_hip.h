@@ -229,6 +229,23 @@ size_t cqs_hip_merge_keys(const uint64_t* lists, const uint32_t* counts, size_t 
  * NULL.  Diagnostic; not part of the VectorIndex trait. */
 void cqs_hip_index_combine_stats(const cqs_hip_index* idx, uint64_t* passes, uint64_t* queries);
 
+/* ---- bf16 shadow scan --------------------------------------------------------
+ * Build (enable != 0) or free (enable == 0) a bf16 copy of the corpus that host searches scan first.
+ * Answers are unchanged byte for byte: the shadow picks candidates, their f32 rows are rescored with the
+ * f32 scan's own arithmetic, and a query whose answer cannot be proven to be the f32 scan's is re-run on
+ * it in the same call.  Costs n x dim x 2 B of device memory.  Off by default.
+ * CQS_HIP_OK | CQS_HIP_ERR_INVALID (sharded or borrowed handle, dim % 8 != 0, dim > 2048, a finite row with
+ * a component of magnitude >= 2^64; reason in last_error) | CQS_HIP_ERR_NOMEM.  The index stays usable on
+ * the f32 path after any failure.
+ * Scope: `cqs_hip_index_search` blocks that run as gemv passes (b <= 8, and the combining queue's exact
+ * blocks); matrix-core blocks, `cqs_hip_index_search_device`, `cqs_hip_index_neighbors` and sharded handles
+ * are unchanged.  `extend` converts the new rows (an outlier row there turns the shadow off); save / load do
+ * not persist it (enable again after load). */
+int32_t cqs_hip_index_set_bf16_scan(cqs_hip_index* idx, int32_t enable);
+/* bytes of the shadow (0 = off); queries answered by the certified path; queries that fell back to the f32
+ * scan.  Any pointer may be NULL. */
+void cqs_hip_index_bf16_stats(const cqs_hip_index* idx, uint64_t* bytes, uint64_t* certified, uint64_t* fallbacks);
+
 /* ---- profiling aid ---------------------------------------------------------
  * With timing enabled every search brackets its dominant scan kernel launch(es)
  * with a HIP event pair on the launch stream (up to 4096 pairs between reads).

@@ -79,6 +79,8 @@ extern "C" {
     fn cqs_hip_index_max_k(idx: *const CqsHipIndex) -> u32;
     fn cqs_hip_index_poisoned(idx: *const CqsHipIndex) -> i32;
     fn cqs_hip_index_last_error(idx: *const CqsHipIndex, buf: *mut c_char, cap: usize) -> usize;
+    fn cqs_hip_index_set_bf16_scan(idx: *mut CqsHipIndex, enable: i32) -> i32;
+    fn cqs_hip_index_bf16_stats(idx: *const CqsHipIndex, bytes: *mut u64, certified: *mut u64, fallbacks: *mut u64);
     fn cqs_hip_index_search(
         idx: *mut CqsHipIndex,
         queries: *const f32,
@@ -149,7 +151,28 @@ fn hip_persist_enabled() -> bool {
     !matches!(std::env::var("CQS_HIP_PERSIST").as_deref(), Ok("0") | Ok("false") | Ok("off"))
 }
 
+fn hip_bf16_scan_enabled() -> bool {
+    // opt-in: a bf16 shadow of the corpus (n x dim x 2 B more device memory), same answers, about half the bytes per search
+    matches!(std::env::var("CQS_HIP_SCAN_BF16").as_deref(), Ok("1"))
+}
+
 impl HipIndex {
+    /// `CQS_HIP_SCAN_BF16=1`: build the bf16 shadow that host searches scan first (answers unchanged byte for byte).  A
+    /// handle that cannot take it (row-sharded, dim % 8 != 0, an outlier row, no memory) keeps searching on the f32 scan.
+    fn enable_bf16_scan_from_env(&self) {
+        if !hip_bf16_scan_enabled() {
+            return;
+        }
+        let rc = unsafe { cqs_hip_index_set_bf16_scan(self.handle, 1) };
+        if rc != CQS_HIP_OK {
+            tracing::warn!(rc, error = %self.last_error(), "HIP bf16 shadow scan not enabled; searching the f32 rows");
+        } else {
+            let mut bytes = 0u64;
+            unsafe { cqs_hip_index_bf16_stats(self.handle, &mut bytes, std::ptr::null_mut(), std::ptr::null_mut()) };
+            tracing::info!(bytes, "HIP bf16 shadow scan enabled");
+        }
+    }
+
     /// `CagraIndex::gpu_available_for` analogue (src/cagra.rs:336-376): every listed device must exist and hold its
     /// shard (corpus / devices + score scratch headroom).
     pub fn gpu_available_for(n: usize, dim: usize, devices: &[i32]) -> bool {
@@ -506,6 +529,7 @@ impl<Mode: ClearHnswDirty> IndexBackend<Mode> for HipBackend {
                 Ok(idx) => {
                     tracing::info!(backend = "hip", source = "persisted", vectors = idx.len(), chunk_count, threshold,
                         "Vector index backend selected");
+                    idx.enable_bf16_scan_from_env();   // (the blob does not hold the shadow)
                     return Ok(Some(Box::new(idx) as Box<dyn VectorIndex>));
                 }
                 Err(e) => {
@@ -531,6 +555,7 @@ impl<Mode: ClearHnswDirty> IndexBackend<Mode> for HipBackend {
                         tracing::warn!(error = %e, path = %blob.display(), "Failed to persist HIP index (will rebuild next restart)");
                     }
                 }
+                idx.enable_bf16_scan_from_env();
                 Ok(Some(Box::new(idx) as Box<dyn VectorIndex>))
             }
             Err(e) => {
