@@ -111,7 +111,8 @@ uint32_t max_query_block(const cqs_hip_index* x) {
 
 // Enqueue scan + select for queries already on the device.  Caller holds mu.
 int32_t enqueue_search(cqs_hip_index* x, const float* d_q, uint32_t b, uint32_t k, const uint32_t* d_keep,
-                       uint32_t mode, float thr, uint64_t* d_out_keys, uint32_t* d_out_counts, hipStream_t st, bool gemv_only) {
+                       uint32_t mode, float thr, uint64_t* d_out_keys, uint32_t* d_out_counts, hipStream_t st, bool gemv_only,
+                       const uint32_t* gate) {
     // the previous search may still be running on another stream and owns the same scratch
     if (x->done_valid && x->done_stream != st) HIP_TRY(x, hipStreamWaitEvent(st, x->done, 0));
     if (!gemv_only && cqs::use_mfma(b, x->dim)) {
@@ -145,7 +146,8 @@ int32_t enqueue_search(cqs_hip_index* x, const float* d_q, uint32_t b, uint32_t 
     a.dbg = x->d_dbg;
     a.gemv_only = gemv_only;
     a.tiers = cqs::plan_tiers(a.n_pad, x->n_cu, !gemv_only && cqs::uniform_groups(b, x->dim));
-    const bool timed = x->timing && x->ev_used + 2 <= kMaxTimingEvents;
+    a.gate = gate;
+    const bool timed = !gate && x->timing && x->ev_used + 2 <= kMaxTimingEvents;   // (gated: the shadow scan was timed)
     if (timed) {
         while (x->ev.size() < x->ev_used + 2) {
             hipEvent_t e = nullptr;
@@ -223,12 +225,28 @@ int32_t create_common(uint64_t n, uint32_t dim, uint32_t metric, int32_t device,
     return CQS_HIP_OK;
 }
 
-// ---- bf16 shadow (cqs_hip_index_set_bf16_scan) ---------------------------------------------------------------------
+// ---- bf16 shadow (create / load policy, cqs_hip_index_set_bf16_scan) -----------------------------------------------
+// What the device-API searches' certify launches counted (d_shadow_stats[3, 5): certified, fallbacks).  Caller holds mu,
+// every search has completed (quiesce).
+static bool shadow_device_counts(cqs_hip_index* x, unsigned long long (&c)[2]) {
+    c[0] = c[1] = 0;
+    if (!x->d_shadow_stats) return true;
+    hipError_t e = hipMemcpyAsync(c, x->d_shadow_stats + 3, sizeof c, hipMemcpyDeviceToHost, x->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(x->stream);
+    if (e != hipSuccess) { (void)hipGetLastError(); c[0] = c[1] = 0; return false; }
+    return true;
+}
+
 void shadow_free(cqs_hip_index* x) {
+    unsigned long long c[2];
+    if (x->d_shadow_stats && quiesce(x) == hipSuccess && shadow_device_counts(x, c)) {   // the counts outlive the shadow
+        x->stat_certified.fetch_add(c[0], std::memory_order_relaxed);
+        x->stat_fallbacks.fetch_add(c[1], std::memory_order_relaxed);
+    }
     hipFree(x->d_shadow); hipFree(x->d_shadow_stats); hipFree(x->d_akeys); hipFree(x->d_acounts); hipFree(x->d_ekeys);
-    hipFree(x->d_cert); hipHostFree(x->h_cert);
+    hipFree(x->d_cert); hipFree(x->d_bq); hipHostFree(x->h_cert);
     x->d_shadow = nullptr; x->d_shadow_stats = nullptr; x->d_akeys = nullptr; x->d_acounts = nullptr; x->d_ekeys = nullptr;
-    x->d_cert = nullptr; x->h_cert = nullptr; x->h_cert_dev = nullptr;
+    x->d_cert = nullptr; x->d_bq = nullptr; x->h_cert = nullptr; x->h_cert_dev = nullptr;
     x->shadow_cap = 0; x->shadow_r = 0.0; x->shadow_norm = 0.0;
 }
 
@@ -278,6 +296,126 @@ int32_t shadow_extend(cqs_hip_index* x, uint64_t n_old) {
     return CQS_HIP_OK;
 }
 
+// Allocate and build the shadow over rows [0, n) (no borrow check: the create policy snapshots borrowed rows too).  On
+// failure the shadow is freed and `fail` has put `what: reason` in last_error.  Caller holds mu (or owns the new handle).
+static int32_t shadow_enable(cqs_hip_index* x, const char* what) {
+    std::string pre(what);
+    if (x->dim % 8u != 0u || x->dim > cqs::kShadowMaxDim)
+        return fail(x, CQS_HIP_ERR_INVALID, (pre + ": dim must be a multiple of 8 and <= 2048").c_str());
+    if (x->d_shadow) return CQS_HIP_OK;
+    const uint64_t cap = x->cap_rows ? x->cap_rows : 1;
+    auto oom = [&](hipError_t e) { (void)hipGetLastError(); shadow_free(x); return fail(x, CQS_HIP_ERR_NOMEM, (pre + ": allocation").c_str(), e); };
+    hipError_t e;
+    if ((e = hipMalloc(&x->d_shadow, (size_t)cap * x->dim * sizeof(uint16_t))) != hipSuccess) return oom(e);
+    x->shadow_cap = cap;
+    unsigned long long* stats = nullptr;   // zeroed before it is the handle's: shadow_free reads its counts
+    if ((e = hipMalloc(&stats, 5 * sizeof(unsigned long long))) != hipSuccess) return oom(e);
+    if ((e = hipMemsetAsync(stats, 0, 5 * sizeof(unsigned long long), x->stream)) != hipSuccess) { hipFree(stats); return oom(e); }
+    x->d_shadow_stats = stats;
+    if ((e = hipMalloc(&x->d_akeys, (size_t)cqs::kShadowMaxQ * kMaxK * sizeof(uint64_t))) != hipSuccess) return oom(e);
+    if ((e = hipMalloc(&x->d_acounts, (size_t)cqs::kShadowMaxQ * sizeof(uint32_t))) != hipSuccess) return oom(e);
+    if ((e = hipMalloc(&x->d_ekeys, (size_t)cqs::kShadowMaxQ * (kMaxK - 1) * sizeof(uint64_t))) != hipSuccess) return oom(e);
+    if ((e = hipMalloc(&x->d_cert, (size_t)cqs::kShadowMaxQ * sizeof(uint32_t))) != hipSuccess) return oom(e);
+    if ((e = hipMalloc(&x->d_bq, (size_t)cqs::kShadowMaxQ * sizeof(float))) != hipSuccess) return oom(e);
+    if ((e = hipHostMalloc(&x->h_cert, (size_t)cqs::kShadowMaxQ * sizeof(uint32_t), hipHostMallocDefault)) != hipSuccess) return oom(e);
+    if (hipHostGetDevicePointer((void**)&x->h_cert_dev, x->h_cert, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        x->h_cert_dev = nullptr;
+    }
+    bool outlier = false;
+    const int32_t rc = shadow_convert(x, 0, &outlier);
+    if (rc != CQS_HIP_OK) { shadow_free(x); return rc; }
+    if (outlier) {
+        shadow_free(x);
+        return fail(x, CQS_HIP_ERR_INVALID, (pre + ": a finite row has a component of magnitude >= 2^64").c_str());
+    }
+    return CQS_HIP_OK;
+}
+
+// The shadow policy of create / create_device / load, for a single-device handle whose rows are in place.
+// CQS_HIP_SCAN_BF16 (read here, at create): unset = where it pays (f32 corpus >= kShadowAutoBytes), 0 = never, 1 = at any
+// size; dim, outlier and free-memory rules either way.  The create never fails for the shadow's sake: the handle then
+// searches the f32 rows and last_error says why.  Returns an error only for a device fault (the handle is poisoned).
+static int32_t shadow_auto(cqs_hip_index* x) {
+    const char* env = getenv("CQS_HIP_SCAN_BF16");
+    if (env && env[0] == '0') return CQS_HIP_OK;
+    const bool any_size = env && env[0] == '1';
+    const uint64_t f32_bytes = x->n * x->dim * sizeof(float);
+    if (!any_size && f32_bytes < kShadowAutoBytes) {
+        x->last_error = "bf16 shadow not built: f32 corpus below 1 GiB (CQS_HIP_SCAN_BF16=1 builds it at any size)";
+        return CQS_HIP_OK;
+    }
+    if (x->dim % 8u != 0u || x->dim > cqs::kShadowMaxDim) {
+        x->last_error = "bf16 shadow not built: dim must be a multiple of 8 and <= 2048";
+        return CQS_HIP_OK;
+    }
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
+        (void)hipGetLastError();
+        x->last_error = "bf16 shadow not built: hipMemGetInfo failed";
+        return CQS_HIP_OK;
+    }
+    const uint64_t cap = x->cap_rows ? x->cap_rows : 1;
+    const uint64_t need = cap * x->dim * sizeof(uint16_t) + (2ull * kMaxK + 2ull) * cqs::kShadowMaxQ * sizeof(uint64_t);
+    const uint64_t frac = (uint64_t)(kShadowFreeFrac * (double)total_b);
+    const uint64_t reserve = frac > kShadowFreeMinBytes ? frac : kShadowFreeMinBytes;
+    if (free_b < need || free_b - need < reserve) {
+        x->last_error = "bf16 shadow not built: the device would keep less than max(4 GiB, 10 %) of its memory free";
+        return CQS_HIP_OK;
+    }
+    const int32_t rc = shadow_enable(x, "bf16 shadow not built");
+    return rc == CQS_HIP_ERR_DEVICE ? rc : CQS_HIP_OK;
+}
+
+// The shadow half of a gemv block, enqueued on `st`: B_q of each query -> shadow scan -> select k' + 1 -> rescore +
+// certify into out_keys / out_counts / cert (counters: nullable, certify's device counts).  d_q [nb, dim] on the device.
+// Caller holds mu and has ordered `st` after the last search.
+static int32_t enqueue_shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k, const uint32_t* d_keep,
+                                   uint32_t mode, float threshold, uint64_t* out_keys, uint32_t* out_counts, uint32_t* cert,
+                                   unsigned long long* counters, hipStream_t st) {
+    const uint32_t kp = cqs::shadow_kprime(k);
+    HIP_TRY(x, cqs::launch_shadow_bound(d_q, nb, x->dim, x->shadow_r, x->shadow_norm, x->d_bq, st));
+    cqs::ScanArgs a;
+    a.rows = x->d_rows;
+    a.n = (uint32_t)x->n;
+    a.n_pad = (uint32_t)pad_rows(x->n);
+    a.dim = x->dim;
+    a.q = d_q;
+    a.b = nb;
+    a.scores = x->d_scores;
+    a.keep = d_keep;
+    a.mode = mode;
+    a.threshold = threshold;
+    a.nontemporal = x->n * x->dim * sizeof(uint16_t) > kNtBytes;
+    a.linear_bins = (x->metric == CQS_HIP_METRIC_COSINE) || (mode == CQS_HIP_MODE_PIPELINE);
+    a.k = kp + 1u;
+    a.gmax = x->d_gmax;
+    a.gaux = a.k >= kGauxMinK ? x->d_gaux : nullptr;
+    a.work = x->d_work;
+    a.n_cu = x->n_cu;
+    a.dbg = nullptr;
+    a.gemv_only = true;
+    a.tiers = cqs::plan_tiers(a.n_pad, x->n_cu, false);
+    const bool timed = x->timing && x->ev_used + 2 <= kMaxTimingEvents;
+    if (timed) {
+        while (x->ev.size() < x->ev_used + 2) {
+            hipEvent_t e = nullptr;
+            HIP_TRY(x, hipEventCreate(&e));
+            x->ev.push_back(e);
+        }
+        HIP_TRY(x, hipEventRecord(x->ev[x->ev_used], st));
+    }
+    HIP_TRY(x, cqs::launch_scan_bf16(a, x->d_shadow, x->d_bq, st));
+    if (timed) {
+        HIP_TRY(x, hipEventRecord(x->ev[x->ev_used + 1], st));
+        x->ev_used += 2;
+    }
+    HIP_TRY(x, cqs::launch_select(a, (uint32_t)x->row_base, x->d_akeys, x->d_acounts, st));
+    HIP_TRY(x, cqs::launch_rescore_certify(x->d_rows, x->dim, d_q, nb, k, kp, mode, threshold, (uint32_t)x->row_base, x->d_bq,
+                                           x->d_akeys, x->d_acounts, x->d_ekeys, out_keys, out_counts, cert, counters, st));
+    return CQS_HIP_OK;
+}
+
 }  // namespace cqs_idx
 
 using namespace cqs_idx;
@@ -301,8 +439,10 @@ int32_t cqs_hip_device_mem(int32_t device, uint64_t* free_bytes, uint64_t* total
     return CQS_HIP_OK;
 } CQS_ABI_CATCH_NOHANDLE
 
-int32_t cqs_hip_index_create(const float* rows, uint64_t n, uint32_t dim, uint32_t metric, int32_t device,
-                             uint64_t row_base, cqs_hip_index** out) CQS_ABI_TRY {
+}  // extern "C"
+
+int32_t cqs_idx::create_owned(const float* rows, uint64_t n, uint32_t dim, uint32_t metric, int32_t device,
+                              uint64_t row_base, cqs_hip_index** out) {
     if (n > 0 && !rows) return CQS_HIP_ERR_INVALID;
     cqs_hip_index* x = nullptr;
     int32_t rc = create_common(n, dim, metric, device, row_base, out, &x);
@@ -318,6 +458,18 @@ int32_t cqs_hip_index_create(const float* rows, uint64_t n, uint32_t dim, uint32
     }
     *out = x;
     return CQS_HIP_OK;
+}
+
+extern "C" {
+
+int32_t cqs_hip_index_create(const float* rows, uint64_t n, uint32_t dim, uint32_t metric, int32_t device,
+                             uint64_t row_base, cqs_hip_index** out) CQS_ABI_TRY {
+    cqs_hip_index* x = nullptr;
+    int32_t rc = create_owned(rows, n, dim, metric, device, row_base, &x);
+    if (rc != CQS_HIP_OK) return rc;
+    if ((rc = shadow_auto(x)) != CQS_HIP_OK) { cqs_hip_index_destroy(x); return rc; }
+    *out = x;
+    return CQS_HIP_OK;
 } CQS_ABI_CATCH_NOHANDLE
 
 int32_t cqs_hip_index_create_device(const void* d_rows, uint64_t n, uint32_t dim, uint32_t metric, int32_t device,
@@ -327,6 +479,9 @@ int32_t cqs_hip_index_create_device(const void* d_rows, uint64_t n, uint32_t dim
     cqs_hip_index* x = nullptr;
     int32_t rc = create_common(n, dim, metric, device, row_base, out, &x);
     if (rc != CQS_HIP_OK) return rc;
+    // The rows may still be in flight from the caller's own streams (torch's null stream, say), which the handle's
+    // non-blocking stream does not order after: wait for the device before the copy or the shadow build reads them.
+    if (n && hipDeviceSynchronize() != hipSuccess) { cqs_hip_index_destroy(x); return CQS_HIP_ERR_DEVICE; }
     if (borrow) {
         x->borrow = true;
         x->d_rows = (float*)d_rows;
@@ -342,6 +497,8 @@ int32_t cqs_hip_index_create_device(const void* d_rows, uint64_t n, uint32_t dim
             return e == hipErrorOutOfMemory ? CQS_HIP_ERR_NOMEM : CQS_HIP_ERR_DEVICE;
         }
     }
+    // borrowed: the shadow is a snapshot of the caller's rows, which the header requires to stay unmodified
+    if ((rc = shadow_auto(x)) != CQS_HIP_OK) { cqs_hip_index_destroy(x); return rc; }
     *out = x;
     return CQS_HIP_OK;
 } CQS_ABI_CATCH_NOHANDLE
@@ -569,6 +726,7 @@ int32_t cqs_hip_index_load(const char* path, uint32_t expected_dim, uint64_t exp
         return CQS_HIP_ERR_NOMEM;
     }
     rc = read_blob_into(fd, checksum, expected_dim, {Segment{device, x->d_rows, rows, x->stream}});
+    if (rc == CQS_HIP_OK) rc = shadow_auto(x);   // (the shadow is never persisted: rebuilt from the loaded rows)
     if (rc != CQS_HIP_OK) { cqs_hip_index_destroy(x); return rc; }
     *out = x;
     return CQS_HIP_OK;
@@ -665,6 +823,18 @@ int32_t cqs_hip_index_search_device(cqs_hip_index* x, const float* d_queries, ui
     }
     int32_t rc = ensure_scratch(x, b, k);
     if (rc != CQS_HIP_OK) return rc;
+    if (x->d_shadow && b <= cqs::kShadowMaxQ && !cqs::use_mfma(b, x->dim) && cqs::shadow_kprime(k) >= k) {
+        // Through the bf16 shadow, with no host sync: certify writes the answers into the caller's buffers and its verdicts
+        // into d_cert; the f32 scan + select that follow are gated by d_cert and return at entry when every query of the
+        // block is certified.  Otherwise they recompute the whole block, which is harmless: gemv-pass scores do not depend
+        // on which queries share a pass, and a certified answer is the f32 answer.
+        if (x->done_valid && x->done_stream != st) HIP_TRY(x, hipStreamWaitEvent(st, x->done, 0));
+        rc = enqueue_shadow_pass(x, d_queries, b, k, d_keep_bitset, mode, threshold, d_out_keys, d_out_counts, x->d_cert,
+                                 x->d_shadow_stats + 3, st);
+        if (rc != CQS_HIP_OK) return rc;
+        // (records `done` after the gated select: the cross-stream hand-off covers d_bq, d_akeys, d_ekeys and d_cert too)
+        return enqueue_search(x, d_queries, b, k, d_keep_bitset, mode, threshold, d_out_keys, d_out_counts, st, false, x->d_cert);
+    }
     return enqueue_search(x, d_queries, b, k, d_keep_bitset, mode, threshold, d_out_keys, d_out_counts, st);
 } CQS_ABI_CATCH(x)
 
@@ -739,57 +909,13 @@ static int32_t f32_block(cqs_hip_index* x, const HostQuery* qs, const uint32_t* 
 // scan).  Caller holds mu; h_q[0, nb) holds the staged queries of qs[q0, q0 + nb).
 static int32_t shadow_block(cqs_hip_index* x, const HostQuery* qs, uint32_t q0, const uint8_t* bad, uint32_t nb, uint32_t k_eff,
                             const uint32_t* d_keep, uint32_t mode, float threshold, std::vector<uint32_t>& redo) {
-    const uint32_t kp = cqs::shadow_kprime(k_eff);
-    float bq[cqs::kShadowMaxQ];
-    for (uint32_t i = 0; i < nb; ++i) {
-        const float* q = x->h_q + (size_t)i * x->dim;
-        double s2 = 0.0;
-        for (uint32_t d = 0; d < x->dim; ++d) s2 += (double)q[d] * (double)q[d];
-        bq[i] = cqs::shadow_query_bound(s2, x->shadow_r, x->shadow_norm, x->dim);
-    }
     hipStream_t st = x->stream;
     HIP_TRY(x, hipMemcpyAsync(x->d_q, x->h_q, (size_t)nb * x->dim * sizeof(float), hipMemcpyHostToDevice, st));
-    cqs::ScanArgs a;
-    a.rows = x->d_rows;
-    a.n = (uint32_t)x->n;
-    a.n_pad = (uint32_t)pad_rows(x->n);
-    a.dim = x->dim;
-    a.q = x->d_q;
-    a.b = nb;
-    a.scores = x->d_scores;
-    a.keep = d_keep;
-    a.mode = mode;
-    a.threshold = threshold;
-    a.nontemporal = x->n * x->dim * sizeof(uint16_t) > kNtBytes;
-    a.linear_bins = (x->metric == CQS_HIP_METRIC_COSINE) || (mode == CQS_HIP_MODE_PIPELINE);
-    a.k = kp + 1u;
-    a.gmax = x->d_gmax;
-    a.gaux = a.k >= kGauxMinK ? x->d_gaux : nullptr;
-    a.work = x->d_work;
-    a.n_cu = x->n_cu;
-    a.dbg = nullptr;
-    a.gemv_only = true;
-    a.tiers = cqs::plan_tiers(a.n_pad, x->n_cu, false);
-    const bool timed = x->timing && x->ev_used + 2 <= kMaxTimingEvents;
-    if (timed) {
-        while (x->ev.size() < x->ev_used + 2) {
-            hipEvent_t e = nullptr;
-            HIP_TRY(x, hipEventCreate(&e));
-            x->ev.push_back(e);
-        }
-        HIP_TRY(x, hipEventRecord(x->ev[x->ev_used], st));
-    }
-    HIP_TRY(x, cqs::launch_scan_bf16(a, x->d_shadow, bq, st));
-    if (timed) {
-        HIP_TRY(x, hipEventRecord(x->ev[x->ev_used + 1], st));
-        x->ev_used += 2;
-    }
-    HIP_TRY(x, cqs::launch_select(a, (uint32_t)x->row_base, x->d_akeys, x->d_acounts, st));
     const bool direct = x->h_out_keys_dev && x->h_out_counts_dev && (size_t)nb * k_eff <= kDirectOutKeys;
-    HIP_TRY(x, cqs::launch_rescore_certify(x->d_rows, x->dim, x->d_q, nb, k_eff, kp, mode, threshold, (uint32_t)x->row_base, bq,
-                                           x->d_akeys, x->d_acounts, x->d_ekeys, direct ? x->h_out_keys_dev : x->d_out_keys,
-                                           direct ? x->h_out_counts_dev : x->d_out_counts,
-                                           x->h_cert_dev ? x->h_cert_dev : x->d_cert, st));
+    int32_t rc = enqueue_shadow_pass(x, x->d_q, nb, k_eff, d_keep, mode, threshold, direct ? x->h_out_keys_dev : x->d_out_keys,
+                                     direct ? x->h_out_counts_dev : x->d_out_counts, x->h_cert_dev ? x->h_cert_dev : x->d_cert,
+                                     nullptr, st);
+    if (rc != CQS_HIP_OK) return rc;
     HIP_TRY(x, hipEventRecord(x->done, st));
     x->done_stream = st;
     x->done_valid = true;
@@ -1071,43 +1197,25 @@ int32_t cqs_hip_index_set_bf16_scan(cqs_hip_index* x, int32_t enable) CQS_ABI_TR
     HIP_TRY(x, hipSetDevice(x->device));
     HIP_TRY(x, quiesce(x));   // a search enqueued on a caller stream may still read the shadow
     if (!enable) { shadow_free(x); return CQS_HIP_OK; }
+    // a borrowed handle gets its shadow at create or not at all: enabling it later would snapshot rows the caller may have
+    // changed since (test_invalid_handles); disabling above works on every handle
     if (x->borrow) return fail(x, CQS_HIP_ERR_INVALID, "set_bf16_scan: index borrows its rows (they may change under the bound)");
-    if (x->dim % 8u != 0u || x->dim > cqs::kShadowMaxDim)
-        return fail(x, CQS_HIP_ERR_INVALID, "set_bf16_scan: dim must be a multiple of 8 and <= 2048");
-    if (x->d_shadow) return CQS_HIP_OK;
-    const uint64_t cap = x->cap_rows ? x->cap_rows : 1;
-    auto oom = [&](hipError_t e) { (void)hipGetLastError(); shadow_free(x); return fail(x, CQS_HIP_ERR_NOMEM, "set_bf16_scan: allocation", e); };
-    hipError_t e;
-    if ((e = hipMalloc(&x->d_shadow, (size_t)cap * x->dim * sizeof(uint16_t))) != hipSuccess) return oom(e);
-    x->shadow_cap = cap;
-    if ((e = hipMalloc(&x->d_shadow_stats, 3 * sizeof(unsigned long long))) != hipSuccess) return oom(e);
-    if ((e = hipMalloc(&x->d_akeys, (size_t)cqs::kShadowMaxQ * kMaxK * sizeof(uint64_t))) != hipSuccess) return oom(e);
-    if ((e = hipMalloc(&x->d_acounts, (size_t)cqs::kShadowMaxQ * sizeof(uint32_t))) != hipSuccess) return oom(e);
-    if ((e = hipMalloc(&x->d_ekeys, (size_t)cqs::kShadowMaxQ * (kMaxK - 1) * sizeof(uint64_t))) != hipSuccess) return oom(e);
-    if ((e = hipMalloc(&x->d_cert, (size_t)cqs::kShadowMaxQ * sizeof(uint32_t))) != hipSuccess) return oom(e);
-    if ((e = hipHostMalloc(&x->h_cert, (size_t)cqs::kShadowMaxQ * sizeof(uint32_t), hipHostMallocDefault)) != hipSuccess) return oom(e);
-    if (hipHostGetDevicePointer((void**)&x->h_cert_dev, x->h_cert, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        x->h_cert_dev = nullptr;
-    }
-    if ((e = hipMemsetAsync(x->d_shadow_stats, 0, 3 * sizeof(unsigned long long), x->stream)) != hipSuccess) { shadow_free(x); HIP_TRY(x, e); }
-    bool outlier = false;
-    const int32_t rc = shadow_convert(x, 0, &outlier);
-    if (rc != CQS_HIP_OK) { shadow_free(x); return rc; }
-    if (outlier) {
-        shadow_free(x);
-        return fail(x, CQS_HIP_ERR_INVALID, "set_bf16_scan: a finite row has a component of magnitude >= 2^64");
-    }
-    return CQS_HIP_OK;
+    return shadow_enable(x, "set_bf16_scan");
 } CQS_ABI_CATCH(x)
 
 void cqs_hip_index_bf16_stats(const cqs_hip_index* x, uint64_t* bytes, uint64_t* certified, uint64_t* fallbacks) CQS_ABI_TRY {
     uint64_t by = 0, c = 0, f = 0;
     if (x && !x->sh) {
-        std::lock_guard<std::mutex> g(x->mu);
-        by = x->d_shadow ? x->shadow_cap * x->dim * sizeof(uint16_t) : 0;
-        c = x->stat_certified.load(std::memory_order_relaxed);
-        f = x->stat_fallbacks.load(std::memory_order_relaxed);
+        cqs_hip_index* m = const_cast<cqs_hip_index*>(x);   // (waits for the device-API searches whose counts it reads)
+        std::lock_guard<std::mutex> g(m->mu);
+        by = m->d_shadow ? m->shadow_cap * m->dim * sizeof(uint16_t) : 0;
+        c = m->stat_certified.load(std::memory_order_relaxed);
+        f = m->stat_fallbacks.load(std::memory_order_relaxed);
+        unsigned long long dc[2];
+        if (m->d_shadow_stats && hipSetDevice(m->device) == hipSuccess && quiesce(m) == hipSuccess && shadow_device_counts(m, dc)) {
+            c += dc[0];
+            f += dc[1];
+        }
     }
     if (bytes) *bytes = by;
     if (certified) *certified = c;
@@ -1189,6 +1297,32 @@ int32_t cqs_hip_index_scan_time(cqs_hip_index* x, uint32_t* launches, double* to
 void cqs_hip_debug_index_fail_next(cqs_hip_index* x) CQS_ABI_TRY {
     if (x) x->inject_fail.store(1, std::memory_order_release);
 } CQS_ABI_CATCH_VOID
+
+// Test hook (not part of the public header): B_q of `b` host queries [b, dim] as the device computes it for a device-API
+// search (launch_shadow_bound) and as the host function computes it from a plain f64 loop (shadow_query_bound), both
+// against this handle's shadow.  INVALID without a shadow or for b > kShadowMaxQ.
+int32_t cqs_hip_debug_shadow_bound(cqs_hip_index* x, const float* queries, uint32_t b, float* out_device, float* out_host) CQS_ABI_TRY {
+    if (!x || x->sh || !queries || !out_device || !out_host || b == 0) return CQS_HIP_ERR_INVALID;
+    std::lock_guard<std::mutex> g(x->mu);
+    if (!x->d_shadow || b > cqs::kShadowMaxQ) return CQS_HIP_ERR_INVALID;
+    HIP_TRY(x, hipSetDevice(x->device));
+    HIP_TRY(x, quiesce(x));   // d_bq belongs to the searches
+    float* d_q = nullptr;
+    HIP_TRY(x, hipMalloc(&d_q, (size_t)b * x->dim * sizeof(float)));
+    hipError_t e = hipMemcpyAsync(d_q, queries, (size_t)b * x->dim * sizeof(float), hipMemcpyHostToDevice, x->stream);
+    if (e == hipSuccess) e = cqs::launch_shadow_bound(d_q, b, x->dim, x->shadow_r, x->shadow_norm, x->d_bq, x->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_device, x->d_bq, (size_t)b * sizeof(float), hipMemcpyDeviceToHost, x->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(x->stream);
+    hipFree(d_q);
+    HIP_TRY(x, e);
+    for (uint32_t i = 0; i < b; ++i) {
+        const float* q = queries + (size_t)i * x->dim;
+        double s2 = 0.0;
+        for (uint32_t d = 0; d < x->dim; ++d) s2 += (double)q[d] * (double)q[d];
+        out_host[i] = cqs::shadow_query_bound(s2, x->shadow_r, x->shadow_norm, x->dim);
+    }
+    return CQS_HIP_OK;
+} CQS_ABI_CATCH(x)
 
 // Bench aid (not part of the public header): `n_threads` native threads, each calling the PUBLIC blocking entry point
 // cqs_hip_index_search `per_thread` times with one query at a time (thread t asks queries t, t + n_threads, ... of the

@@ -3,7 +3,8 @@
 //
 // A search over the shadow is exact: the approximate scan picks k' + 1 candidates, their f32 rows are rescored with the
 // f32 gemv kernel's own arithmetic, and the answer is kept only when no row outside the first k' candidates can enter
-// the top k.  Otherwise the host re-runs the query on the f32 scan.
+// the top k.  Otherwise the query is re-run on the f32 scan: by the host (host searches) or by the gated
+// f32 launches that follow on the same stream (cqs_hip_index_search_device).
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -11,6 +12,9 @@
 #if defined(__HIPCC__)
 #include <hip/hip_runtime.h>
 #include "scan_kernels.h"
+#define CQS_HD __host__ __device__
+#else
+#define CQS_HD
 #endif
 
 namespace cqs {
@@ -28,14 +32,14 @@ inline uint32_t shadow_kprime(uint32_t k) {
 
 // Relative f32 error of a `dim`-term dot product computed by FMA chains and a butterfly whose longest path rounds at most
 // dim times: gamma_dim = dim u / (1 - dim u), u = 2^-24 (IEEE fma and add, subnormals kept).
-inline double shadow_gamma(uint32_t dim) {
+CQS_HD inline double shadow_gamma(uint32_t dim) {
     const double du = (double)dim * 0x1p-24;
     return du / (1.0 - du);
 }
 
 // Smallest f32 >= v (v >= 0, finite; +inf if v is past the f32 range).
-inline float round_up_f32(double v) {
-    float f = (float)v;
+CQS_HD inline float round_up_f32(double v) {
+    float f = (float)v;   // (f64 -> f32 conversion rounds to nearest on host and device alike)
     if ((double)f < v) f = nextafterf(f, INFINITY);
     return f;
 }
@@ -43,7 +47,11 @@ inline float round_up_f32(double v) {
 // Per-query bound B_q = ||q||_2 * R (plus an absolute term for underflow in the dim roundings of either chain), rounded
 // up, so that |s - s~| <= B_q for every finite row.  q_norm2 = sum of q_i^2 in f64.  +inf (no certificate for this
 // query) when ||q|| * max(||x||, ||x~||) could reach the f32 overflow range, where one path could overflow and the other not.
-inline float shadow_query_bound(double q_norm2, double r_max, double norm_max, uint32_t dim) {
+// One definition for both sides: the device computes q_norm2 as its own f64 sum (shadow_bound_kernel), in another order
+// than a host loop.  Each of the <= 2048 f64 additions errs by at most 2^-53 relative, so any summation order lands within
+// 2048 * 2^-53 = 2^-42 of the exact sum of squares (all terms >= 0), and the sqrt halves that: the 2^-40 factor on ||q||
+// covers it with room to spare, whoever summed.
+CQS_HD inline float shadow_query_bound(double q_norm2, double r_max, double norm_max, uint32_t dim) {
     const double qn = sqrt(q_norm2) * (1.0 + 0x1p-40);            // f64 sum + sqrt: relative error far below 2^-40
     if (!(qn * norm_max * (1.0 + shadow_gamma(dim)) < 0x1p100)) return INFINITY;
     return round_up_f32(qn * r_max * (1.0 + 0x1p-40) + (double)dim * 0x1p-140);
@@ -57,18 +65,26 @@ inline float shadow_query_bound(double q_norm2, double r_max, double norm_max, u
 hipError_t launch_shadow_build(const float* rows, uint16_t* shadow, uint64_t row0, uint64_t n_rows, uint32_t dim,
                                double gamma, unsigned long long* stats, hipStream_t st);
 
+// bq[i] = shadow_query_bound(||q_i||^2 in f64, r_max, norm_max, dim) for the b queries q [b, dim] (device): one wave per
+// query.  A non-finite query gets +inf (no certificate).
+hipError_t launch_shadow_bound(const float* q, uint32_t b, uint32_t dim, double r_max, double norm_max, float* bq,
+                               hipStream_t st);
+
 // Approximate scan of the shadow: the scores / gmax / gaux layout of launch_scan (gemv passes of <= 8 queries), so the
-// unchanged launch_select picks each query's top k' + 1.  a.rows is ignored; bq[b] = B_q of query b (a.b <= kShadowMaxQ).
+// unchanged launch_select picks each query's top k' + 1.  a.rows is ignored; bq: device [a.b], B_q of each query
+// (a.b <= kShadowMaxQ), read by the PIPELINE drop rule only.
 hipError_t launch_scan_bf16(const ScanArgs& a, const uint16_t* shadow, const float* bq, hipStream_t st);
 
 // Rescore the first min(count, k') approximate keys of each query from the f32 rows (the gemv kernel's arithmetic and
 // epilogue), take the top k by the select's rank sort, write out_keys [b, k] / out_counts [b] as launch_select does, and
 // cert[b] = 1 when that answer is provably the f32 scan's (else the caller re-runs the query on the f32 scan).
-// akeys [b, k' + 1] / acounts [b]: the select's output; ekeys: [b, k'] scratch.
+// akeys [b, k' + 1] / acounts [b]: the select's output; ekeys: [b, k'] scratch; bq: device [b] (launch_shadow_bound).
+// counters: nullable device [2]: += certified, += not certified queries of the block (device-API searches, whose outcome
+// the host never sees).
 hipError_t launch_rescore_certify(const float* rows, uint32_t dim, const float* q, uint32_t b, uint32_t k, uint32_t kprime,
                                   uint32_t mode, float thr, uint32_t row_base, const float* bq, const uint64_t* akeys,
                                   const uint32_t* acounts, uint64_t* ekeys, uint64_t* out_keys, uint32_t* out_counts,
-                                  uint32_t* cert, hipStream_t st);
+                                  uint32_t* cert, unsigned long long* counters, hipStream_t st);
 #endif
 
 }  // namespace cqs

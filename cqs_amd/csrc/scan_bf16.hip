@@ -2,6 +2,8 @@
 //
 //  shadow_build_kernel   one pass over the f32 rows: bf16 copy (v_cvt_pk_bf16_f32: round to nearest even, NaN stays NaN)
 //                        and the index-wide error bound R.
+//  shadow_bound_kernel   one wave per query: B_q = ||q|| R (shadow_query_bound) into a device buffer, so that a search
+//                        enqueued without a host sync can certify.
 //  scan_bf16_kernel      HBM-streaming dot of every bf16 row with 1..8 f32 queries: half the bytes of scan_gemv_kernel.
 //                        Same tasks / work queue / score + gmax (+ gaux) layout, so the unchanged select_finish_kernel
 //                        takes each query's top k' + 1 approximate keys.
@@ -82,6 +84,28 @@ hipError_t launch_shadow_build(const float* rows, uint16_t* shadow, uint64_t row
     return hipGetLastError();
 }
 
+// ---- per-query bound ----------------------------------------------------------------------------------------------
+// ||q||^2 as an f64 sum (the squares of f32 components are exact in f64; the order differs from a host loop, which the
+// 2^-40 slack of shadow_query_bound covers), then the same bound function the host compiles.
+__global__ __launch_bounds__(64) void shadow_bound_kernel(const float* __restrict__ q, uint32_t dim, double r_max,
+                                                          double norm_max, float* __restrict__ bq) {
+    const uint32_t lane = threadIdx.x;
+    const float* qp = q + (size_t)blockIdx.x * dim;
+    double s2 = 0.0;
+    for (uint32_t d = lane; d < dim; d += 64u) s2 += (double)qp[d] * (double)qp[d];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s2 += __shfl_xor(s2, m, 64);
+    if (lane == 0) bq[blockIdx.x] = shadow_query_bound(s2, r_max, norm_max, dim);   // (NaN / inf in q: +inf)
+}
+
+hipError_t launch_shadow_bound(const float* q, uint32_t b, uint32_t dim, double r_max, double norm_max, float* bq,
+                               hipStream_t st) {
+    if (b == 0) return hipSuccess;
+    if (b > kShadowMaxQ) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(shadow_bound_kernel, dim3(b), dim3(64), 0, st, q, dim, r_max, norm_max, bq);
+    return hipGetLastError();
+}
+
 // ---- approximate scan -------------------------------------------------------------------------------------------
 struct Bf16ScanParams {
     const uint16_t* rows;   // [n, dim] bf16
@@ -97,7 +121,7 @@ struct Bf16ScanParams {
     uint32_t n_tasks;
     float* gmax;
     uint64_t* gaux;         // nullable
-    float bq[kMaxGemvQ];    // B_q of each query of the pass
+    const float* bq;        // [nq] B_q of each query of the pass (device)
 };
 
 // NCH = ceil(dim / 512): 1-KiB bf16 chunks per row; lane owns components [c*512 + lane*8, +8) of chunk c (one 16-byte load).
@@ -193,7 +217,7 @@ __global__ __launch_bounds__(256) void scan_bf16_kernel(const Bf16ScanParams p) 
         for (int b = 0; b < BQ; ++b) {
             float s = sc[b];
             if (!live || !(__builtin_fabsf(s) <= 3.4028234664e38f)) s = -INFINITY;
-            else if (p.mode == 1u) {
+            else if (p.mode == 1u && (uint32_t)b < p.nq) {
                 // s <= s~ + B_q, rounding is monotone and the clamp too: clamp(s) >= thr implies clamp(s~ + B_q) >= thr
                 float t = s + p.bq[b];
                 t = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);
@@ -269,7 +293,7 @@ static hipError_t launch_bf16(const ScanArgs& a, const uint16_t* shadow, const f
     p.n_tasks = a.tiers.total();
     p.gmax = a.gmax + (size_t)q0 * p.n_tasks;
     p.gaux = a.gaux ? a.gaux + (size_t)q0 * p.n_tasks : nullptr;
-    for (uint32_t b = 0; b < kMaxGemvQ; ++b) p.bq[b] = b < nq ? bq[q0 + b] : 0.f;
+    p.bq = bq + q0;
     const bool one_shot = p.n_tasks <= a.n_cu * 4u * CQS_BF16_ONE_SHOT;
     const uint32_t wpb = 4u;
     const uint32_t blocks = one_shot ? (p.n_tasks + wpb - 1u) / wpb : a.n_cu * CQS_BF16_BLOCKS_PER_CU;
@@ -386,7 +410,8 @@ struct CertifyParams {
     uint64_t* out_keys;        // [b, k]
     uint32_t* out_counts;      // [b]
     uint32_t* cert;            // [b]
-    float bq[kShadowMaxQ];
+    const float* bq;           // [b]
+    unsigned long long* counters;   // nullable [2]: certified, not certified
 };
 
 __global__ __launch_bounds__(1024) void certify_kernel(const CertifyParams p) {
@@ -422,13 +447,14 @@ __global__ __launch_bounds__(1024) void certify_kernel(const CertifyParams p) {
             }
         }
         p.cert[qi] = ok ? 1u : 0u;
+        if (p.counters) atomicAdd(&p.counters[ok ? 0 : 1], 1ull);
     }
 }
 
 hipError_t launch_rescore_certify(const float* rows, uint32_t dim, const float* q, uint32_t b, uint32_t k, uint32_t kprime,
                                   uint32_t mode, float thr, uint32_t row_base, const float* bq, const uint64_t* akeys,
                                   const uint32_t* acounts, uint64_t* ekeys, uint64_t* out_keys, uint32_t* out_counts,
-                                  uint32_t* cert, hipStream_t st) {
+                                  uint32_t* cert, unsigned long long* counters, hipStream_t st) {
     if (b == 0) return hipSuccess;
     if (b > kShadowMaxQ || k == 0 || kprime < k || kprime >= kShadowKMax || dim % 8u != 0u || dim > kShadowMaxDim)
         return hipErrorInvalidValue;
@@ -447,8 +473,7 @@ hipError_t launch_rescore_certify(const float* rows, uint32_t dim, const float* 
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    CertifyParams cp{ekeys, akeys, acounts, k, kprime, mode, out_keys, out_counts, cert, {}};
-    for (uint32_t i = 0; i < b; ++i) cp.bq[i] = bq[i];
+    CertifyParams cp{ekeys, akeys, acounts, k, kprime, mode, out_keys, out_counts, cert, bq, counters};
     hipLaunchKernelGGL(certify_kernel, dim3(b), dim3(1024), 0, st, cp);
     return hipGetLastError();
 }

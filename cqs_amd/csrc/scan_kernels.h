@@ -59,6 +59,9 @@ struct ScanArgs {
                             // (the scores of a gemv pass do not depend on how many queries share it)
     void* dbg;              // nullable: (16 + 2 * kDbgWaves) x u64: select_finish phase stamps, then the scan's
                             // per-wave start/end stamps (CQS_HIP_DEBUG_STAMPS=1)
+    const uint32_t* gate = nullptr;  // nullable device [b] (gemv passes, b <= 64): every workgroup of the gemv scan and of
+                            // the select reads gate[0, b) at entry and returns at once when all are 1 (the bf16 shadow has
+                            // certified every query of the block; see gate_closed)
 };
 
 // scores[q][row] = dot(rows[row], q) (+ mode / bitset / non-finite handling; dropped
@@ -82,6 +85,20 @@ inline bool uniform_groups(uint32_t b, uint32_t dim) { return use_mfma(b, dim); 
 bool scan_dim_supported(uint32_t dim);
 
 #if defined(__HIPCC__)
+// The f32 fallback gate of the device-API shadow search (index.hip, cqs_hip_index_search_device): true when gate[0, b)
+// are all 1.  Invariants, kept by every kernel that takes a gate:
+//  - the gemv scan and the select decide the same way from the same words (this function, at entry, in every wave;
+//    the words were written by an earlier kernel of the stream and do not change during the launch);
+//  - a skipped scan never touches the work-queue heads: the shadow pass's select has re-zeroed them already, and the
+//    skipped select has nothing to re-zero;
+//  - the launches between the certify kernel and the gated select include no memset (gemv blocks of <= 32 queries stay
+//    under kWorkWords launches); a memset added there must be gated too.
+__device__ __forceinline__ bool gate_closed(const uint32_t* gate, uint32_t b) {
+    uint32_t all = 1u;
+    for (uint32_t i = 0; i < b; ++i) all &= gate[i];   // (uniform: scalar loads, no vector registers at entry)
+    return all != 0u;
+}
+
 // Maximum over the 64 lanes of a wave, in every lane, without the LDS: four DPP steps inside the 16-lane rows (quad_perm
 // xor 1, xor 2, row_half_mirror, row_mirror), then v_permlane16_swap and v_permlane32_swap between the rows.  (`__shfl_xor`
 // compiles to ds_bpermute_b32 on gfx950: six dependent trips through the LDS queue per maximum.)  max16: the first four

@@ -123,6 +123,8 @@ struct ScanParams {
     float* gmax;        // [BQ][n_tasks] maximum valid score of each task's rows (-inf if none)
     uint64_t* gaux;     // nullable, [BQ][n_tasks]: (lane of that maximum << 32) | bits of the largest score of the task's OTHER rows
     unsigned long long* dbg;  // CQS_HIP_DEBUG_STAMPS: [16 + 2*wave] = start / end realtime of each wave
+    const uint32_t* gate;     // nullable, [gate_n]: skip the launch when all are 1 (ScanArgs::gate)
+    uint32_t gate_n;
 };
 
 // NCH = ceil(dim / 256): 1-KiB chunks per row.  BQ queries, RI rows per batch (RI*BQ partial
@@ -135,6 +137,7 @@ struct ScanParams {
 //       use an OCC = 2 build instead so that every task is resident at once.
 template <int NCH, int BQ, int RI, bool NT, bool FULL, int PIPE, int OCC>
 __global__ __launch_bounds__(256, OCC) void scan_gemv_kernel(const ScanParams p) {
+    if (p.gate && gate_closed(p.gate, p.gate_n)) return;   // the bf16 shadow certified the block (before any load or dequeue)
     constexpr int NV = RI * BQ;
     constexpr int LPV = 64 / NV;  // lanes per reduced value
     const int lane = threadIdx.x & 63;
@@ -401,7 +404,9 @@ __global__ __launch_bounds__(1024) void select_finish_kernel(const float* __rest
                                                              uint64_t* __restrict__ out_keys,
                                                              uint32_t* __restrict__ out_counts,
                                                              uint32_t* __restrict__ work,
-                                                             unsigned long long* __restrict__ dbg) {
+                                                             unsigned long long* __restrict__ dbg,
+                                                             const uint32_t* __restrict__ gate, uint32_t gate_n) {
+    if (gate && gate_closed(gate, gate_n)) return;   // (same words, same decision as the gated scan; before any barrier)
     __shared__ uint64_t s_keys[kCandCap];
     __shared__ uint32_t s_groups[kGroupCap];
     __shared__ __attribute__((aligned(16))) uint32_t s_hist[kHistBins];
@@ -704,6 +709,8 @@ static hipError_t launch_gemv(const ScanArgs& a, uint32_t q0, uint32_t nq, uint3
     p.gmax = a.gmax + (size_t)q0 * p.n_tasks;
     p.gaux = a.gaux ? a.gaux + (size_t)q0 * p.n_tasks : nullptr;
     p.dbg = (unsigned long long*)a.dbg;
+    p.gate = a.gate;
+    p.gate_n = a.b;
     // One-shot grid (one task per wave, the hardware dispatcher schedules: beats a persistent grid up to
     // ~1.5M rows) or, for huge corpora, a persistent grid that continues from the work queue (beats the
     // one-shot grid by 3 % at 10M rows).
@@ -779,6 +786,7 @@ static hipError_t launch_gemv_groups(const ScanArgs& a, hipStream_t st) {
 
 hipError_t launch_scan(const ScanArgs& a, hipStream_t st) {
     if (a.b == 0 || a.n == 0) return hipSuccess;
+    if (a.gate && (a.b > 64u || (!a.gemv_only && use_mfma(a.b, a.dim)))) return hipErrorInvalidValue;   // gemv passes only
     if (!a.gemv_only && use_mfma(a.b, a.dim)) {
         uint32_t slot = 0;
         for (uint32_t q0 = 0; q0 < a.b; q0 += 256u) {
@@ -818,11 +826,12 @@ hipError_t launch_scan(const ScanArgs& a, hipStream_t st) {
 hipError_t launch_select(const ScanArgs& a, uint32_t row_base, uint64_t* out_keys, uint32_t* out_counts,
                          hipStream_t st) {
     if (a.b == 0 || a.k == 0) return hipSuccess;
+    if (a.gate && a.b > 64u) return hipErrorInvalidValue;
     hipLaunchKernelGGL(select_finish_kernel, dim3(a.b), dim3(1024), 0, st, a.scores, a.gmax,
                        (!a.gemv_only && use_mfma(a.b, a.dim)) ? nullptr : a.gaux, a.n_pad,
                        a.tiers, tier_slot_log2(a.tiers), a.k, row_base,
                        a.range_bins ? 2u : (a.linear_bins ? 1u : 0u), out_keys, out_counts, a.work,
-                       (unsigned long long*)a.dbg);
+                       (unsigned long long*)a.dbg, a.gate, a.b);
     return hipGetLastError();
 }
 

@@ -584,8 +584,8 @@ int32_t cqs_hip_index_create_sharded(const float* rows, uint64_t n, uint32_t dim
     int32_t rc = CQS_HIP_OK;
     for (uint32_t s = 0; s < n_devices && rc == CQS_HIP_OK; ++s) {
         cqs_hip_index* c = nullptr;
-        rc = cqs_hip_index_create(rows ? rows + (size_t)lo[s] * dim : nullptr, lo[s + 1] - lo[s], dim, metric, devices[s],
-                                  row_base + lo[s], &c);
+        rc = cqs_idx::create_owned(rows ? rows + (size_t)lo[s] * dim : nullptr, lo[s + 1] - lo[s], dim, metric, devices[s],
+                                   row_base + lo[s], &c);   // (no bf16 shadow: sharded handles stay on f32)
         if (rc == CQS_HIP_OK) { p->sh->shard.push_back(c); p->sh->lo.push_back(lo[s]); }
     }
     if (rc == CQS_HIP_OK) rc = cqs_sharded::finish(p, devices);

@@ -453,8 +453,9 @@ class HipIndex(VectorIndex):
         return int(p.value), int(q.value)
 
     def set_bf16_scan(self, enable: bool) -> None:
-        """Build / free the bf16 shadow of the corpus (`cqs_hip_index_set_bf16_scan`).  Answers stay byte-identical; host
-        searches that run as gemv passes read half the bytes.  Raises HipError (INVALID: sharded or borrowed handle,
+        """Build / free the bf16 shadow of the corpus (`cqs_hip_index_set_bf16_scan`; create / load already build it from a
+        1 GiB f32 corpus on, or at any size with CQS_HIP_SCAN_BF16=1).  Answers stay byte-identical; searches that run as
+        gemv passes read half the bytes.  Raises HipError (INVALID: sharded handle, enable on a borrowed handle,
         dim % 8 != 0, dim > 2048, a finite row with a component >= 2^64; NOMEM); the index stays usable either way."""
         rc = self._lib.cqs_hip_index_set_bf16_scan(self._h, 1 if enable else 0)
         if rc != _lib.OK:

@@ -83,7 +83,11 @@ int32_t cqs_hip_index_create(const float* rows, uint64_t n, uint32_t dim, uint32
                              int32_t device, uint64_t row_base, cqs_hip_index** out);
 /* Same, from rows already resident in `device`'s HBM.  borrow != 0: the index
  * uses the caller's buffer in place (caller keeps it alive and unmodified);
- * borrow == 0: the rows are copied device-to-device. */
+ * borrow == 0: the rows are copied device-to-device.
+ * Every single-device create / create_device / load may build the bf16 shadow (see cqs_hip_index_set_bf16_scan).
+ * On a borrowed handle the shadow is a snapshot of the rows taken here: rows written after create break the
+ * "unmodified" contract, and searches may then return the old rows' answers or a mix of old and new ones.  A
+ * caller that must write its rows disables the shadow first (cqs_hip_index_set_bf16_scan(idx, 0)). */
 int32_t cqs_hip_index_create_device(const void* d_rows, uint64_t n, uint32_t dim, uint32_t metric,
                                     int32_t device, uint64_t row_base, int32_t borrow,
                                     cqs_hip_index** out);
@@ -230,20 +234,29 @@ size_t cqs_hip_merge_keys(const uint64_t* lists, const uint32_t* counts, size_t 
 void cqs_hip_index_combine_stats(const cqs_hip_index* idx, uint64_t* passes, uint64_t* queries);
 
 /* ---- bf16 shadow scan --------------------------------------------------------
- * Build (enable != 0) or free (enable == 0) a bf16 copy of the corpus that host searches scan first.
+ * Build (enable != 0) or free (enable == 0) a bf16 copy of the corpus that searches scan first.
  * Answers are unchanged byte for byte: the shadow picks candidates, their f32 rows are rescored with the
  * f32 scan's own arithmetic, and a query whose answer cannot be proven to be the f32 scan's is re-run on
- * it in the same call.  Costs n x dim x 2 B of device memory.  Off by default.
- * CQS_HIP_OK | CQS_HIP_ERR_INVALID (sharded or borrowed handle, dim % 8 != 0, dim > 2048, a finite row with
- * a component of magnitude >= 2^64; reason in last_error) | CQS_HIP_ERR_NOMEM.  The index stays usable on
- * the f32 path after any failure.
+ * it in the same call (device API: in the same stream, by f32 launches that return at once when every
+ * query of the block was proven).  Costs n x dim x 2 B of device memory.
+ * Built automatically by create / create_device / load of a single-device handle when the f32 corpus is at
+ * least 1 GiB, dim % 8 == 0, dim <= 2048, no finite row has a component of magnitude >= 2^64, and the device
+ * keeps max(4 GiB, 10 % of its memory) free afterwards; otherwise the handle is created on the f32 path and
+ * last_error says why.  Environment, read at create / load: CQS_HIP_SCAN_BF16=0 never builds it
+ * automatically, =1 builds it at any size (same dim, outlier and memory rules).
+ * CQS_HIP_OK | CQS_HIP_ERR_INVALID (sharded handle, enable on a borrowed handle, dim % 8 != 0, dim > 2048, a
+ * finite row with a component of magnitude >= 2^64; reason in last_error) | CQS_HIP_ERR_NOMEM.  The index
+ * stays usable on the f32 path after any failure.  enable == 0 works on every single-device handle,
+ * borrowed ones included (the per-handle opt-out); enable != 0 on a borrowed handle stays INVALID, whether
+ * or not create built the shadow: its rows could have changed since create.  Enable is idempotent.
  * Scope: `cqs_hip_index_search` blocks that run as gemv passes (b <= 8, and the combining queue's exact
- * blocks); matrix-core blocks, `cqs_hip_index_search_device`, `cqs_hip_index_neighbors` and sharded handles
- * are unchanged.  `extend` converts the new rows (an outlier row there turns the shadow off); save / load do
- * not persist it (enable again after load). */
+ * blocks) and `cqs_hip_index_search_device` blocks of b <= 8 (and of <= 32 queries where dim % 32 != 0);
+ * matrix-core blocks, `cqs_hip_index_neighbors` and sharded handles are unchanged.  `extend` converts the
+ * new rows (an outlier row there turns the shadow off); save does not persist it (load rebuilds it under
+ * the rules above). */
 int32_t cqs_hip_index_set_bf16_scan(cqs_hip_index* idx, int32_t enable);
 /* bytes of the shadow (0 = off); queries answered by the certified path; queries that fell back to the f32
- * scan.  Any pointer may be NULL. */
+ * scan (host and device-API searches; waits for the device-API searches in flight).  Any pointer may be NULL. */
 void cqs_hip_index_bf16_stats(const cqs_hip_index* idx, uint64_t* bytes, uint64_t* certified, uint64_t* fallbacks);
 
 /* ---- profiling aid ---------------------------------------------------------

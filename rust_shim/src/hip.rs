@@ -152,13 +152,16 @@ fn hip_persist_enabled() -> bool {
 }
 
 fn hip_bf16_scan_enabled() -> bool {
-    // opt-in: a bf16 shadow of the corpus (n x dim x 2 B more device memory), same answers, about half the bytes per search
+    // `1`: a bf16 shadow of the corpus at any size (n x dim x 2 B more device memory), same answers, about half the bytes per
+    // search; the library already builds it unasked from a 1 GiB f32 corpus on
     matches!(std::env::var("CQS_HIP_SCAN_BF16").as_deref(), Ok("1"))
 }
 
 impl HipIndex {
-    /// `CQS_HIP_SCAN_BF16=1`: build the bf16 shadow that host searches scan first (answers unchanged byte for byte).  A
-    /// handle that cannot take it (row-sharded, dim % 8 != 0, an outlier row, no memory) keeps searching on the f32 scan.
+    /// `CQS_HIP_SCAN_BF16=1`: make sure the bf16 shadow that searches scan first is built (answers unchanged byte for byte).
+    /// The library reads the same variable at create / load and has usually built it already (unset: from a 1 GiB f32
+    /// corpus on); enable is idempotent, so this call is then a no-op.  A handle that cannot take it (row-sharded,
+    /// dim % 8 != 0, an outlier row, no memory) keeps searching on the f32 scan.
     fn enable_bf16_scan_from_env(&self) {
         if !hip_bf16_scan_enabled() {
             return;
