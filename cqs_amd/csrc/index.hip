@@ -109,19 +109,8 @@ uint32_t max_query_block(const cqs_hip_index* x) {
     return (uint32_t)q;
 }
 
-// Enqueue scan + select for queries already on the device.  Caller holds mu.
-int32_t enqueue_search(cqs_hip_index* x, const float* d_q, uint32_t b, uint32_t k, const uint32_t* d_keep,
-                       uint32_t mode, float thr, uint64_t* d_out_keys, uint32_t* d_out_counts, hipStream_t st, bool gemv_only,
-                       const uint32_t* gate) {
-    // the previous search may still be running on another stream and owns the same scratch
-    if (x->done_valid && x->done_stream != st) HIP_TRY(x, hipStreamWaitEvent(st, x->done, 0));
-    if (!gemv_only && cqs::use_mfma(b, x->dim)) {
-        // the matrix-core path reads whole query tiles: stage the block in d_q with a zero tail
-        const size_t qbytes = (size_t)b * x->dim * sizeof(float);
-        if (d_q != x->d_q) HIP_TRY(x, hipMemcpyAsync(x->d_q, d_q, qbytes, hipMemcpyDeviceToDevice, st));
-        HIP_TRY(x, hipMemsetAsync((char*)x->d_q + qbytes, 0, (size_t)256 * x->dim * sizeof(float), st));
-        d_q = x->d_q;
-    }
+cqs::ScanArgs scan_args(const cqs_hip_index* x, const float* d_q, uint32_t b, uint32_t k, const uint32_t* d_keep,
+                        uint32_t mode, float thr, size_t elem_bytes, bool gemv_only, void* dbg, const uint32_t* gate) {
     cqs::ScanArgs a;
     a.rows = x->d_rows;
     a.n = (uint32_t)x->n;
@@ -133,21 +122,23 @@ int32_t enqueue_search(cqs_hip_index* x, const float* d_q, uint32_t b, uint32_t 
     a.keep = d_keep;
     a.mode = mode;
     a.threshold = thr;
-    a.nontemporal = x->n * x->dim * sizeof(float) > kNtBytes;
+    a.nontemporal = x->n * x->dim * elem_bytes > kNtBytes;
     a.linear_bins = (x->metric == CQS_HIP_METRIC_COSINE) || (mode == CQS_HIP_MODE_PIPELINE);
     a.k = k;
     a.gmax = x->d_gmax;
-    static const bool use_gaux = [] { const char* e = getenv("CQS_HIP_SELECT_AUX"); return !(e && e[0] == '0'); }();   // A/B hook
-    // Only where the gather it replaces is long: at k = 20 the index costs what it saves (same-box A/B, 1M x 768, scan + select per
-    // step: k = 20 0.4698 with / 0.4667 ms without; k = 500 0.4783 / 0.4825 - tools/ab_select_aux.sh), so small k keeps round 4's path.
-    a.gaux = (use_gaux && b <= kGauxQueries && k >= kGauxMinK) ? x->d_gaux : nullptr;
+    a.gaux = (b <= kGauxQueries && k >= kGauxMinK) ? x->d_gaux : nullptr;
     a.work = x->d_work;
     a.n_cu = x->n_cu;
-    a.dbg = x->d_dbg;
+    a.dbg = dbg;
     a.gemv_only = gemv_only;
     a.tiers = cqs::plan_tiers(a.n_pad, x->n_cu, !gemv_only && cqs::uniform_groups(b, x->dim));
     a.gate = gate;
-    const bool timed = !gate && x->timing && x->ev_used + 2 <= kMaxTimingEvents;   // (gated: the shadow scan was timed)
+    return a;
+}
+
+int32_t scan_select(cqs_hip_index* x, const cqs::ScanArgs& a, hipStream_t st, const uint16_t* bf16, const float* bq,
+                    uint64_t* out_keys, uint32_t* out_counts) {
+    const bool timed = !a.gate && x->timing && x->ev_used + 2 <= kMaxTimingEvents;
     if (timed) {
         while (x->ev.size() < x->ev_used + 2) {
             hipEvent_t e = nullptr;
@@ -156,16 +147,36 @@ int32_t enqueue_search(cqs_hip_index* x, const float* d_q, uint32_t b, uint32_t 
         }
         HIP_TRY(x, hipEventRecord(x->ev[x->ev_used], st));
     }
-    HIP_TRY(x, cqs::launch_scan(a, st));
+    if (bf16) HIP_TRY(x, cqs::launch_scan_bf16(a, bf16, bq, st));
+    else HIP_TRY(x, cqs::launch_scan(a, st));
     if (timed) {
         HIP_TRY(x, hipEventRecord(x->ev[x->ev_used + 1], st));
         x->ev_used += 2;
     }
-    HIP_TRY(x, cqs::launch_select(a, (uint32_t)x->row_base, d_out_keys, d_out_counts, st));
-    HIP_TRY(x, hipEventRecord(x->done, st));
-    x->done_stream = st;
-    x->done_valid = true;
+    HIP_TRY(x, cqs::launch_select(a, (uint32_t)x->row_base, out_keys, out_counts, st));
     return CQS_HIP_OK;
+}
+
+// Enqueue scan + select for queries already on the device.  Caller holds mu.
+int32_t enqueue_search(cqs_hip_index* x, const float* d_q, uint32_t b, uint32_t k, const uint32_t* d_keep,
+                       uint32_t mode, float thr, uint64_t* d_out_keys, uint32_t* d_out_counts, hipStream_t st, bool gemv_only,
+                       const uint32_t* gate) {
+    HIP_TRY(x, order_after_last(x, st));   // the previous search may still be running on another stream and owns the same scratch
+    if (!gemv_only && cqs::use_mfma(b, x->dim)) {
+        // the matrix-core path reads whole query tiles: stage the block in d_q with a zero tail
+        const size_t qbytes = (size_t)b * x->dim * sizeof(float);
+        if (d_q != x->d_q) HIP_TRY(x, hipMemcpyAsync(x->d_q, d_q, qbytes, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(x, hipMemsetAsync((char*)x->d_q + qbytes, 0, (size_t)256 * x->dim * sizeof(float), st));
+        d_q = x->d_q;
+    }
+    cqs::ScanArgs a = scan_args(x, d_q, b, k, d_keep, mode, thr, sizeof(float), gemv_only, x->d_dbg, gate);
+    static const bool use_gaux = [] { const char* e = getenv("CQS_HIP_SELECT_AUX"); return !(e && e[0] == '0'); }();   // A/B hook
+    // The index only where the gather it replaces is long (scan_args): at k = 20 it costs what it saves (same-box A/B, 1M x 768,
+    // scan + select per step: k = 20 0.4698 with / 0.4667 ms without; k = 500 0.4783 / 0.4825 - tools/ab_select_aux.sh).
+    if (!use_gaux) a.gaux = nullptr;
+    const int32_t rc = scan_select(x, a, st, nullptr, nullptr, d_out_keys, d_out_counts);
+    if (rc == CQS_HIP_OK) HIP_TRY(x, record_done(x, st));
+    return rc;
 }
 
 // Wait (host) for the last enqueued search, whatever stream it ran on.  Caller holds mu.
@@ -222,197 +233,6 @@ int32_t create_common(uint64_t n, uint32_t dim, uint32_t metric, int32_t device,
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0)
         x->n_cu = (uint32_t)prop.multiProcessorCount;
     *made = x;
-    return CQS_HIP_OK;
-}
-
-// ---- bf16 shadow (create / load policy, cqs_hip_index_set_bf16_scan) -----------------------------------------------
-// What the device-API searches' certify launches counted (d_shadow_stats[3, 5): certified, fallbacks).  Caller holds mu,
-// every search has completed (quiesce).
-static bool shadow_device_counts(cqs_hip_index* x, unsigned long long (&c)[2]) {
-    c[0] = c[1] = 0;
-    if (!x->d_shadow_stats) return true;
-    hipError_t e = hipMemcpyAsync(c, x->d_shadow_stats + 3, sizeof c, hipMemcpyDeviceToHost, x->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(x->stream);
-    if (e != hipSuccess) { (void)hipGetLastError(); c[0] = c[1] = 0; return false; }
-    return true;
-}
-
-void shadow_free(cqs_hip_index* x) {
-    unsigned long long c[2];
-    if (x->d_shadow_stats && quiesce(x) == hipSuccess && shadow_device_counts(x, c)) {   // the counts outlive the shadow
-        x->stat_certified.fetch_add(c[0], std::memory_order_relaxed);
-        x->stat_fallbacks.fetch_add(c[1], std::memory_order_relaxed);
-    }
-    hipFree(x->d_shadow); hipFree(x->d_shadow_stats); hipFree(x->d_akeys); hipFree(x->d_acounts); hipFree(x->d_ekeys);
-    hipFree(x->d_cert); hipFree(x->d_bq); hipHostFree(x->h_cert);
-    x->d_shadow = nullptr; x->d_shadow_stats = nullptr; x->d_akeys = nullptr; x->d_acounts = nullptr; x->d_ekeys = nullptr;
-    x->d_cert = nullptr; x->d_bq = nullptr; x->h_cert = nullptr; x->h_cert_dev = nullptr;
-    x->shadow_cap = 0; x->shadow_r = 0.0; x->shadow_norm = 0.0;
-}
-
-// Convert rows [row0, x->n) into the shadow and fold them into R.  Caller holds mu, the stream is idle.  *outlier: a finite
-// row has a component of magnitude >= 2^64 (the shadow cannot certify against it).
-static int32_t shadow_convert(cqs_hip_index* x, uint64_t row0, bool* outlier) {
-    HIP_TRY(x, hipMemsetAsync(x->d_shadow_stats + 2, 0, sizeof(unsigned long long), x->stream));
-    HIP_TRY(x, cqs::launch_shadow_build(x->d_rows, x->d_shadow, row0, x->n - row0, x->dim, cqs::shadow_gamma(x->dim),
-                                        x->d_shadow_stats, x->stream));
-    unsigned long long st[3];
-    HIP_TRY(x, hipMemcpyAsync(st, x->d_shadow_stats, sizeof st, hipMemcpyDeviceToHost, x->stream));
-    HIP_TRY(x, hipStreamSynchronize(x->stream));
-    double r, m;
-    memcpy(&r, &st[0], sizeof r);
-    memcpy(&m, &st[1], sizeof m);
-    x->shadow_r = r * (1.0 + 0x1p-30);      // (f64 sums of <= 2048 squares and three square roots: relative error < 2^-40)
-    x->shadow_norm = m * (1.0 + 0x1p-30);
-    *outlier = st[2] != 0;
-    return CQS_HIP_OK;
-}
-
-// extend() on a handle with the shadow on: grow it with cap_rows, convert rows [n_old, n).  A failure here (no memory,
-// an outlier row) turns the shadow off and leaves the f32 index as extended: the call still succeeds.
-int32_t shadow_extend(cqs_hip_index* x, uint64_t n_old) {
-    if (x->cap_rows > x->shadow_cap) {
-        uint16_t* nd = nullptr;
-        if (hipMalloc(&nd, (size_t)x->cap_rows * x->dim * sizeof(uint16_t)) != hipSuccess) {
-            (void)hipGetLastError();
-            shadow_free(x);
-            x->last_error = "extend: no device memory to grow the bf16 shadow; shadow turned off";
-            return CQS_HIP_OK;
-        }
-        hipError_t e = hipMemcpyAsync(nd, x->d_shadow, (size_t)n_old * x->dim * sizeof(uint16_t), hipMemcpyDeviceToDevice, x->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(x->stream);
-        if (e != hipSuccess) { hipFree(nd); return fail(x, CQS_HIP_ERR_DEVICE, "extend: shadow copy", e); }
-        hipFree(x->d_shadow);
-        x->d_shadow = nd;
-        x->shadow_cap = x->cap_rows;
-    }
-    bool outlier = false;
-    const int32_t rc = shadow_convert(x, n_old, &outlier);
-    if (rc != CQS_HIP_OK) return rc;
-    if (outlier) {
-        shadow_free(x);
-        x->last_error = "extend: a new row has a component of magnitude >= 2^64; bf16 shadow turned off";
-    }
-    return CQS_HIP_OK;
-}
-
-// Allocate and build the shadow over rows [0, n) (no borrow check: the create policy snapshots borrowed rows too).  On
-// failure the shadow is freed and `fail` has put `what: reason` in last_error.  Caller holds mu (or owns the new handle).
-static int32_t shadow_enable(cqs_hip_index* x, const char* what) {
-    std::string pre(what);
-    if (x->dim % 8u != 0u || x->dim > cqs::kShadowMaxDim)
-        return fail(x, CQS_HIP_ERR_INVALID, (pre + ": dim must be a multiple of 8 and <= 2048").c_str());
-    if (x->d_shadow) return CQS_HIP_OK;
-    const uint64_t cap = x->cap_rows ? x->cap_rows : 1;
-    auto oom = [&](hipError_t e) { (void)hipGetLastError(); shadow_free(x); return fail(x, CQS_HIP_ERR_NOMEM, (pre + ": allocation").c_str(), e); };
-    hipError_t e;
-    if ((e = hipMalloc(&x->d_shadow, (size_t)cap * x->dim * sizeof(uint16_t))) != hipSuccess) return oom(e);
-    x->shadow_cap = cap;
-    unsigned long long* stats = nullptr;   // zeroed before it is the handle's: shadow_free reads its counts
-    if ((e = hipMalloc(&stats, 5 * sizeof(unsigned long long))) != hipSuccess) return oom(e);
-    if ((e = hipMemsetAsync(stats, 0, 5 * sizeof(unsigned long long), x->stream)) != hipSuccess) { hipFree(stats); return oom(e); }
-    x->d_shadow_stats = stats;
-    if ((e = hipMalloc(&x->d_akeys, (size_t)cqs::kShadowMaxQ * kMaxK * sizeof(uint64_t))) != hipSuccess) return oom(e);
-    if ((e = hipMalloc(&x->d_acounts, (size_t)cqs::kShadowMaxQ * sizeof(uint32_t))) != hipSuccess) return oom(e);
-    if ((e = hipMalloc(&x->d_ekeys, (size_t)cqs::kShadowMaxQ * (kMaxK - 1) * sizeof(uint64_t))) != hipSuccess) return oom(e);
-    if ((e = hipMalloc(&x->d_cert, (size_t)cqs::kShadowMaxQ * sizeof(uint32_t))) != hipSuccess) return oom(e);
-    if ((e = hipMalloc(&x->d_bq, (size_t)cqs::kShadowMaxQ * sizeof(float))) != hipSuccess) return oom(e);
-    if ((e = hipHostMalloc(&x->h_cert, (size_t)cqs::kShadowMaxQ * sizeof(uint32_t), hipHostMallocDefault)) != hipSuccess) return oom(e);
-    if (hipHostGetDevicePointer((void**)&x->h_cert_dev, x->h_cert, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        x->h_cert_dev = nullptr;
-    }
-    bool outlier = false;
-    const int32_t rc = shadow_convert(x, 0, &outlier);
-    if (rc != CQS_HIP_OK) { shadow_free(x); return rc; }
-    if (outlier) {
-        shadow_free(x);
-        return fail(x, CQS_HIP_ERR_INVALID, (pre + ": a finite row has a component of magnitude >= 2^64").c_str());
-    }
-    return CQS_HIP_OK;
-}
-
-// The shadow policy of create / create_device / load, for a single-device handle whose rows are in place.
-// CQS_HIP_SCAN_BF16 (read here, at create): unset = where it pays (f32 corpus >= kShadowAutoBytes), 0 = never, 1 = at any
-// size; dim, outlier and free-memory rules either way.  The create never fails for the shadow's sake: the handle then
-// searches the f32 rows and last_error says why.  Returns an error only for a device fault (the handle is poisoned).
-static int32_t shadow_auto(cqs_hip_index* x) {
-    const char* env = getenv("CQS_HIP_SCAN_BF16");
-    if (env && env[0] == '0') return CQS_HIP_OK;
-    const bool any_size = env && env[0] == '1';
-    const uint64_t f32_bytes = x->n * x->dim * sizeof(float);
-    if (!any_size && f32_bytes < kShadowAutoBytes) {
-        x->last_error = "bf16 shadow not built: f32 corpus below 1 GiB (CQS_HIP_SCAN_BF16=1 builds it at any size)";
-        return CQS_HIP_OK;
-    }
-    if (x->dim % 8u != 0u || x->dim > cqs::kShadowMaxDim) {
-        x->last_error = "bf16 shadow not built: dim must be a multiple of 8 and <= 2048";
-        return CQS_HIP_OK;
-    }
-    size_t free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
-        (void)hipGetLastError();
-        x->last_error = "bf16 shadow not built: hipMemGetInfo failed";
-        return CQS_HIP_OK;
-    }
-    const uint64_t cap = x->cap_rows ? x->cap_rows : 1;
-    const uint64_t need = cap * x->dim * sizeof(uint16_t) + (2ull * kMaxK + 2ull) * cqs::kShadowMaxQ * sizeof(uint64_t);
-    const uint64_t frac = (uint64_t)(kShadowFreeFrac * (double)total_b);
-    const uint64_t reserve = frac > kShadowFreeMinBytes ? frac : kShadowFreeMinBytes;
-    if (free_b < need || free_b - need < reserve) {
-        x->last_error = "bf16 shadow not built: the device would keep less than max(4 GiB, 10 %) of its memory free";
-        return CQS_HIP_OK;
-    }
-    const int32_t rc = shadow_enable(x, "bf16 shadow not built");
-    return rc == CQS_HIP_ERR_DEVICE ? rc : CQS_HIP_OK;
-}
-
-// The shadow half of a gemv block, enqueued on `st`: B_q of each query -> shadow scan -> select k' + 1 -> rescore +
-// certify into out_keys / out_counts / cert (counters: nullable, certify's device counts).  d_q [nb, dim] on the device.
-// Caller holds mu and has ordered `st` after the last search.
-static int32_t enqueue_shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k, const uint32_t* d_keep,
-                                   uint32_t mode, float threshold, uint64_t* out_keys, uint32_t* out_counts, uint32_t* cert,
-                                   unsigned long long* counters, hipStream_t st) {
-    const uint32_t kp = cqs::shadow_kprime(k);
-    HIP_TRY(x, cqs::launch_shadow_bound(d_q, nb, x->dim, x->shadow_r, x->shadow_norm, x->d_bq, st));
-    cqs::ScanArgs a;
-    a.rows = x->d_rows;
-    a.n = (uint32_t)x->n;
-    a.n_pad = (uint32_t)pad_rows(x->n);
-    a.dim = x->dim;
-    a.q = d_q;
-    a.b = nb;
-    a.scores = x->d_scores;
-    a.keep = d_keep;
-    a.mode = mode;
-    a.threshold = threshold;
-    a.nontemporal = x->n * x->dim * sizeof(uint16_t) > kNtBytes;
-    a.linear_bins = (x->metric == CQS_HIP_METRIC_COSINE) || (mode == CQS_HIP_MODE_PIPELINE);
-    a.k = kp + 1u;
-    a.gmax = x->d_gmax;
-    a.gaux = a.k >= kGauxMinK ? x->d_gaux : nullptr;
-    a.work = x->d_work;
-    a.n_cu = x->n_cu;
-    a.dbg = nullptr;
-    a.gemv_only = true;
-    a.tiers = cqs::plan_tiers(a.n_pad, x->n_cu, false);
-    const bool timed = x->timing && x->ev_used + 2 <= kMaxTimingEvents;
-    if (timed) {
-        while (x->ev.size() < x->ev_used + 2) {
-            hipEvent_t e = nullptr;
-            HIP_TRY(x, hipEventCreate(&e));
-            x->ev.push_back(e);
-        }
-        HIP_TRY(x, hipEventRecord(x->ev[x->ev_used], st));
-    }
-    HIP_TRY(x, cqs::launch_scan_bf16(a, x->d_shadow, x->d_bq, st));
-    if (timed) {
-        HIP_TRY(x, hipEventRecord(x->ev[x->ev_used + 1], st));
-        x->ev_used += 2;
-    }
-    HIP_TRY(x, cqs::launch_select(a, (uint32_t)x->row_base, x->d_akeys, x->d_acounts, st));
-    HIP_TRY(x, cqs::launch_rescore_certify(x->d_rows, x->dim, d_q, nb, k, kp, mode, threshold, (uint32_t)x->row_base, x->d_bq,
-                                           x->d_akeys, x->d_acounts, x->d_ekeys, out_keys, out_counts, cert, counters, st));
     return CQS_HIP_OK;
 }
 
@@ -534,8 +354,7 @@ int32_t cqs_hip_index_extend(cqs_hip_index* x, const float* rows, uint64_t n_new
     HIP_TRY(x, hipStreamSynchronize(x->stream));
     const uint64_t n_old = x->n;
     x->n += n_new;
-    if (x->d_shadow) return shadow_extend(x, n_old);
-    return CQS_HIP_OK;
+    return shadow_extend(x, n_old);
 } CQS_ABI_CATCH(x)
 
 }  // extern "C"
@@ -823,19 +642,15 @@ int32_t cqs_hip_index_search_device(cqs_hip_index* x, const float* d_queries, ui
     }
     int32_t rc = ensure_scratch(x, b, k);
     if (rc != CQS_HIP_OK) return rc;
-    if (x->d_shadow && b <= cqs::kShadowMaxQ && !cqs::use_mfma(b, x->dim) && cqs::shadow_kprime(k) >= k) {
-        // Through the bf16 shadow, with no host sync: certify writes the answers into the caller's buffers and its verdicts
-        // into d_cert; the f32 scan + select that follow are gated by d_cert and return at entry when every query of the
-        // block is certified.  Otherwise they recompute the whole block, which is harmless: gemv-pass scores do not depend
-        // on which queries share a pass, and a certified answer is the f32 answer.
-        if (x->done_valid && x->done_stream != st) HIP_TRY(x, hipStreamWaitEvent(st, x->done, 0));
-        rc = enqueue_shadow_pass(x, d_queries, b, k, d_keep_bitset, mode, threshold, d_out_keys, d_out_counts, x->d_cert,
-                                 x->d_shadow_stats + 3, st);
-        if (rc != CQS_HIP_OK) return rc;
-        // (records `done` after the gated select: the cross-stream hand-off covers d_bq, d_akeys, d_ekeys and d_cert too)
-        return enqueue_search(x, d_queries, b, k, d_keep_bitset, mode, threshold, d_out_keys, d_out_counts, st, false, x->d_cert);
-    }
-    return enqueue_search(x, d_queries, b, k, d_keep_bitset, mode, threshold, d_out_keys, d_out_counts, st);
+    // Through the bf16 shadow, no host sync: certify writes the answers into the caller's buffers and its verdicts into the
+    // gate words.  The f32 scan + select that follow return at entry when every query is certified, else recompute the whole
+    // block, which is harmless (gemv-pass scores do not depend on which queries share a pass; a certified answer is the f32
+    // one).  `done` is recorded after the gated select, so the cross-stream hand-off covers the shadow's scratch too.
+    const uint32_t* gate = nullptr;
+    if (shadow_takes(x, b, k, /*gemv_only=*/false) &&
+        (rc = shadow_pass(x, d_queries, b, k, d_keep_bitset, mode, threshold, d_out_keys, d_out_counts, st, &gate)) != CQS_HIP_OK)
+        return rc;
+    return enqueue_search(x, d_queries, b, k, d_keep_bitset, mode, threshold, d_out_keys, d_out_counts, st, false, gate);
 } CQS_ABI_CATCH(x)
 
 }  // extern "C"
@@ -868,76 +683,46 @@ static void print_debug_stamps(cqs_hip_index* x) {
     (void)hipMemset(x->d_dbg + 16, 0, w.size() * sizeof(unsigned long long));
 }
 
-// One host query of a block and where its answer goes.
-struct HostQuery {
-    const float* q;          // [dim]
-    uint64_t* out_rows;      // [k]
-    float* out_scores;       // [k]
-    uint32_t* out_count;
-};
-
-// Scan + select for the nq queries staged in h_q[0, nq) (query i answers qs[map[i]]), wait, unpack.  Caller holds mu.
-static int32_t f32_block(cqs_hip_index* x, const HostQuery* qs, const uint32_t* map, const uint8_t* bad, uint32_t nq,
-                         uint32_t k_eff, const uint32_t* d_keep, uint32_t mode, float threshold, bool gemv_only) {
+// The nq queries staged in h_q (row i answers qs[i]; null: non-finite, a zero row, no answer), one wait: the f32 scan, or
+// with redo the bf16 shadow, whose uncovered queries go to *redo, restaged in order in h_q[0, redo->size()).  Caller holds
+// mu; x->stream is ordered after the last search.
+static int32_t host_block(cqs_hip_index* x, const cqs_combine_req* const* qs, uint32_t nq, uint32_t k, const uint32_t* d_keep,
+                          uint32_t mode, float thr, bool gemv_only, std::vector<const cqs_combine_req*>* redo) {
     HIP_TRY(x, hipMemcpyAsync(x->d_q, x->h_q, (size_t)nq * x->dim * sizeof(float), hipMemcpyHostToDevice, x->stream));
     // Small blocks: the select kernel writes keys and counts straight into the pinned host buffers (device-visible
     // addresses): no copy calls behind the kernels, one wait.  Large blocks keep the device buffers + two copies
     // (hundreds of KB of scattered 8-byte stores over PCIe would cost more than the copies).
-    const bool direct = x->h_out_keys_dev && x->h_out_counts_dev && (size_t)nq * k_eff <= kDirectOutKeys;
-    int32_t rc = enqueue_search(x, x->d_q, nq, k_eff, d_keep, mode, threshold, direct ? x->h_out_keys_dev : x->d_out_keys,
-                                direct ? x->h_out_counts_dev : x->d_out_counts, x->stream, gemv_only);
+    const bool direct = x->h_out_keys_dev && x->h_out_counts_dev && (size_t)nq * k <= kDirectOutKeys;
+    uint64_t* const keys = direct ? x->h_out_keys_dev : x->d_out_keys;
+    uint32_t* const counts = direct ? x->h_out_counts_dev : x->d_out_counts;
+    int32_t rc = redo ? shadow_pass(x, x->d_q, nq, k, d_keep, mode, thr, keys, counts, x->stream, nullptr)
+                      : enqueue_search(x, x->d_q, nq, k, d_keep, mode, thr, keys, counts, x->stream, gemv_only);
     if (rc != CQS_HIP_OK) return rc;
+    if (redo) HIP_TRY(x, record_done(x, x->stream));
     if (!direct) {
-        HIP_TRY(x, hipMemcpyAsync(x->h_out_keys, x->d_out_keys, (size_t)nq * k_eff * sizeof(uint64_t), hipMemcpyDeviceToHost, x->stream));
+        HIP_TRY(x, hipMemcpyAsync(x->h_out_keys, x->d_out_keys, (size_t)nq * k * sizeof(uint64_t), hipMemcpyDeviceToHost, x->stream));
         HIP_TRY(x, hipMemcpyAsync(x->h_out_counts, x->d_out_counts, (size_t)nq * sizeof(uint32_t), hipMemcpyDeviceToHost, x->stream));
     }
+    const uint32_t* cert = nullptr;   // the shadow's verdicts
+    if (redo) HIP_TRY(x, shadow_verdicts(x, nq, &cert));
     HIP_TRY(x, hipStreamSynchronize(x->stream));
-    if (x->d_dbg) print_debug_stamps(x);
-    for (uint32_t i = 0; i < nq; ++i) {
-        const uint32_t qi = map[i];
-        if (bad[qi]) continue;
-        uint32_t c = x->h_out_counts[i];
-        if (c > k_eff) c = k_eff;
-        cqs_hip_unpack_keys(x->h_out_keys + (size_t)i * k_eff, c, qs[qi].out_rows, qs[qi].out_scores);
-        *qs[qi].out_count = c;
-    }
-    return CQS_HIP_OK;
-}
-
-// The same block through the bf16 shadow (scan_bf16.h): shadow scan -> select k' + 1 -> rescore + certify -> one wait.
-// Certified answers are unpacked; the block-relative indices of the others go to `redo` (the caller runs them on the f32
-// scan).  Caller holds mu; h_q[0, nb) holds the staged queries of qs[q0, q0 + nb).
-static int32_t shadow_block(cqs_hip_index* x, const HostQuery* qs, uint32_t q0, const uint8_t* bad, uint32_t nb, uint32_t k_eff,
-                            const uint32_t* d_keep, uint32_t mode, float threshold, std::vector<uint32_t>& redo) {
-    hipStream_t st = x->stream;
-    HIP_TRY(x, hipMemcpyAsync(x->d_q, x->h_q, (size_t)nb * x->dim * sizeof(float), hipMemcpyHostToDevice, st));
-    const bool direct = x->h_out_keys_dev && x->h_out_counts_dev && (size_t)nb * k_eff <= kDirectOutKeys;
-    int32_t rc = enqueue_shadow_pass(x, x->d_q, nb, k_eff, d_keep, mode, threshold, direct ? x->h_out_keys_dev : x->d_out_keys,
-                                     direct ? x->h_out_counts_dev : x->d_out_counts, x->h_cert_dev ? x->h_cert_dev : x->d_cert,
-                                     nullptr, st);
-    if (rc != CQS_HIP_OK) return rc;
-    HIP_TRY(x, hipEventRecord(x->done, st));
-    x->done_stream = st;
-    x->done_valid = true;
-    if (!direct) {
-        HIP_TRY(x, hipMemcpyAsync(x->h_out_keys, x->d_out_keys, (size_t)nb * k_eff * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-        HIP_TRY(x, hipMemcpyAsync(x->h_out_counts, x->d_out_counts, (size_t)nb * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    }
-    if (!x->h_cert_dev) HIP_TRY(x, hipMemcpyAsync(x->h_cert, x->d_cert, (size_t)nb * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(x, hipStreamSynchronize(st));
+    if (!redo && x->d_dbg) print_debug_stamps(x);
+    if (redo) redo->clear();
     uint64_t certified = 0;
-    for (uint32_t i = 0; i < nb; ++i) {
-        const uint32_t qi = q0 + i;
-        if (bad[qi]) continue;
-        if (!x->h_cert[i]) { redo.push_back(i); continue; }
-        uint32_t c = x->h_out_counts[i];
-        if (c > k_eff) c = k_eff;
-        cqs_hip_unpack_keys(x->h_out_keys + (size_t)i * k_eff, c, qs[qi].out_rows, qs[qi].out_scores);
-        *qs[qi].out_count = c;
-        ++certified;
+    for (uint32_t i = 0; i < nq; ++i) {
+        if (!qs[i]) continue;
+        if (cert && !cert[i]) {   // restaged for the f32 scan (ascending, so rows only move down)
+            if (redo->size() != i) memcpy(x->h_q + redo->size() * x->dim, x->h_q + (size_t)i * x->dim, (size_t)x->dim * sizeof(float));
+            redo->push_back(qs[i]);
+            continue;
+        }
+        const uint32_t c = x->h_out_counts[i] < k ? x->h_out_counts[i] : k;
+        cqs_hip_unpack_keys(x->h_out_keys + (size_t)i * k, c, qs[i]->out_rows, qs[i]->out_scores);
+        *qs[i]->out_count = c;
+        certified += cert ? 1 : 0;
     }
     x->stat_certified.fetch_add(certified, std::memory_order_relaxed);
-    x->stat_fallbacks.fetch_add(redo.size(), std::memory_order_relaxed);
+    if (redo) x->stat_fallbacks.fetch_add(redo->size(), std::memory_order_relaxed);
     return CQS_HIP_OK;
 }
 
@@ -945,16 +730,16 @@ static int32_t shadow_block(cqs_hip_index* x, const HostQuery* qs, uint32_t q0, 
 // budget allows.  Caller holds mu, has checked the arguments and zeroed the counts.  `gemv_only`: every block goes
 // through the HBM-streaming passes of <= 8 queries, whose scores do not depend on how many queries share a pass (same
 // per-lane FMA chain, same butterfly) - what the combining queue needs to hand each caller the bits it would have got alone.
-// With the bf16 shadow on, blocks that run as gemv passes go through it first (shadow_block); the matrix-core blocks keep
+// With the bf16 shadow on, blocks that run as gemv passes go through it first (host_block); the matrix-core blocks keep
 // their path (their scores are not the gemv kernel's).
-static int32_t search_host_locked(cqs_hip_index* x, const HostQuery* qs, uint32_t b, uint32_t k, const uint32_t* keep_bitset,
+static int32_t search_host_locked(cqs_hip_index* x, const cqs_combine_req* qs, uint32_t b, uint32_t k, const uint32_t* keep_bitset,
                                   uint32_t mode, float threshold, bool gemv_only) {
     if (x->inject_fail.exchange(0, std::memory_order_acq_rel) != 0)
         return fail(x, CQS_HIP_ERR_DEVICE, "search: injected device failure (test hook)");
     if (x->n == 0 || k == 0) return CQS_HIP_OK;               // src/cagra.rs:445-447
     HIP_TRY(x, hipSetDevice(x->device));
     // a device-API search on a caller stream may still use the shared scratch this call is about to overwrite
-    if (x->done_valid && x->done_stream != x->stream) HIP_TRY(x, hipStreamWaitEvent(x->stream, x->done, 0));
+    HIP_TRY(x, order_after_last(x, x->stream));
     // bitset: count kept rows on the host (src/cagra.rs:747-775)
     const uint32_t* d_keep = nullptr;
     uint32_t k_eff = k;
@@ -976,41 +761,29 @@ static int32_t search_host_locked(cqs_hip_index* x, const HostQuery* qs, uint32_
     }
 
     const uint32_t blk = max_query_block(x);
-    std::vector<uint8_t> bad(b, 0);
-    std::vector<uint32_t> map, redo;
+    std::vector<const cqs_combine_req*> staged, redo;
     for (uint32_t done = 0; done < b;) {
         const uint32_t nb = (b - done) < blk ? (b - done) : blk;
         int32_t rc = ensure_scratch(x, nb, k_eff);
         if (rc != CQS_HIP_OK) return rc;
-        // stage queries; a non-finite query yields an empty result (src/cagra.rs:464-470)
+        // stage queries; a non-finite query is a zero row with an empty result (src/cagra.rs:464-470)
+        staged.clear();
         for (uint32_t i = 0; i < nb; ++i) {
             const float* src = qs[done + i].q;
             float* dst = x->h_q + (size_t)i * x->dim;
             bool ok = true;
             for (uint32_t d = 0; d < x->dim; ++d) ok &= std::isfinite(src[d]);
-            bad[done + i] = !ok;
             if (ok) memcpy(dst, src, (size_t)x->dim * sizeof(float));
             else memset(dst, 0, (size_t)x->dim * sizeof(float));
+            staged.push_back(ok ? &qs[done + i] : nullptr);
         }
-        map.clear();
-        const bool shadow = x->d_shadow && (gemv_only || !cqs::use_mfma(nb, x->dim)) && nb <= cqs::kShadowMaxQ &&
-                            cqs::shadow_kprime(k_eff) >= k_eff;
-        if (shadow) {
-            redo.clear();
-            rc = shadow_block(x, qs, done, bad.data(), nb, k_eff, d_keep, mode, threshold, redo);
-            if (rc != CQS_HIP_OK) return rc;
-            // the queries the certificate did not cover: same call, f32 scan (redo is ascending: rows only move down)
-            for (uint32_t j = 0; j < (uint32_t)redo.size(); ++j) {
-                if (redo[j] != j) memcpy(x->h_q + (size_t)j * x->dim, x->h_q + (size_t)redo[j] * x->dim, (size_t)x->dim * sizeof(float));
-                map.push_back(done + redo[j]);
-            }
-        } else {
-            for (uint32_t i = 0; i < nb; ++i) map.push_back(done + i);
+        if (shadow_takes(x, nb, k_eff, gemv_only)) {
+            if ((rc = host_block(x, staged.data(), nb, k_eff, d_keep, mode, threshold, gemv_only, &redo)) != CQS_HIP_OK) return rc;
+            staged.swap(redo);   // the queries the certificate did not cover: same call, f32 scan
         }
-        if (!map.empty()) {
-            rc = f32_block(x, qs, map.data(), bad.data(), (uint32_t)map.size(), k_eff, d_keep, mode, threshold, gemv_only);
-            if (rc != CQS_HIP_OK) return rc;
-        }
+        if (!staged.empty() &&
+            (rc = host_block(x, staged.data(), (uint32_t)staged.size(), k_eff, d_keep, mode, threshold, gemv_only, nullptr)) != CQS_HIP_OK)
+            return rc;
         done += nb;
     }
     return CQS_HIP_OK;
@@ -1038,14 +811,14 @@ static uint32_t count_like_front(const cqs_hip_index* x) {
 static int32_t combine_run_single(cqs_hip_index* x, cqs_combine_req* const* batch, uint32_t nb) {
     std::lock_guard<std::mutex> dev(x->mu);       // (other entry points - device API searches, extend, save - order with the pass here)
     if (x->poisoned.load(std::memory_order_acquire)) return CQS_HIP_ERR_POISONED;
-    HostQuery hq[kCombineCap];
-    for (uint32_t i = 0; i < nb; ++i) hq[i] = HostQuery{batch[i]->q, batch[i]->out_rows, batch[i]->out_scores, batch[i]->out_count};
+    cqs_combine_req rq[kCombineCap];
+    for (uint32_t i = 0; i < nb; ++i) rq[i] = *batch[i];
     // gemv passes only: each caller gets its lone call's bits.  CQS_HIP_COMBINE_BITS=relaxed (opt-in, read at create) lets a
     // block of >= 9 callers take the matrix-core kernel instead - 32 queries per corpus sweep instead of 8, scores in another
     // summation order (|delta| <= 2e-6 on unit vectors, inside the parity tolerance; the reference's GPU backend promises no
     // bit-reproducibility across calls either, src/cagra.rs:443-492)
     const bool gemv_only = !(x->combine_relaxed && nb >= cqs::kMfmaMinQueries);
-    return search_host_locked(x, hq, nb, batch[0]->k, nullptr, batch[0]->mode, batch[0]->thr, gemv_only);
+    return search_host_locked(x, rq, nb, batch[0]->k, nullptr, batch[0]->mode, batch[0]->thr, gemv_only);
 }
 
 // Lead one pass.  `lk` holds cmu on entry and on exit; x->leader is set by the caller.
@@ -1173,10 +946,10 @@ int32_t cqs_hip_index_search(cqs_hip_index* x, const float* queries, uint32_t b,
     if (k > kMaxK) return fail(x, CQS_HIP_ERR_INVALID, "search: k > max_k");
     if (mode > CQS_HIP_MODE_PIPELINE) return fail(x, CQS_HIP_ERR_INVALID, "search: bad mode");
     if (!out_rows || !out_scores) return fail(x, CQS_HIP_ERR_INVALID, "search: null output buffer");
-    std::vector<HostQuery> hq(b);
+    std::vector<cqs_combine_req> rq(b);
     for (uint32_t i = 0; i < b; ++i)
-        hq[i] = HostQuery{queries + (size_t)i * x->dim, out_rows + (size_t)i * k, out_scores + (size_t)i * k, out_counts + i};
-    return search_host_locked(x, hq.data(), b, k, keep_bitset, mode, threshold, /*gemv_only=*/false);
+        rq[i] = cqs_combine_req{queries + (size_t)i * x->dim, k, mode, threshold, out_rows + (size_t)i * k, out_scores + (size_t)i * k, out_counts + i};
+    return search_host_locked(x, rq.data(), b, k, keep_bitset, mode, threshold, /*gemv_only=*/false);
 } CQS_ABI_CATCH(x)
 
 // Combining-queue counters since the handle was made: passes run by the queue and the queries they carried (bench /
@@ -1184,42 +957,6 @@ int32_t cqs_hip_index_search(cqs_hip_index* x, const float* queries, uint32_t b,
 void cqs_hip_index_combine_stats(const cqs_hip_index* x, uint64_t* passes, uint64_t* queries) CQS_ABI_TRY {
     if (passes) *passes = x ? x->stat_passes.load(std::memory_order_relaxed) : 0;
     if (queries) *queries = x ? x->stat_queries.load(std::memory_order_relaxed) : 0;
-} CQS_ABI_CATCH_VOID
-
-// bf16 shadow of the corpus for `VectorIndex::search` (src/index.rs:146; the reference's GPU backend keeps its f32
-// dataset resident, src/cagra.rs:255-277): host searches that run as gemv passes scan n x dim x 2 B instead of x 4 and
-// return the f32 scan's bytes (scan_bf16.h).  Owned single-device handles only.
-int32_t cqs_hip_index_set_bf16_scan(cqs_hip_index* x, int32_t enable) CQS_ABI_TRY {
-    if (!x) return CQS_HIP_ERR_INVALID;
-    if (x->sh) return CQS_HIP_ERR_INVALID;   // a row-sharded parent: out of scope (header)
-    std::lock_guard<std::mutex> g(x->mu);
-    if (x->poisoned.load(std::memory_order_acquire)) return CQS_HIP_ERR_POISONED;
-    HIP_TRY(x, hipSetDevice(x->device));
-    HIP_TRY(x, quiesce(x));   // a search enqueued on a caller stream may still read the shadow
-    if (!enable) { shadow_free(x); return CQS_HIP_OK; }
-    // a borrowed handle gets its shadow at create or not at all: enabling it later would snapshot rows the caller may have
-    // changed since (test_invalid_handles); disabling above works on every handle
-    if (x->borrow) return fail(x, CQS_HIP_ERR_INVALID, "set_bf16_scan: index borrows its rows (they may change under the bound)");
-    return shadow_enable(x, "set_bf16_scan");
-} CQS_ABI_CATCH(x)
-
-void cqs_hip_index_bf16_stats(const cqs_hip_index* x, uint64_t* bytes, uint64_t* certified, uint64_t* fallbacks) CQS_ABI_TRY {
-    uint64_t by = 0, c = 0, f = 0;
-    if (x && !x->sh) {
-        cqs_hip_index* m = const_cast<cqs_hip_index*>(x);   // (waits for the device-API searches whose counts it reads)
-        std::lock_guard<std::mutex> g(m->mu);
-        by = m->d_shadow ? m->shadow_cap * m->dim * sizeof(uint16_t) : 0;
-        c = m->stat_certified.load(std::memory_order_relaxed);
-        f = m->stat_fallbacks.load(std::memory_order_relaxed);
-        unsigned long long dc[2];
-        if (m->d_shadow_stats && hipSetDevice(m->device) == hipSuccess && quiesce(m) == hipSuccess && shadow_device_counts(m, dc)) {
-            c += dc[0];
-            f += dc[1];
-        }
-    }
-    if (bytes) *bytes = by;
-    if (certified) *certified = c;
-    if (fallbacks) *fallbacks = f;
 } CQS_ABI_CATCH_VOID
 
 // `find_neighbors` (src/cli/commands/search/neighbors.rs:86-132) for a row of this index: the query is the
@@ -1242,7 +979,7 @@ int32_t cqs_hip_index_neighbors(cqs_hip_index* x, uint64_t target_row, uint32_t 
     if (x->n <= 1) return CQS_HIP_OK;
     const uint32_t k = (uint64_t)limit + 1u < x->n ? limit + 1u : (uint32_t)x->n;
     HIP_TRY(x, hipSetDevice(x->device));
-    if (x->done_valid && x->done_stream != x->stream) HIP_TRY(x, hipStreamWaitEvent(x->stream, x->done, 0));
+    HIP_TRY(x, order_after_last(x, x->stream));
     int32_t rc = ensure_scratch(x, 1, k);
     if (rc != CQS_HIP_OK) return rc;
     const float* d_target = x->d_rows + (size_t)(target_row - x->row_base) * x->dim;
@@ -1297,32 +1034,6 @@ int32_t cqs_hip_index_scan_time(cqs_hip_index* x, uint32_t* launches, double* to
 void cqs_hip_debug_index_fail_next(cqs_hip_index* x) CQS_ABI_TRY {
     if (x) x->inject_fail.store(1, std::memory_order_release);
 } CQS_ABI_CATCH_VOID
-
-// Test hook (not part of the public header): B_q of `b` host queries [b, dim] as the device computes it for a device-API
-// search (launch_shadow_bound) and as the host function computes it from a plain f64 loop (shadow_query_bound), both
-// against this handle's shadow.  INVALID without a shadow or for b > kShadowMaxQ.
-int32_t cqs_hip_debug_shadow_bound(cqs_hip_index* x, const float* queries, uint32_t b, float* out_device, float* out_host) CQS_ABI_TRY {
-    if (!x || x->sh || !queries || !out_device || !out_host || b == 0) return CQS_HIP_ERR_INVALID;
-    std::lock_guard<std::mutex> g(x->mu);
-    if (!x->d_shadow || b > cqs::kShadowMaxQ) return CQS_HIP_ERR_INVALID;
-    HIP_TRY(x, hipSetDevice(x->device));
-    HIP_TRY(x, quiesce(x));   // d_bq belongs to the searches
-    float* d_q = nullptr;
-    HIP_TRY(x, hipMalloc(&d_q, (size_t)b * x->dim * sizeof(float)));
-    hipError_t e = hipMemcpyAsync(d_q, queries, (size_t)b * x->dim * sizeof(float), hipMemcpyHostToDevice, x->stream);
-    if (e == hipSuccess) e = cqs::launch_shadow_bound(d_q, b, x->dim, x->shadow_r, x->shadow_norm, x->d_bq, x->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(out_device, x->d_bq, (size_t)b * sizeof(float), hipMemcpyDeviceToHost, x->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(x->stream);
-    hipFree(d_q);
-    HIP_TRY(x, e);
-    for (uint32_t i = 0; i < b; ++i) {
-        const float* q = queries + (size_t)i * x->dim;
-        double s2 = 0.0;
-        for (uint32_t d = 0; d < x->dim; ++d) s2 += (double)q[d] * (double)q[d];
-        out_host[i] = cqs::shadow_query_bound(s2, x->shadow_r, x->shadow_norm, x->dim);
-    }
-    return CQS_HIP_OK;
-} CQS_ABI_CATCH(x)
 
 // Bench aid (not part of the public header): `n_threads` native threads, each calling the PUBLIC blocking entry point
 // cqs_hip_index_search `per_thread` times with one query at a time (thread t asks queries t, t + n_threads, ... of the

@@ -15,9 +15,10 @@
 #include "scan_kernels.h"
 
 namespace cqs_sharded { struct ShardSet; }
+namespace cqs_idx { struct Shadow; }
 
-// One single-query host search waiting for a pass over the corpus (the combining queue of cqs_hip_index_search).
-// Lives on its caller's stack; the pointers are the caller's own output buffers.
+// One single-query host search: its query, parameters and output buffers (the caller's own).  The combining queue of
+// cqs_hip_index_search parks these on their callers' stacks; the host search runs blocks of them (index.hip).
 struct cqs_combine_req {
     const float* q;          // [dim] host, validated (finite)
     uint32_t k, mode;
@@ -99,24 +100,8 @@ struct cqs_hip_index {
     std::atomic<uint64_t> stat_passes{0}, stat_queries{0};   // combined passes run / queries they carried
     std::atomic<int32_t> inject_fail{0};  // test hook (cqs_hip_debug_index_fail_next): the next host search fails as a device error
 
-    // bf16 shadow (built at create / load where it pays, CQS_HIP_SCAN_BF16, or cqs_hip_index_set_bf16_scan; null = off):
-    // searches of gemv blocks scan it first, rescore the candidates from d_rows and fall back to the f32 scan for any query
-    // the certificate does not cover (scan_bf16.h): host searches from the host, device-API searches through the gated f32
-    // launches.  On a borrowed handle it is a snapshot of the caller's rows taken at create.
-    uint16_t* d_shadow = nullptr;         // [shadow_cap, dim] bf16
-    uint64_t shadow_cap = 0;              // rows the shadow buffer holds (follows cap_rows)
-    double shadow_r = 0.0;                // max over the finite rows of ||x - x~|| + gamma (||x|| + ||x~||)
-    double shadow_norm = 0.0;             // max over the finite rows of max(||x||, ||x~||)
-    unsigned long long* d_shadow_stats = nullptr;   // [5] the build pass's maxima (f64 bits) and outlier flag, then the
-                                                    // device-API searches' certified / fallback counts (certify adds)
-    uint64_t* d_akeys = nullptr;          // [kShadowMaxQ, kMaxK] approximate keys of the select
-    uint32_t* d_acounts = nullptr;        // [kShadowMaxQ]
-    uint64_t* d_ekeys = nullptr;          // [kShadowMaxQ, kMaxK - 1] rescored keys
-    uint32_t* d_cert = nullptr;           // [kShadowMaxQ] certified flags (device-API searches: the f32 gate; host searches:
-                                          // when h_cert is not mappable)
-    float* d_bq = nullptr;                // [kShadowMaxQ] B_q of each query of the block (launch_shadow_bound)
-    uint32_t* h_cert = nullptr;           // pinned [kShadowMaxQ]
-    uint32_t* h_cert_dev = nullptr;       // its device-visible address (null: not mappable)
+    // bf16 shadow (index_shadow.hip; null = off).  Its certified / fallback counts outlive it: they live on the handle.
+    cqs_idx::Shadow* shadow = nullptr;
     std::atomic<uint64_t> stat_certified{0}, stat_fallbacks{0};
 };
 
@@ -127,33 +112,48 @@ constexpr uint64_t kNtBytes = 200ull << 20;  // corpus larger than this streams 
 constexpr uint32_t kGauxQueries = 32;        // query blocks up to this size (every gemv block the host paths form) carry the select's (argmax, runner-up) index
 constexpr uint32_t kGauxMinK = 100;          // ... and only from this k on (below it the gather it replaces is a few groups)
 constexpr size_t kDirectOutKeys = 8192;      // host searches of up to this many result keys have them written straight to pinned host memory
-// bf16 shadow built automatically at create / load (CQS_HIP_SCAN_BF16 unset) from this f32 corpus size on: 4x the 256 MB
-// Infinity Cache, where the f32 scan streams from HBM alone and half the bytes is close to half the time
-constexpr uint64_t kShadowAutoBytes = 1ull << 30;
-// ... and only if, once it is allocated, the device still has max(this, kShadowFreeFrac of its memory) free
-constexpr uint64_t kShadowFreeMinBytes = 4ull << 30;
-constexpr double kShadowFreeFrac = 0.10;
 
 uint64_t pad_rows(uint64_t n);
 int32_t fail(cqs_hip_index* idx, int32_t code, const char* what, hipError_t e = hipSuccess);
 void free_scratch(cqs_hip_index* x);
 int32_t ensure_scratch(cqs_hip_index* x, uint32_t b, uint32_t k);
 uint32_t max_query_block(const cqs_hip_index* x);
+// Scan + select arguments over the handle's corpus.  elem_bytes (4 f32, 2 the bf16 shadow) sizes `nontemporal`.
+cqs::ScanArgs scan_args(const cqs_hip_index* x, const float* d_q, uint32_t b, uint32_t k, const uint32_t* d_keep,
+                        uint32_t mode, float thr, size_t elem_bytes, bool gemv_only, void* dbg, const uint32_t* gate);
+// The scan of `a` on st (the bf16 one over `bf16` when set; timed unless a.gate: the shadow scan was), then the select.
+int32_t scan_select(cqs_hip_index* x, const cqs::ScanArgs& a, hipStream_t st, const uint16_t* bf16, const float* bq,
+                    uint64_t* out_keys, uint32_t* out_counts);
+// Searches share one scratch: order `st` after the last search / record `done` on `st` at the end of one.  Caller holds mu.
+inline hipError_t order_after_last(cqs_hip_index* x, hipStream_t st) {
+    return x->done_valid && x->done_stream != st ? hipStreamWaitEvent(st, x->done, 0) : hipSuccess;
+}
+inline hipError_t record_done(cqs_hip_index* x, hipStream_t st) {
+    const hipError_t e = hipEventRecord(x->done, st);
+    if (e == hipSuccess) { x->done_stream = st; x->done_valid = true; }
+    return e;
+}
 // Enqueue scan + select for queries already on the device.  Caller holds mu.  gate: ScanArgs::gate (gemv blocks only).
 int32_t enqueue_search(cqs_hip_index* x, const float* d_q, uint32_t b, uint32_t k, const uint32_t* d_keep,
                        uint32_t mode, float thr, uint64_t* d_out_keys, uint32_t* d_out_counts, hipStream_t st,
                        bool gemv_only = false, const uint32_t* gate = nullptr);
 hipError_t quiesce(cqs_hip_index* x);
-// bf16 shadow (index.hip).  Caller holds mu.
-void shadow_free(cqs_hip_index* x);
 // cqs_hip_index_create without the bf16 shadow policy (the shards of a row-sharded parent stay on f32)
 int32_t create_owned(const float* rows, uint64_t n, uint32_t dim, uint32_t metric, int32_t device, uint64_t row_base,
                      cqs_hip_index** out);
-int32_t shadow_extend(cqs_hip_index* x, uint64_t n_old);
 int32_t stage_keep(cqs_hip_index* x, const uint32_t* host_words, uint64_t words);
 int32_t create_common(uint64_t n, uint32_t dim, uint32_t metric, int32_t device, uint64_t row_base,
                       cqs_hip_index** out, cqs_hip_index** made);
 void read_combine_env(cqs_hip_index* x);
+// bf16 shadow (index_shadow.hip).  Caller holds mu (or owns the new handle).
+int32_t shadow_auto(cqs_hip_index* x);
+int32_t shadow_extend(cqs_hip_index* x, uint64_t n_old);
+void shadow_free(cqs_hip_index* x);
+bool shadow_takes(const cqs_hip_index* x, uint32_t b, uint32_t k, bool gemv_only);
+int32_t shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k, const uint32_t* d_keep, uint32_t mode,
+                    float thr, uint64_t* out_keys, uint32_t* out_counts, hipStream_t st, const uint32_t** device_gate);
+// The last host shadow pass's verdicts, pinned, valid after x->stream's wait (queues their copy when not mappable).
+hipError_t shadow_verdicts(cqs_hip_index* x, uint32_t nb, const uint32_t** h_cert);
 
 // persistence over one or more device segments in row order (index.hip)
 struct Segment { int device; float* d_rows; uint64_t rows; hipStream_t stream; };

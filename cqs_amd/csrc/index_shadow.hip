@@ -1,0 +1,288 @@
+// index_shadow.hip — host side of the dense index's bf16 shadow (scan_bf16.h), behind one handle pointer.
+#include <cstdlib>
+#include <cstring>
+#include <new>
+
+#include "abi_guard.h"
+#include "index_internal.h"
+#include "scan_bf16.h"
+
+namespace cqs_idx {
+
+// bf16 shadow built automatically at create / load (CQS_HIP_SCAN_BF16 unset) from this f32 corpus size on: 4x the 256 MB
+// Infinity Cache, where the f32 scan streams from HBM alone and half the bytes is close to half the time
+constexpr uint64_t kShadowAutoBytes = 1ull << 30;
+// ... and only if, once it is allocated, the device still has max(this, kShadowFreeFrac of its memory) free
+constexpr uint64_t kShadowFreeMinBytes = 4ull << 30;
+constexpr double kShadowFreeFrac = 0.10;
+
+// Built at create / load where it pays, CQS_HIP_SCAN_BF16, or cqs_hip_index_set_bf16_scan: searches of gemv blocks scan it
+// first, rescore the candidates from the f32 rows and fall back to the f32 scan for any query the certificate does not
+// cover (scan_bf16.h): host searches from the host, device-API searches through the gated f32 launches.  On a borrowed
+// handle it is a snapshot of the caller's rows taken at create.
+struct Shadow {
+    uint16_t* d_bf16 = nullptr;           // [cap, dim] bf16
+    uint64_t cap = 0;                     // rows the buffer holds (follows cap_rows)
+    double r = 0.0;                       // max over the finite rows of ||x - x~|| + gamma (||x|| + ||x~||)
+    double norm = 0.0;                    // max over the finite rows of max(||x||, ||x~||)
+    unsigned long long* d_stats = nullptr;   // [5] the build pass's maxima (f64 bits) and outlier flag, then the
+                                             // device-API searches' certified / fallback counts (certify adds)
+    uint64_t* d_akeys = nullptr;          // [kShadowMaxQ, kMaxK] approximate keys of the select
+    uint32_t* d_acounts = nullptr;        // [kShadowMaxQ]
+    uint64_t* d_ekeys = nullptr;          // [kShadowMaxQ, kMaxK - 1] rescored keys
+    uint32_t* d_cert = nullptr;           // [kShadowMaxQ] certified flags (device-API searches: the f32 gate; host searches:
+                                          // when h_cert is not mappable)
+    float* d_bq = nullptr;                // [kShadowMaxQ] B_q of each query of the block (launch_shadow_bound)
+    uint32_t* h_cert = nullptr;           // pinned [kShadowMaxQ]
+    uint32_t* h_cert_dev = nullptr;       // its device-visible address (null: not mappable)
+};
+
+// Add what the device-API searches' certify launches counted (d_stats[3, 5)) to *certified / *fallbacks, once every
+// search has completed (quiesce).  Caller holds mu.
+static void shadow_device_counts(cqs_hip_index* x, uint64_t* certified, uint64_t* fallbacks) {
+    unsigned long long c[2];
+    if (!x->shadow || !x->shadow->d_stats || quiesce(x) != hipSuccess) return;
+    hipError_t e = hipMemcpyAsync(c, x->shadow->d_stats + 3, sizeof c, hipMemcpyDeviceToHost, x->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(x->stream);
+    if (e != hipSuccess) { (void)hipGetLastError(); return; }
+    *certified += c[0];
+    *fallbacks += c[1];
+}
+
+void shadow_free(cqs_hip_index* x) {
+    Shadow* s = x->shadow;
+    if (!s) return;
+    uint64_t c = 0, f = 0;   // the counts outlive the shadow
+    shadow_device_counts(x, &c, &f);
+    x->stat_certified.fetch_add(c, std::memory_order_relaxed);
+    x->stat_fallbacks.fetch_add(f, std::memory_order_relaxed);
+    hipFree(s->d_bf16); hipFree(s->d_stats); hipFree(s->d_akeys); hipFree(s->d_acounts); hipFree(s->d_ekeys);
+    hipFree(s->d_cert); hipFree(s->d_bq); hipHostFree(s->h_cert);
+    delete s;
+    x->shadow = nullptr;
+}
+
+// Convert rows [row0, x->n) into the shadow and fold them into R.  Caller holds mu, the stream is idle.  *outlier: a finite
+// row has a component of magnitude >= 2^64 (the shadow cannot certify against it).
+static int32_t shadow_convert(cqs_hip_index* x, uint64_t row0, bool* outlier) {
+    Shadow* s = x->shadow;
+    HIP_TRY(x, hipMemsetAsync(s->d_stats + 2, 0, sizeof(unsigned long long), x->stream));
+    HIP_TRY(x, cqs::launch_shadow_build(x->d_rows, s->d_bf16, row0, x->n - row0, x->dim, cqs::shadow_gamma(x->dim),
+                                        s->d_stats, x->stream));
+    unsigned long long st[3];
+    HIP_TRY(x, hipMemcpyAsync(st, s->d_stats, sizeof st, hipMemcpyDeviceToHost, x->stream));
+    HIP_TRY(x, hipStreamSynchronize(x->stream));
+    double r, m;
+    memcpy(&r, &st[0], sizeof r);
+    memcpy(&m, &st[1], sizeof m);
+    s->r = r * (1.0 + 0x1p-30);      // (f64 sums of <= 2048 squares and three square roots: relative error < 2^-40)
+    s->norm = m * (1.0 + 0x1p-30);
+    *outlier = st[2] != 0;
+    return CQS_HIP_OK;
+}
+
+// extend() on a handle with the shadow on: grow it with cap_rows, convert rows [n_old, n).  A failure here (no memory,
+// an outlier row) turns the shadow off and leaves the f32 index as extended: the call still succeeds.
+int32_t shadow_extend(cqs_hip_index* x, uint64_t n_old) {
+    Shadow* s = x->shadow;
+    if (!s) return CQS_HIP_OK;
+    if (x->cap_rows > s->cap) {
+        uint16_t* nd = nullptr;
+        if (hipMalloc(&nd, (size_t)x->cap_rows * x->dim * sizeof(uint16_t)) != hipSuccess) {
+            (void)hipGetLastError();
+            shadow_free(x);
+            x->last_error = "extend: no device memory to grow the bf16 shadow; shadow turned off";
+            return CQS_HIP_OK;
+        }
+        hipError_t e = hipMemcpyAsync(nd, s->d_bf16, (size_t)n_old * x->dim * sizeof(uint16_t), hipMemcpyDeviceToDevice, x->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(x->stream);
+        if (e != hipSuccess) { hipFree(nd); return fail(x, CQS_HIP_ERR_DEVICE, "extend: shadow copy", e); }
+        hipFree(s->d_bf16);
+        s->d_bf16 = nd;
+        s->cap = x->cap_rows;
+    }
+    bool outlier = false;
+    const int32_t rc = shadow_convert(x, n_old, &outlier);
+    if (rc != CQS_HIP_OK) return rc;
+    if (outlier) {
+        shadow_free(x);
+        x->last_error = "extend: a new row has a component of magnitude >= 2^64; bf16 shadow turned off";
+    }
+    return CQS_HIP_OK;
+}
+
+// The shadow's dim rule (16-byte loads of 8 components, up to kShadowMaxDim) and how last_error states it.
+static bool dim_ok(uint32_t dim) { return dim % 8u == 0u && dim <= cqs::kShadowMaxDim; }
+static const char* const kDimRule = ": dim must be a multiple of 8 and <= 2048";
+
+// Allocate and build the shadow over rows [0, n) (no borrow check: the create policy snapshots borrowed rows too).  On
+// failure the shadow is freed and `fail` has put `what: reason` in last_error.  Caller holds mu (or owns the new handle).
+static int32_t shadow_enable(cqs_hip_index* x, const char* what) {
+    std::string pre(what);
+    if (!dim_ok(x->dim)) return fail(x, CQS_HIP_ERR_INVALID, (pre + kDimRule).c_str());
+    if (x->shadow) return CQS_HIP_OK;
+    auto oom = [&](hipError_t e) { (void)hipGetLastError(); shadow_free(x); return fail(x, CQS_HIP_ERR_NOMEM, (pre + ": allocation").c_str(), e); };
+    Shadow* s = x->shadow = new (std::nothrow) Shadow();
+    if (!s) return oom(hipErrorOutOfMemory);
+    const uint64_t cap = x->cap_rows ? x->cap_rows : 1;
+    hipError_t e;
+    if ((e = hipMalloc(&s->d_bf16, (size_t)cap * x->dim * sizeof(uint16_t))) != hipSuccess) return oom(e);
+    s->cap = cap;
+    unsigned long long* stats = nullptr;   // zeroed before it is the shadow's: shadow_free reads its counts
+    if ((e = hipMalloc(&stats, 5 * sizeof(unsigned long long))) != hipSuccess) return oom(e);
+    if ((e = hipMemsetAsync(stats, 0, 5 * sizeof(unsigned long long), x->stream)) != hipSuccess) { hipFree(stats); return oom(e); }
+    s->d_stats = stats;
+    if ((e = hipMalloc(&s->d_akeys, (size_t)cqs::kShadowMaxQ * cqs::kMaxK * sizeof(uint64_t))) != hipSuccess) return oom(e);
+    if ((e = hipMalloc(&s->d_acounts, (size_t)cqs::kShadowMaxQ * sizeof(uint32_t))) != hipSuccess) return oom(e);
+    if ((e = hipMalloc(&s->d_ekeys, (size_t)cqs::kShadowMaxQ * (cqs::kMaxK - 1) * sizeof(uint64_t))) != hipSuccess) return oom(e);
+    if ((e = hipMalloc(&s->d_cert, (size_t)cqs::kShadowMaxQ * sizeof(uint32_t))) != hipSuccess) return oom(e);
+    if ((e = hipMalloc(&s->d_bq, (size_t)cqs::kShadowMaxQ * sizeof(float))) != hipSuccess) return oom(e);
+    if ((e = hipHostMalloc(&s->h_cert, (size_t)cqs::kShadowMaxQ * sizeof(uint32_t), hipHostMallocDefault)) != hipSuccess) return oom(e);
+    if (hipHostGetDevicePointer((void**)&s->h_cert_dev, s->h_cert, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        s->h_cert_dev = nullptr;
+    }
+    bool outlier = false;
+    const int32_t rc = shadow_convert(x, 0, &outlier);
+    if (rc != CQS_HIP_OK) { shadow_free(x); return rc; }
+    if (outlier) {
+        shadow_free(x);
+        return fail(x, CQS_HIP_ERR_INVALID, (pre + ": a finite row has a component of magnitude >= 2^64").c_str());
+    }
+    return CQS_HIP_OK;
+}
+
+// The shadow policy of create / create_device / load, for a single-device handle whose rows are in place.
+// CQS_HIP_SCAN_BF16 (read here, at create): unset = where it pays (f32 corpus >= kShadowAutoBytes), 0 = never, 1 = at any
+// size; dim, outlier and free-memory rules either way.  The create never fails for the shadow's sake: the handle then
+// searches the f32 rows and last_error says why.  Returns an error only for a device fault (the handle is poisoned).
+int32_t shadow_auto(cqs_hip_index* x) {
+    const char* env = getenv("CQS_HIP_SCAN_BF16");
+    if (env && env[0] == '0') return CQS_HIP_OK;
+    const bool any_size = env && env[0] == '1';
+    const uint64_t f32_bytes = x->n * x->dim * sizeof(float);
+    if (!any_size && f32_bytes < kShadowAutoBytes) {
+        x->last_error = "bf16 shadow not built: f32 corpus below 1 GiB (CQS_HIP_SCAN_BF16=1 builds it at any size)";
+        return CQS_HIP_OK;
+    }
+    if (!dim_ok(x->dim)) {
+        x->last_error = std::string("bf16 shadow not built") + kDimRule;
+        return CQS_HIP_OK;
+    }
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
+        (void)hipGetLastError();
+        x->last_error = "bf16 shadow not built: hipMemGetInfo failed";
+        return CQS_HIP_OK;
+    }
+    const uint64_t cap = x->cap_rows ? x->cap_rows : 1;
+    const uint64_t need = cap * x->dim * sizeof(uint16_t) + (2ull * cqs::kMaxK + 2ull) * cqs::kShadowMaxQ * sizeof(uint64_t);
+    const uint64_t frac = (uint64_t)(kShadowFreeFrac * (double)total_b);
+    const uint64_t reserve = frac > kShadowFreeMinBytes ? frac : kShadowFreeMinBytes;
+    if (free_b < need || free_b - need < reserve) {
+        x->last_error = "bf16 shadow not built: the device would keep less than max(4 GiB, 10 %) of its memory free";
+        return CQS_HIP_OK;
+    }
+    const int32_t rc = shadow_enable(x, "bf16 shadow not built");
+    return rc == CQS_HIP_ERR_DEVICE ? rc : CQS_HIP_OK;
+}
+
+// Blocks that run as gemv passes (the matrix-core blocks' scores are not the gemv kernel's) of up to kShadowMaxQ queries,
+// at a k the shadow can certify (k' < k only at k = kMaxK).
+bool shadow_takes(const cqs_hip_index* x, uint32_t b, uint32_t k, bool gemv_only) {
+    return x->shadow && b <= cqs::kShadowMaxQ && (gemv_only || !cqs::use_mfma(b, x->dim)) && cqs::shadow_kprime(k) >= k;
+}
+
+// The shadow half of a gemv block on `st`: B_q -> shadow scan -> select k' + 1 -> rescore + certify into out_keys /
+// out_counts.  device_gate (device-API searches): `st` is ordered after the last search here, certify counts outcomes on
+// the device, *device_gate = the verdicts that must gate the f32 launches next.  Null: host searches (shadow_verdicts).
+int32_t shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k, const uint32_t* d_keep, uint32_t mode,
+                    float threshold, uint64_t* out_keys, uint32_t* out_counts, hipStream_t st, const uint32_t** device_gate) {
+    const Shadow* s = x->shadow;
+    uint32_t* const cert = device_gate || !s->h_cert_dev ? s->d_cert : s->h_cert_dev;
+    if (device_gate) *device_gate = cert;
+    if (device_gate) HIP_TRY(x, order_after_last(x, st));
+    const uint32_t kp = cqs::shadow_kprime(k);
+    HIP_TRY(x, cqs::launch_shadow_bound(d_q, nb, x->dim, s->r, s->norm, s->d_bq, st));
+    // gemv passes over the bf16 rows (non-uniform tiers, no debug stamps), top k' + 1; the select's (argmax, runner-up)
+    // index from kGauxMinK on whatever CQS_HIP_SELECT_AUX says (that A/B hook is the f32 select's)
+    const cqs::ScanArgs a = scan_args(x, d_q, nb, kp + 1u, d_keep, mode, threshold, sizeof(uint16_t), true, nullptr, nullptr);
+    const int32_t rc = scan_select(x, a, st, s->d_bf16, s->d_bq, s->d_akeys, s->d_acounts);
+    if (rc == CQS_HIP_OK)
+        HIP_TRY(x, cqs::launch_rescore_certify(x->d_rows, x->dim, d_q, nb, k, kp, mode, threshold, (uint32_t)x->row_base,
+                                               s->d_bq, s->d_akeys, s->d_acounts, s->d_ekeys, out_keys, out_counts, cert,
+                                               device_gate ? s->d_stats + 3 : nullptr, st));
+    return rc;
+}
+
+hipError_t shadow_verdicts(cqs_hip_index* x, uint32_t nb, const uint32_t** h_cert) {
+    const Shadow* s = x->shadow;
+    *h_cert = s->h_cert;
+    return s->h_cert_dev ? hipSuccess : hipMemcpyAsync(s->h_cert, s->d_cert, (size_t)nb * sizeof(uint32_t), hipMemcpyDeviceToHost, x->stream);
+}
+
+}  // namespace cqs_idx
+
+using namespace cqs_idx;
+
+extern "C" {
+
+// bf16 shadow of the corpus for `VectorIndex::search` (src/index.rs:146; the reference's GPU backend keeps its f32
+// dataset resident, src/cagra.rs:255-277): host searches that run as gemv passes scan n x dim x 2 B instead of x 4 and
+// return the f32 scan's bytes (scan_bf16.h).  Owned single-device handles only.
+int32_t cqs_hip_index_set_bf16_scan(cqs_hip_index* x, int32_t enable) CQS_ABI_TRY {
+    if (!x || x->sh) return CQS_HIP_ERR_INVALID;   // (a row-sharded parent: out of scope, header)
+    std::lock_guard<std::mutex> g(x->mu);
+    if (x->poisoned.load(std::memory_order_acquire)) return CQS_HIP_ERR_POISONED;
+    HIP_TRY(x, hipSetDevice(x->device));
+    HIP_TRY(x, quiesce(x));   // a search enqueued on a caller stream may still read the shadow
+    if (!enable) { shadow_free(x); return CQS_HIP_OK; }
+    // a borrowed handle gets its shadow at create or not at all: enabling it later would snapshot rows the caller may have
+    // changed since (test_invalid_handles); disabling above works on every handle
+    if (x->borrow) return fail(x, CQS_HIP_ERR_INVALID, "set_bf16_scan: index borrows its rows (they may change under the bound)");
+    return shadow_enable(x, "set_bf16_scan");
+} CQS_ABI_CATCH(x)
+
+void cqs_hip_index_bf16_stats(const cqs_hip_index* x, uint64_t* bytes, uint64_t* certified, uint64_t* fallbacks) CQS_ABI_TRY {
+    uint64_t by = 0, c = 0, f = 0;
+    if (x && !x->sh) {
+        cqs_hip_index* m = const_cast<cqs_hip_index*>(x);   // (waits for the device-API searches whose counts it reads)
+        std::lock_guard<std::mutex> g(m->mu);
+        by = m->shadow ? m->shadow->cap * m->dim * sizeof(uint16_t) : 0;
+        c = m->stat_certified.load(std::memory_order_relaxed);
+        f = m->stat_fallbacks.load(std::memory_order_relaxed);
+        if (m->shadow && hipSetDevice(m->device) == hipSuccess) shadow_device_counts(m, &c, &f);
+    }
+    if (bytes) *bytes = by;
+    if (certified) *certified = c;
+    if (fallbacks) *fallbacks = f;
+} CQS_ABI_CATCH_VOID
+
+// Test hook (not part of the public header): B_q of `b` host queries [b, dim] as the device computes it for a device-API
+// search (launch_shadow_bound) and as the host function computes it from a plain f64 loop (shadow_query_bound), both
+// against this handle's shadow.  INVALID without a shadow or for b > kShadowMaxQ.
+int32_t cqs_hip_debug_shadow_bound(cqs_hip_index* x, const float* queries, uint32_t b, float* out_device, float* out_host) CQS_ABI_TRY {
+    if (!x || x->sh || !queries || !out_device || !out_host || b == 0) return CQS_HIP_ERR_INVALID;
+    std::lock_guard<std::mutex> g(x->mu);
+    const Shadow* s = x->shadow;
+    if (!s || b > cqs::kShadowMaxQ) return CQS_HIP_ERR_INVALID;
+    HIP_TRY(x, hipSetDevice(x->device));
+    HIP_TRY(x, quiesce(x));   // d_bq belongs to the searches
+    float* d_q = nullptr;
+    HIP_TRY(x, hipMalloc(&d_q, (size_t)b * x->dim * sizeof(float)));
+    hipError_t e = hipMemcpyAsync(d_q, queries, (size_t)b * x->dim * sizeof(float), hipMemcpyHostToDevice, x->stream);
+    if (e == hipSuccess) e = cqs::launch_shadow_bound(d_q, b, x->dim, s->r, s->norm, s->d_bq, x->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_device, s->d_bq, (size_t)b * sizeof(float), hipMemcpyDeviceToHost, x->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(x->stream);
+    hipFree(d_q);
+    HIP_TRY(x, e);
+    for (uint32_t i = 0; i < b; ++i) {
+        const float* q = queries + (size_t)i * x->dim;
+        double s2 = 0.0;
+        for (uint32_t d = 0; d < x->dim; ++d) s2 += (double)q[d] * (double)q[d];
+        out_host[i] = cqs::shadow_query_bound(s2, s->r, s->norm, x->dim);
+    }
+    return CQS_HIP_OK;
+} CQS_ABI_CATCH(x)
+
+}  // extern "C"
