@@ -31,6 +31,7 @@
 #include "index_internal.h"
 #include "persist_util.h"
 #include "scan_bf16.h"
+#include "scan_i8.h"
 
 using cqs::kMaxK;
 using cqs::kRowsPerBlock;
@@ -136,7 +137,7 @@ cqs::ScanArgs scan_args(const cqs_hip_index* x, const float* d_q, uint32_t b, ui
     return a;
 }
 
-int32_t scan_select(cqs_hip_index* x, const cqs::ScanArgs& a, hipStream_t st, const uint16_t* bf16, const float* bq,
+int32_t scan_select(cqs_hip_index* x, const cqs::ScanArgs& a, hipStream_t st, const ShadowRows* shadow,
                     uint64_t* out_keys, uint32_t* out_counts) {
     const bool timed = !a.gate && x->timing && x->ev_used + 2 <= kMaxTimingEvents;
     if (timed) {
@@ -147,7 +148,8 @@ int32_t scan_select(cqs_hip_index* x, const cqs::ScanArgs& a, hipStream_t st, co
         }
         HIP_TRY(x, hipEventRecord(x->ev[x->ev_used], st));
     }
-    if (bf16) HIP_TRY(x, cqs::launch_scan_bf16(a, bf16, bq, st));
+    if (shadow && shadow->bf16) HIP_TRY(x, cqs::launch_scan_bf16(a, shadow->bf16, shadow->bq, st));
+    else if (shadow) HIP_TRY(x, cqs::launch_scan_i8(a, shadow->i8, shadow->i8_scale, shadow->bq, st));
     else HIP_TRY(x, cqs::launch_scan(a, st));
     if (timed) {
         HIP_TRY(x, hipEventRecord(x->ev[x->ev_used + 1], st));
@@ -174,7 +176,7 @@ int32_t enqueue_search(cqs_hip_index* x, const float* d_q, uint32_t b, uint32_t 
     // The index only where the gather it replaces is long (scan_args): at k = 20 it costs what it saves (same-box A/B, 1M x 768,
     // scan + select per step: k = 20 0.4698 with / 0.4667 ms without; k = 500 0.4783 / 0.4825 - tools/ab_select_aux.sh).
     if (!use_gaux) a.gaux = nullptr;
-    const int32_t rc = scan_select(x, a, st, nullptr, nullptr, d_out_keys, d_out_counts);
+    const int32_t rc = scan_select(x, a, st, nullptr, d_out_keys, d_out_counts);
     if (rc == CQS_HIP_OK) HIP_TRY(x, record_done(x, st));
     return rc;
 }
@@ -723,6 +725,10 @@ static int32_t host_block(cqs_hip_index* x, const cqs_combine_req* const* qs, ui
     }
     x->stat_certified.fetch_add(certified, std::memory_order_relaxed);
     if (redo) x->stat_fallbacks.fetch_add(redo->size(), std::memory_order_relaxed);
+    if (redo && shadow_uses_i8(x, nq, k)) {   // (the decision shadow_pass took: same handle state, same (b, k))
+        x->stat_i8_certified.fetch_add(certified, std::memory_order_relaxed);
+        x->stat_i8_fallbacks.fetch_add(redo->size(), std::memory_order_relaxed);
+    }
     return CQS_HIP_OK;
 }
 

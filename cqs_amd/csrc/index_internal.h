@@ -103,6 +103,7 @@ struct cqs_hip_index {
     // bf16 shadow (index_shadow.hip; null = off).  Its certified / fallback counts outlive it: they live on the handle.
     cqs_idx::Shadow* shadow = nullptr;
     std::atomic<uint64_t> stat_certified{0}, stat_fallbacks{0};
+    std::atomic<uint64_t> stat_i8_certified{0}, stat_i8_fallbacks{0};   // those of them that the int8 copy served
 };
 
 namespace cqs_idx {
@@ -121,8 +122,10 @@ uint32_t max_query_block(const cqs_hip_index* x);
 // Scan + select arguments over the handle's corpus.  elem_bytes (4 f32, 2 the bf16 shadow) sizes `nontemporal`.
 cqs::ScanArgs scan_args(const cqs_hip_index* x, const float* d_q, uint32_t b, uint32_t k, const uint32_t* d_keep,
                         uint32_t mode, float thr, size_t elem_bytes, bool gemv_only, void* dbg, const uint32_t* gate);
-// The scan of `a` on st (the bf16 one over `bf16` when set; timed unless a.gate: the shadow scan was), then the select.
-int32_t scan_select(cqs_hip_index* x, const cqs::ScanArgs& a, hipStream_t st, const uint16_t* bf16, const float* bq,
+// The rows a shadow scan reads: the bf16 copy, or (bf16 null) the int8 codes and their row scales; bq: B_q of the block.
+struct ShadowRows { const uint16_t* bf16; const int8_t* i8; const float* i8_scale; const float* bq; };
+// The scan of `a` on st (over `shadow` when set; timed unless a.gate: the shadow scan was), then the select.
+int32_t scan_select(cqs_hip_index* x, const cqs::ScanArgs& a, hipStream_t st, const ShadowRows* shadow,
                     uint64_t* out_keys, uint32_t* out_counts);
 // Searches share one scratch: order `st` after the last search / record `done` on `st` at the end of one.  Caller holds mu.
 inline hipError_t order_after_last(cqs_hip_index* x, hipStream_t st) {
@@ -150,6 +153,7 @@ int32_t shadow_auto(cqs_hip_index* x);
 int32_t shadow_extend(cqs_hip_index* x, uint64_t n_old);
 void shadow_free(cqs_hip_index* x);
 bool shadow_takes(const cqs_hip_index* x, uint32_t b, uint32_t k, bool gemv_only);
+bool shadow_uses_i8(const cqs_hip_index* x, uint32_t b, uint32_t k);   // of a block shadow_takes: the int8 copy serves it
 int32_t shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k, const uint32_t* d_keep, uint32_t mode,
                     float thr, uint64_t* out_keys, uint32_t* out_counts, hipStream_t st, const uint32_t** device_gate);
 // The last host shadow pass's verdicts, pinned, valid after x->stream's wait (queues their copy when not mappable).

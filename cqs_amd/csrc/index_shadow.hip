@@ -1,4 +1,5 @@
-// index_shadow.hip — host side of the dense index's bf16 shadow (scan_bf16.h), behind one handle pointer.
+// index_shadow.hip — host side of the dense index's shadow: the bf16 copy and the optional int8 copy beside it (scan_bf16.h,
+// scan_i8.h), behind one handle pointer.
 #include <cstdlib>
 #include <cstring>
 #include <new>
@@ -6,6 +7,7 @@
 #include "abi_guard.h"
 #include "index_internal.h"
 #include "scan_bf16.h"
+#include "scan_i8.h"
 
 namespace cqs_idx {
 
@@ -15,6 +17,9 @@ constexpr uint64_t kShadowAutoBytes = 1ull << 30;
 // ... and only if, once it is allocated, the device still has max(this, kShadowFreeFrac of its memory) free
 constexpr uint64_t kShadowFreeMinBytes = 4ull << 30;
 constexpr double kShadowFreeFrac = 0.10;
+// Device counters behind the maxima of the two build passes: [3, 5) certified / fallback queries of the device-API
+// searches, whichever copy served them; [8, 10) those of them the int8 copy served.
+constexpr uint32_t kStatWords = 10, kStatCounts = 3, kStatI8 = 5, kStatI8Counts = 8;
 
 // Built at create / load where it pays, CQS_HIP_SCAN_BF16, or cqs_hip_index_set_bf16_scan: searches of gemv blocks scan it
 // first, rescore the candidates from the f32 rows and fall back to the f32 scan for any query the certificate does not
@@ -22,11 +27,15 @@ constexpr double kShadowFreeFrac = 0.10;
 // handle it is a snapshot of the caller's rows taken at create.
 struct Shadow {
     uint16_t* d_bf16 = nullptr;           // [cap, dim] bf16
-    uint64_t cap = 0;                     // rows the buffer holds (follows cap_rows)
+    uint64_t cap = 0;                     // rows the buffers hold (follows cap_rows)
+    int8_t* d_i8 = nullptr;               // [cap, dim] int8 codes of the optional second copy (null: bf16 alone), which
+    float* d_i8_scale = nullptr;          // [cap] searches of <= kI8MaxQ queries at an i8_k_ok k scan instead of the bf16 one
+    double r8 = 0.0, norm8 = 0.0;         // r / norm of the int8 copy
     double r = 0.0;                       // max over the finite rows of ||x - x~|| + gamma (||x|| + ||x~||)
     double norm = 0.0;                    // max over the finite rows of max(||x||, ||x~||)
-    unsigned long long* d_stats = nullptr;   // [5] the build pass's maxima (f64 bits) and outlier flag, then the
-                                             // device-API searches' certified / fallback counts (certify adds)
+    unsigned long long* d_stats = nullptr;   // [kStatWords] the build pass's maxima (f64 bits) and outlier flag, the
+                                             // device-API searches' certified / fallback counts (certify adds), then the
+                                             // same five words of the int8 copy
     uint64_t* d_akeys = nullptr;          // [kShadowMaxQ, kMaxK] approximate keys of the select
     uint32_t* d_acounts = nullptr;        // [kShadowMaxQ]
     uint64_t* d_ekeys = nullptr;          // [kShadowMaxQ, kMaxK - 1] rescored keys
@@ -37,25 +46,36 @@ struct Shadow {
     uint32_t* h_cert_dev = nullptr;       // its device-visible address (null: not mappable)
 };
 
-// Add what the device-API searches' certify launches counted (d_stats[3, 5)) to *certified / *fallbacks, once every
-// search has completed (quiesce).  Caller holds mu.
-static void shadow_device_counts(cqs_hip_index* x, uint64_t* certified, uint64_t* fallbacks) {
+// Add what the device-API searches' certify launches counted (d_stats + first, two words) to *certified / *fallbacks,
+// once every search has completed (quiesce).  Caller holds mu.
+static void shadow_device_counts(cqs_hip_index* x, uint32_t first, uint64_t* certified, uint64_t* fallbacks) {
     unsigned long long c[2];
     if (!x->shadow || !x->shadow->d_stats || quiesce(x) != hipSuccess) return;
-    hipError_t e = hipMemcpyAsync(c, x->shadow->d_stats + 3, sizeof c, hipMemcpyDeviceToHost, x->stream);
+    hipError_t e = hipMemcpyAsync(c, x->shadow->d_stats + first, sizeof c, hipMemcpyDeviceToHost, x->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(x->stream);
     if (e != hipSuccess) { (void)hipGetLastError(); return; }
     *certified += c[0];
     *fallbacks += c[1];
 }
 
+// Free the int8 copy alone; the bf16 copy then serves every block.  Its device counts stay in d_stats.
+static void i8_free(Shadow* s) {
+    hipFree(s->d_i8); hipFree(s->d_i8_scale);
+    s->d_i8 = nullptr; s->d_i8_scale = nullptr;
+}
+
 void shadow_free(cqs_hip_index* x) {
     Shadow* s = x->shadow;
     if (!s) return;
     uint64_t c = 0, f = 0;   // the counts outlive the shadow
-    shadow_device_counts(x, &c, &f);
+    shadow_device_counts(x, kStatCounts, &c, &f);
     x->stat_certified.fetch_add(c, std::memory_order_relaxed);
     x->stat_fallbacks.fetch_add(f, std::memory_order_relaxed);
+    c = f = 0;
+    shadow_device_counts(x, kStatI8Counts, &c, &f);
+    x->stat_i8_certified.fetch_add(c, std::memory_order_relaxed);
+    x->stat_i8_fallbacks.fetch_add(f, std::memory_order_relaxed);
+    i8_free(s);
     hipFree(s->d_bf16); hipFree(s->d_stats); hipFree(s->d_akeys); hipFree(s->d_acounts); hipFree(s->d_ekeys);
     hipFree(s->d_cert); hipFree(s->d_bq); hipHostFree(s->h_cert);
     delete s;
@@ -81,6 +101,40 @@ static int32_t shadow_convert(cqs_hip_index* x, uint64_t row0, bool* outlier) {
     return CQS_HIP_OK;
 }
 
+// The same for the int8 copy (codes, scales, r8 / norm8); the outlier flag is shadow_convert's.
+static int32_t i8_convert(cqs_hip_index* x, uint64_t row0) {
+    Shadow* s = x->shadow;
+    HIP_TRY(x, cqs::launch_i8_build(x->d_rows, s->d_i8, s->d_i8_scale, row0, x->n - row0, x->dim, cqs::i8_gamma(x->dim),
+                                    s->d_stats + kStatI8, x->stream));
+    unsigned long long st[2];
+    HIP_TRY(x, hipMemcpyAsync(st, s->d_stats + kStatI8, sizeof st, hipMemcpyDeviceToHost, x->stream));
+    HIP_TRY(x, hipStreamSynchronize(x->stream));
+    double r, m;
+    memcpy(&r, &st[0], sizeof r);
+    memcpy(&m, &st[1], sizeof m);
+    s->r8 = r * (1.0 + 0x1p-30);
+    s->norm8 = m * (1.0 + 0x1p-30);
+    return CQS_HIP_OK;
+}
+
+static uint64_t i8_bytes(uint64_t cap, uint32_t dim) { return cap * dim + cap * sizeof(float); }
+
+// Allocate and build the int8 copy over rows [0, n) beside a bf16 copy that is in place.  *built = false: no memory (freed again).
+static int32_t i8_enable(cqs_hip_index* x, bool* built) {
+    Shadow* s = x->shadow;
+    *built = false;
+    if (hipMalloc(&s->d_i8, (size_t)s->cap * x->dim) != hipSuccess ||
+        hipMalloc(&s->d_i8_scale, (size_t)s->cap * sizeof(float)) != hipSuccess) {
+        (void)hipGetLastError();
+        i8_free(s);
+        return CQS_HIP_OK;
+    }
+    const int32_t rc = i8_convert(x, 0);
+    if (rc != CQS_HIP_OK) { i8_free(s); return rc; }
+    *built = true;
+    return CQS_HIP_OK;
+}
+
 // extend() on a handle with the shadow on: grow it with cap_rows, convert rows [n_old, n).  A failure here (no memory,
 // an outlier row) turns the shadow off and leaves the f32 index as extended: the call still succeeds.
 int32_t shadow_extend(cqs_hip_index* x, uint64_t n_old) {
@@ -99,10 +153,29 @@ int32_t shadow_extend(cqs_hip_index* x, uint64_t n_old) {
         if (e != hipSuccess) { hipFree(nd); return fail(x, CQS_HIP_ERR_DEVICE, "extend: shadow copy", e); }
         hipFree(s->d_bf16);
         s->d_bf16 = nd;
+        if (s->d_i8) {   // the int8 copy grows with it, or goes (the bf16 copy then serves every block)
+            int8_t* n8 = nullptr;
+            float* ns = nullptr;
+            if (hipMalloc(&n8, (size_t)x->cap_rows * x->dim) != hipSuccess || hipMalloc(&ns, (size_t)x->cap_rows * sizeof(float)) != hipSuccess) {
+                (void)hipGetLastError();
+                hipFree(n8);
+                i8_free(s);
+                x->last_error = "extend: no device memory to grow the int8 copy of the shadow; int8 copy turned off";
+            } else {
+                e = hipMemcpyAsync(n8, s->d_i8, (size_t)n_old * x->dim, hipMemcpyDeviceToDevice, x->stream);
+                if (e == hipSuccess) e = hipMemcpyAsync(ns, s->d_i8_scale, (size_t)n_old * sizeof(float), hipMemcpyDeviceToDevice, x->stream);
+                if (e == hipSuccess) e = hipStreamSynchronize(x->stream);
+                if (e != hipSuccess) { hipFree(n8); hipFree(ns); return fail(x, CQS_HIP_ERR_DEVICE, "extend: int8 copy", e); }
+                i8_free(s);
+                s->d_i8 = n8;
+                s->d_i8_scale = ns;
+            }
+        }
         s->cap = x->cap_rows;
     }
     bool outlier = false;
-    const int32_t rc = shadow_convert(x, n_old, &outlier);
+    int32_t rc = shadow_convert(x, n_old, &outlier);
+    if (rc == CQS_HIP_OK && s->d_i8 && !outlier) rc = i8_convert(x, n_old);
     if (rc != CQS_HIP_OK) return rc;
     if (outlier) {
         shadow_free(x);
@@ -129,8 +202,8 @@ static int32_t shadow_enable(cqs_hip_index* x, const char* what) {
     if ((e = hipMalloc(&s->d_bf16, (size_t)cap * x->dim * sizeof(uint16_t))) != hipSuccess) return oom(e);
     s->cap = cap;
     unsigned long long* stats = nullptr;   // zeroed before it is the shadow's: shadow_free reads its counts
-    if ((e = hipMalloc(&stats, 5 * sizeof(unsigned long long))) != hipSuccess) return oom(e);
-    if ((e = hipMemsetAsync(stats, 0, 5 * sizeof(unsigned long long), x->stream)) != hipSuccess) { hipFree(stats); return oom(e); }
+    if ((e = hipMalloc(&stats, kStatWords * sizeof(unsigned long long))) != hipSuccess) return oom(e);
+    if ((e = hipMemsetAsync(stats, 0, kStatWords * sizeof(unsigned long long), x->stream)) != hipSuccess) { hipFree(stats); return oom(e); }
     s->d_stats = stats;
     if ((e = hipMalloc(&s->d_akeys, (size_t)cqs::kShadowMaxQ * cqs::kMaxK * sizeof(uint64_t))) != hipSuccess) return oom(e);
     if ((e = hipMalloc(&s->d_acounts, (size_t)cqs::kShadowMaxQ * sizeof(uint32_t))) != hipSuccess) return oom(e);
@@ -149,6 +222,38 @@ static int32_t shadow_enable(cqs_hip_index* x, const char* what) {
         shadow_free(x);
         return fail(x, CQS_HIP_ERR_INVALID, (pre + ": a finite row has a component of magnitude >= 2^64").c_str());
     }
+    return CQS_HIP_OK;
+}
+
+// The int8 copy's policy, once the bf16 copy is built (create / load policy and set_bf16_scan alike).  CQS_HIP_SCAN_I8, read
+// here: unset = where it pays (f32 corpus >= kShadowAutoBytes), 0 = never, 1 = beside every bf16 copy; its own dim rule
+// and the free-memory rule over both copies either way.  Never fails for the copy's sake: the bf16 copy then serves
+// every block and last_error says why.  Returns an error only for a device fault.
+static bool i8_dim_ok(uint32_t dim) { return cqs::i8_dim_ok(dim); }
+static const char* const kI8DimRule = ": dim must be a multiple of 16 and <= 2048";
+static int32_t i8_auto(cqs_hip_index* x) {
+    Shadow* s = x->shadow;
+    if (!s || s->d_i8) return CQS_HIP_OK;
+    const char* env = getenv("CQS_HIP_SCAN_I8");
+    if (env && env[0] == '0') return CQS_HIP_OK;
+    if (!(env && env[0] == '1') && x->n * x->dim * sizeof(float) < kShadowAutoBytes) return CQS_HIP_OK;
+    const std::string pre("int8 copy of the shadow not built (the bf16 copy serves every block)");
+    if (!i8_dim_ok(x->dim)) { x->last_error = pre + kI8DimRule; return CQS_HIP_OK; }
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) {
+        (void)hipGetLastError();
+        x->last_error = pre + ": hipMemGetInfo failed";
+        return CQS_HIP_OK;
+    }
+    const uint64_t need = i8_bytes(s->cap, x->dim);
+    const uint64_t frac = (uint64_t)(kShadowFreeFrac * (double)total_b);
+    const uint64_t reserve = frac > kShadowFreeMinBytes ? frac : kShadowFreeMinBytes;
+    bool built = false;
+    if (free_b >= need && free_b - need >= reserve) {
+        const int32_t rc = i8_enable(x, &built);
+        if (rc != CQS_HIP_OK) return rc;
+    }
+    if (!built) x->last_error = pre + ": the device would keep less than max(4 GiB, 10 %) of its memory free with both copies";
     return CQS_HIP_OK;
 }
 
@@ -183,7 +288,8 @@ int32_t shadow_auto(cqs_hip_index* x) {
         x->last_error = "bf16 shadow not built: the device would keep less than max(4 GiB, 10 %) of its memory free";
         return CQS_HIP_OK;
     }
-    const int32_t rc = shadow_enable(x, "bf16 shadow not built");
+    int32_t rc = shadow_enable(x, "bf16 shadow not built");
+    if (rc == CQS_HIP_OK) rc = i8_auto(x);   // (free memory is read again: the bf16 copy is counted)
     return rc == CQS_HIP_ERR_DEVICE ? rc : CQS_HIP_OK;
 }
 
@@ -191,6 +297,12 @@ int32_t shadow_auto(cqs_hip_index* x) {
 // at a k the shadow can certify (k' < k only at k = kMaxK).
 bool shadow_takes(const cqs_hip_index* x, uint32_t b, uint32_t k, bool gemv_only) {
     return x->shadow && b <= cqs::kShadowMaxQ && (gemv_only || !cqs::use_mfma(b, x->dim)) && cqs::shadow_kprime(k) >= k;
+}
+
+// Which copy serves a block the shadow takes, from (b, k) alone: the int8 one where it exists, for blocks of <= kI8MaxQ
+// queries at a k whose k'_8 fits the select; else the bf16 one.
+bool shadow_uses_i8(const cqs_hip_index* x, uint32_t b, uint32_t k) {
+    return x->shadow && x->shadow->d_i8 && b <= cqs::kI8MaxQ && cqs::i8_k_ok(k);
 }
 
 // The shadow half of a gemv block on `st`: B_q -> shadow scan -> select k' + 1 -> rescore + certify into out_keys /
@@ -202,16 +314,22 @@ int32_t shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k,
     uint32_t* const cert = device_gate || !s->h_cert_dev ? s->d_cert : s->h_cert_dev;
     if (device_gate) *device_gate = cert;
     if (device_gate) HIP_TRY(x, order_after_last(x, st));
-    const uint32_t kp = cqs::shadow_kprime(k);
-    HIP_TRY(x, cqs::launch_shadow_bound(d_q, nb, x->dim, s->r, s->norm, s->d_bq, st));
-    // gemv passes over the bf16 rows (non-uniform tiers, no debug stamps), top k' + 1; the select's (argmax, runner-up)
+    // The same chain over either copy: its bound, its scan, its k'.  A query the int8 copy does not certify goes to the f32
+    // scan like any other, not through the bf16 copy.
+    const bool i8 = shadow_uses_i8(x, nb, k);
+    const uint32_t kp = i8 ? cqs::i8_kprime(k) : cqs::shadow_kprime(k);
+    if (i8) HIP_TRY(x, cqs::launch_i8_bound(d_q, nb, x->dim, s->r8, s->norm8, s->d_bq, st));
+    else HIP_TRY(x, cqs::launch_shadow_bound(d_q, nb, x->dim, s->r, s->norm, s->d_bq, st));
+    // gemv passes over the copy's rows (non-uniform tiers, no debug stamps), top k' + 1; the select's (argmax, runner-up)
     // index from kGauxMinK on whatever CQS_HIP_SELECT_AUX says (that A/B hook is the f32 select's)
-    const cqs::ScanArgs a = scan_args(x, d_q, nb, kp + 1u, d_keep, mode, threshold, sizeof(uint16_t), true, nullptr, nullptr);
-    const int32_t rc = scan_select(x, a, st, s->d_bf16, s->d_bq, s->d_akeys, s->d_acounts);
+    const cqs::ScanArgs a = scan_args(x, d_q, nb, kp + 1u, d_keep, mode, threshold, i8 ? sizeof(int8_t) : sizeof(uint16_t), true, nullptr, nullptr);
+    const ShadowRows rows{i8 ? nullptr : s->d_bf16, i8 ? s->d_i8 : nullptr, s->d_i8_scale, s->d_bq};
+    const int32_t rc = scan_select(x, a, st, &rows, s->d_akeys, s->d_acounts);
     if (rc == CQS_HIP_OK)
         HIP_TRY(x, cqs::launch_rescore_certify(x->d_rows, x->dim, d_q, nb, k, kp, mode, threshold, (uint32_t)x->row_base,
                                                s->d_bq, s->d_akeys, s->d_acounts, s->d_ekeys, out_keys, out_counts, cert,
-                                               device_gate ? s->d_stats + 3 : nullptr, st));
+                                               device_gate ? s->d_stats + kStatCounts : nullptr,
+                                               device_gate && i8 ? s->d_stats + kStatI8Counts : nullptr, st));
     return rc;
 }
 
@@ -240,7 +358,8 @@ int32_t cqs_hip_index_set_bf16_scan(cqs_hip_index* x, int32_t enable) CQS_ABI_TR
     // a borrowed handle gets its shadow at create or not at all: enabling it later would snapshot rows the caller may have
     // changed since (test_invalid_handles); disabling above works on every handle
     if (x->borrow) return fail(x, CQS_HIP_ERR_INVALID, "set_bf16_scan: index borrows its rows (they may change under the bound)");
-    return shadow_enable(x, "set_bf16_scan");
+    const int32_t rc = shadow_enable(x, "set_bf16_scan");
+    return rc == CQS_HIP_OK ? i8_auto(x) : rc;   // (the int8 copy: under CQS_HIP_SCAN_I8's rule, as at create)
 } CQS_ABI_CATCH(x)
 
 void cqs_hip_index_bf16_stats(const cqs_hip_index* x, uint64_t* bytes, uint64_t* certified, uint64_t* fallbacks) CQS_ABI_TRY {
@@ -251,7 +370,22 @@ void cqs_hip_index_bf16_stats(const cqs_hip_index* x, uint64_t* bytes, uint64_t*
         by = m->shadow ? m->shadow->cap * m->dim * sizeof(uint16_t) : 0;
         c = m->stat_certified.load(std::memory_order_relaxed);
         f = m->stat_fallbacks.load(std::memory_order_relaxed);
-        if (m->shadow && hipSetDevice(m->device) == hipSuccess) shadow_device_counts(m, &c, &f);
+        if (m->shadow && hipSetDevice(m->device) == hipSuccess) shadow_device_counts(m, kStatCounts, &c, &f);
+    }
+    if (bytes) *bytes = by;
+    if (certified) *certified = c;
+    if (fallbacks) *fallbacks = f;
+} CQS_ABI_CATCH_VOID
+
+void cqs_hip_index_i8_stats(const cqs_hip_index* x, uint64_t* bytes, uint64_t* certified, uint64_t* fallbacks) CQS_ABI_TRY {
+    uint64_t by = 0, c = 0, f = 0;
+    if (x && !x->sh) {
+        cqs_hip_index* m = const_cast<cqs_hip_index*>(x);
+        std::lock_guard<std::mutex> g(m->mu);
+        by = m->shadow && m->shadow->d_i8 ? i8_bytes(m->shadow->cap, m->dim) : 0;
+        c = m->stat_i8_certified.load(std::memory_order_relaxed);
+        f = m->stat_i8_fallbacks.load(std::memory_order_relaxed);
+        if (m->shadow && hipSetDevice(m->device) == hipSuccess) shadow_device_counts(m, kStatI8Counts, &c, &f);
     }
     if (bytes) *bytes = by;
     if (certified) *certified = c;

@@ -79,12 +79,12 @@ hipError_t launch_scan_bf16(const ScanArgs& a, const uint16_t* shadow, const flo
 // epilogue), take the top k by the select's rank sort, write out_keys [b, k] / out_counts [b] as launch_select does, and
 // cert[b] = 1 when that answer is provably the f32 scan's (else the caller re-runs the query on the f32 scan).
 // akeys [b, k' + 1] / acounts [b]: the select's output; ekeys: [b, k'] scratch; bq: device [b] (launch_shadow_bound).
-// counters: nullable device [2]: += certified, += not certified queries of the block (device-API searches, whose outcome
-// the host never sees).
+// counters, counters2: nullable device [2] each: += certified, += not certified queries of the block (device-API searches,
+// whose outcome the host never sees; the second pair counts what the int8 copy served).
 hipError_t launch_rescore_certify(const float* rows, uint32_t dim, const float* q, uint32_t b, uint32_t k, uint32_t kprime,
                                   uint32_t mode, float thr, uint32_t row_base, const float* bq, const uint64_t* akeys,
                                   const uint32_t* acounts, uint64_t* ekeys, uint64_t* out_keys, uint32_t* out_counts,
-                                  uint32_t* cert, unsigned long long* counters, hipStream_t st);
+                                  uint32_t* cert, unsigned long long* counters, unsigned long long* counters2, hipStream_t st);
 #endif
 
 }  // namespace cqs

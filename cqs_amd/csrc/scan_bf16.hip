@@ -412,6 +412,7 @@ struct CertifyParams {
     uint32_t* cert;            // [b]
     const float* bq;           // [b]
     unsigned long long* counters;   // nullable [2]: certified, not certified
+    unsigned long long* counters2;  // nullable [2]: the same again (the int8 copy's own counts)
 };
 
 __global__ __launch_bounds__(1024) void certify_kernel(const CertifyParams p) {
@@ -448,13 +449,14 @@ __global__ __launch_bounds__(1024) void certify_kernel(const CertifyParams p) {
         }
         p.cert[qi] = ok ? 1u : 0u;
         if (p.counters) atomicAdd(&p.counters[ok ? 0 : 1], 1ull);
+        if (p.counters2) atomicAdd(&p.counters2[ok ? 0 : 1], 1ull);
     }
 }
 
 hipError_t launch_rescore_certify(const float* rows, uint32_t dim, const float* q, uint32_t b, uint32_t k, uint32_t kprime,
                                   uint32_t mode, float thr, uint32_t row_base, const float* bq, const uint64_t* akeys,
                                   const uint32_t* acounts, uint64_t* ekeys, uint64_t* out_keys, uint32_t* out_counts,
-                                  uint32_t* cert, unsigned long long* counters, hipStream_t st) {
+                                  uint32_t* cert, unsigned long long* counters, unsigned long long* counters2, hipStream_t st) {
     if (b == 0) return hipSuccess;
     if (b > kShadowMaxQ || k == 0 || kprime < k || kprime >= kShadowKMax || dim % 8u != 0u || dim > kShadowMaxDim)
         return hipErrorInvalidValue;
@@ -473,7 +475,7 @@ hipError_t launch_rescore_certify(const float* rows, uint32_t dim, const float* 
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    CertifyParams cp{ekeys, akeys, acounts, k, kprime, mode, out_keys, out_counts, cert, bq, counters};
+    CertifyParams cp{ekeys, akeys, acounts, k, kprime, mode, out_keys, out_counts, cert, bq, counters, counters2};
     hipLaunchKernelGGL(certify_kernel, dim3(b), dim3(1024), 0, st, cp);
     return hipGetLastError();
 }

@@ -1,0 +1,337 @@
+// scan_i8.hip — gfx950 kernels of the int8 copy of the dense index's shadow (scan_i8.h).
+//
+//  i8_build_kernel   one wave per f32 row, the row held in registers: scale = max|x_i| / 127, the codes, and the copy's
+//                    index-wide error bound R from the stored codes and scale.
+//  scan_i8_kernel    HBM-streaming dot of every int8 row with 1..4 f32 queries, times the row's scale: a quarter of the
+//                    bytes of scan_gemv_kernel.  scan_bf16_kernel's tasks, score + gmax (+ gaux) layout and one-sided
+//                    epilogue, so the unchanged select, rescore and certify follow it; one wave per task at every size.
+//
+// Wave = 64 lanes.  gfx950 only.
+#include "scan_i8.h"
+#include "launch_util.h"
+#include "scan_device.h"
+
+namespace cqs {
+
+typedef float f4 __attribute__((ext_vector_type(4)));
+typedef float f2 __attribute__((ext_vector_type(2)));
+typedef unsigned u4 __attribute__((ext_vector_type(4)));
+
+// byte i of w as a signed code, converted (exact)
+template <int I>
+__device__ __forceinline__ float code_f32(uint32_t w) { return (float)(int)(int8_t)(w >> (8 * I)); }
+
+// ---- build ------------------------------------------------------------------------------------------------------
+constexpr int kI8BuildVecs = (int)(kShadowMaxDim / 256u);   // f4 per lane that hold a row of up to kShadowMaxDim
+
+__global__ __launch_bounds__(256) void i8_build_kernel(const float* __restrict__ rows, int8_t* __restrict__ codes,
+                                                       float* __restrict__ scales, uint64_t row0, uint64_t n_rows,
+                                                       uint32_t dim, double gamma, unsigned long long* __restrict__ stats) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
+    for (uint64_t r = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); r < n_rows; r += waves) {
+        const float* xp = rows + (row0 + r) * dim;
+        int8_t* op = codes + (row0 + r) * dim;
+        f4 v[kI8BuildVecs];
+        float m = 0.f;
+        bool fin = true;
+#pragma unroll
+        for (int j = 0; j < kI8BuildVecs; ++j) {   // dim % 16 == 0: a lane's four floats never straddle the row end
+            const uint32_t i = (uint32_t)j * 256u + lane * 4u;
+            v[j] = i < dim ? *(const f4*)(xp + i) : (f4)(0.f);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                fin = fin && __builtin_isfinite(v[j][e]);
+                m = fmaxf(m, __builtin_fabsf(v[j][e]));   // (fmaxf drops a NaN operand; `fin` carries it)
+            }
+        }
+        m = wave_max64(m);
+        const bool all_fin = __ballot(!fin) == 0ull;
+        const float scale = all_fin ? m / 127.f : __builtin_nanf("");
+        const bool zero = !(scale > 0.f);   // (and the non-finite rows: their codes are 0, their scale NaN)
+        double d2 = 0.0, n2 = 0.0, t2 = 0.0;
+#pragma unroll
+        for (int j = 0; j < kI8BuildVecs; ++j) {
+            const uint32_t i = (uint32_t)j * 256u + lane * 4u;
+            if (i >= dim) continue;
+            uint32_t w = 0u;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float c = zero ? 0.f : __builtin_rintf(v[j][e] / scale);
+                c = c < -127.f ? -127.f : (c > 127.f ? 127.f : c);
+                w |= ((uint32_t)(int)c & 0xFFu) << (8 * e);
+                const double t = (double)scale * (double)c;   // x~: exact in f64 (24-bit scale, 7-bit code)
+                const double d = (double)v[j][e] - t;
+                d2 += d * d;
+                n2 += (double)v[j][e] * (double)v[j][e];
+                t2 += t * t;
+            }
+            *(uint32_t*)(op + i) = w;
+        }
+#pragma unroll
+        for (int s = 32; s >= 1; s >>= 1) {
+            d2 += __shfl_xor(d2, s, 64);
+            n2 += __shfl_xor(n2, s, 64);
+            t2 += __shfl_xor(t2, s, 64);
+        }
+        if (lane == 0u) {
+            scales[row0 + r] = scale;
+            if (all_fin) {   // rows with a non-finite component score non-finite in both paths: no part in R
+                const double nx = sqrt(n2), nt = sqrt(t2);
+                atomicMax(&stats[0], (unsigned long long)__double_as_longlong(sqrt(d2) + gamma * (nx + nt)));
+                atomicMax(&stats[1], (unsigned long long)__double_as_longlong(nx > nt ? nx : nt));
+                if (m >= 0x1p64f) atomicMax(&stats[2], 1ull);
+            }
+        }
+    }
+}
+
+hipError_t launch_i8_build(const float* rows, int8_t* codes, float* scales, uint64_t row0, uint64_t n_rows, uint32_t dim,
+                           double gamma, unsigned long long* stats, hipStream_t st) {
+    if (n_rows == 0) return hipSuccess;
+    if (!i8_dim_ok(dim)) return hipErrorInvalidValue;
+    const uint64_t blocks = (n_rows + 3u) / 4u;
+    hipLaunchKernelGGL(i8_build_kernel, dim3((uint32_t)(blocks < 8192u ? blocks : 8192u)), dim3(256), 0, st, rows, codes,
+                       scales, row0, n_rows, dim, gamma, stats);
+    return hipGetLastError();
+}
+
+// ---- per-query bound ----------------------------------------------------------------------------------------------
+// shadow_bound_kernel with the int8 copy's bound function (same f64 sum of squares, same 2^-40 slack for its order).
+__global__ __launch_bounds__(64) void i8_bound_kernel(const float* __restrict__ q, uint32_t dim, double r_max,
+                                                      double norm_max, float* __restrict__ bq) {
+    const uint32_t lane = threadIdx.x;
+    const float* qp = q + (size_t)blockIdx.x * dim;
+    double s2 = 0.0;
+    for (uint32_t d = lane; d < dim; d += 64u) s2 += (double)qp[d] * (double)qp[d];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s2 += __shfl_xor(s2, m, 64);
+    if (lane == 0) bq[blockIdx.x] = i8_query_bound(s2, r_max, norm_max, dim);   // (NaN / inf in q: +inf)
+}
+
+hipError_t launch_i8_bound(const float* q, uint32_t b, uint32_t dim, double r_max, double norm_max, float* bq, hipStream_t st) {
+    if (b == 0) return hipSuccess;
+    if (b > kShadowMaxQ) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(i8_bound_kernel, dim3(b), dim3(64), 0, st, q, dim, r_max, norm_max, bq);
+    return hipGetLastError();
+}
+
+// ---- approximate scan -------------------------------------------------------------------------------------------
+struct I8ScanParams {
+    const int8_t* rows;     // [n, dim] codes
+    const float* scales;    // [n]
+    uint32_t n, n_pad, dim;
+    const float* q;
+    float* scores;
+    const uint32_t* keep;
+    uint32_t mode;
+    float thr;
+    uint32_t nq;            // queries present (<= BQ)
+    TaskTiers tiers;
+    uint32_t n_tasks;
+    float* gmax;
+    uint64_t* gaux;         // nullable
+    const float* bq;        // [nq] B_q of each query of the pass (device)
+};
+
+// NCH = ceil(dim / 1024): 1-KiB chunks per row; lane owns components [c*1024 + lane*16, +16) of chunk c (one 16-byte load).
+// A partial last chunk (FULL = false, 768-d: lanes 48..63) reads a clamped in-row address against a zero query fragment, as
+// scan_bf16_kernel does: the same quarter of the lane-loads of a 768-d row.  Per lane and chunk: 16 converts and 8 packed
+// FMAs, (even, odd) accumulators; the row's scale multiplies the reduced sum once, in the epilogue.
+// One task per wave at every size, no persistent grid + work queue: with the queue a search took 0.26 ms against 0.158 at
+// 1M rows and 2.11 against 1.24 at 10M - both about 14 ns per dequeued task, whatever the blocks per CU,
+// which points at the one returning atomic per task on an address every XCD shares; this scan needs a task every 8 ns.
+template <int NCH, int BQ, int RI, bool NT, bool FULL>
+__global__ __launch_bounds__(256) void scan_i8_kernel(const I8ScanParams p) {
+    constexpr int NV = RI * BQ;
+    constexpr int LPV = 64 / NV;
+    const int lane = threadIdx.x & 63;
+    const uint32_t n = p.n, dim = p.dim;
+
+    uint32_t coff[NCH];
+    f4 qv[BQ][NCH][4];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        const uint32_t idx = (uint32_t)c * 1024u + (uint32_t)lane * 16u;
+        const bool in = FULL || idx < dim;
+        coff[c] = in ? idx : dim - 16u;
+#pragma unroll
+        for (int b = 0; b < BQ; ++b) {
+            const float* qp = p.q + (size_t)((uint32_t)b < p.nq ? b : 0) * dim + coff[c];
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                const f4 t = *(const f4*)(qp + 4 * w);
+                qv[b][c][w] = in ? t : (f4)(0.f);
+            }
+        }
+    }
+
+    const uint32_t last = n - 1u;
+    const uint32_t nwords = (n + 31u) / 32u;
+    const uint32_t n_tasks = p.n_tasks;
+    const uint32_t wpb = blockDim.x >> 6;
+    const uint32_t cur = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * wpb + (threadIdx.x >> 6)));
+    if (cur >= n_tasks) return;
+
+    const char* const rows_b = (const char*)p.rows;
+    auto load_rows = [&](uint32_t base, int j, u4 (&x)[RI][NCH]) {
+#pragma unroll
+        for (int r = 0; r < RI; ++r) {
+            uint32_t row = base + (uint32_t)(RI * j + r);
+            row = row > last ? last : row;
+            const char* rp = rows_b + (uint64_t)row * dim;
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) {
+                const u4* src = (const u4*)(rp + coff[c]);
+                if (NT) x[r][c] = __builtin_nontemporal_load(src);
+                else x[r][c] = *src;
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+    };
+    auto reduce_rows = [&](int j, u4 (&x)[RI][NCH], float (&sc)[BQ]) {
+        f2 acc2[NV];
+#pragma unroll
+        for (int i = 0; i < NV; ++i) acc2[i] = (f2)(0.f);
+#pragma unroll
+        for (int r = 0; r < RI; ++r)
+#pragma unroll
+            for (int c = 0; c < NCH; ++c)
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    const uint32_t u = x[r][c][w];
+                    const f2 lo = {code_f32<0>(u), code_f32<1>(u)}, hi = {code_f32<2>(u), code_f32<3>(u)};
+#pragma unroll
+                    for (int b = 0; b < BQ; ++b) {
+                        const f4 qq = qv[b][c][w];
+                        f2 a = acc2[b * RI + r];
+                        a = __builtin_elementwise_fma(lo, __builtin_shufflevector(qq, qq, 0, 1), a);
+                        a = __builtin_elementwise_fma(hi, __builtin_shufflevector(qq, qq, 2, 3), a);
+                        acc2[b * RI + r] = a;
+                    }
+                }
+        float acc[NV];
+#pragma unroll
+        for (int i = 0; i < NV; ++i) acc[i] = acc2[i].x + acc2[i].y;
+        treduce<NV>(acc, lane);
+#pragma unroll
+        for (int b = 0; b < BQ; ++b) {
+            const float t = __shfl(acc[0], (b * RI + (lane % RI)) * LPV, 64);
+            if (lane / RI == j) sc[b] = t;
+        }
+    };
+    // scan_bf16_kernel's epilogue after the scale: the f32 drop rules made one-sided with this copy's B_q.  A row with a
+    // non-finite component has a NaN scale, so its score is dropped here as the f32 scan drops it.
+    auto epilogue = [&](uint32_t cur, uint32_t base, uint32_t trows, uint64_t mask, float scale, float (&sc)[BQ]) {
+        const uint32_t row = base + (uint32_t)lane;
+        const bool live = (uint32_t)lane < trows && ((mask >> lane) & 1ull);
+#pragma unroll
+        for (int b = 0; b < BQ; ++b) {
+            float s = sc[b] * scale;
+            if (!live || !(__builtin_fabsf(s) <= 3.4028234664e38f)) s = -INFINITY;
+            else if (p.mode == 1u && (uint32_t)b < p.nq) {
+                float t = s + p.bq[b];
+                t = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);
+                if (!(t >= p.thr)) s = -INFINITY;
+            }
+            if ((uint32_t)b >= p.nq) continue;
+            if ((uint32_t)lane < trows && row < p.n_pad) p.scores[(size_t)b * p.n_pad + row] = s;
+            const float gm = wave_max64(s);
+            if (lane == 0) p.gmax[(size_t)b * n_tasks + cur] = gm;
+            if (p.gaux) {
+                const uint32_t arg = (uint32_t)__builtin_ctzll(__ballot(s == gm));
+                const float sec = wave_max64(((uint32_t)lane == arg) ? -INFINITY : s);
+                if (lane == 0) p.gaux[(size_t)b * n_tasks + cur] = ((uint64_t)arg << 32) | (uint64_t)__float_as_uint(sec);
+            }
+        }
+    };
+    auto task_mask = [&](uint32_t base, uint32_t trows) -> uint64_t {
+        const uint64_t all = trows == 64u ? ~0ull : ((1ull << trows) - 1ull);
+        uint64_t mask = all;
+        if (base + trows > n) mask = (base >= n) ? 0ull : (all >> (trows - (n - base)));
+        if (p.keep) {
+            const uint32_t w = base / 32u;
+            const uint32_t w0 = (w < nwords) ? p.keep[w] : 0u;
+            const uint32_t w1 = (w + 1u < nwords) ? p.keep[w + 1u] : 0u;
+            mask &= (((uint64_t)w1 << 32) | (uint64_t)w0) >> (base & 31u);
+        }
+        const uint32_t mlo = __builtin_amdgcn_readfirstlane((uint32_t)mask);
+        const uint32_t mhi = __builtin_amdgcn_readfirstlane((uint32_t)(mask >> 32));
+        return ((uint64_t)mhi << 32) | mlo;
+    };
+
+    u4 x[RI][NCH];
+    uint32_t trows;
+    const uint32_t base = p.tiers.locate(cur, trows);
+    const uint64_t mask = task_mask(base, trows);
+    const uint32_t srow = base + (uint32_t)lane;
+    const float scale = p.scales[srow > last ? last : srow];
+    float sc[BQ];
+#pragma unroll
+    for (int b = 0; b < BQ; ++b) sc[b] = -INFINITY;
+    const int nb = (int)(trows / (uint32_t)RI);
+    for (int j = 0; j < nb; ++j) {
+        const uint32_t m = (uint32_t)(mask >> (RI * j)) & ((1u << RI) - 1u);
+        if (m == 0u) continue;   // all RI rows filtered out / past the end: skip their reads
+        load_rows(base, j, x);
+        reduce_rows(j, x, sc);
+    }
+    epilogue(cur, base, trows, mask, scale, sc);
+}
+
+constexpr int kI8RowsPerBatch = 16;   // of the single-query pass (divides the 16-row task); 8 measured 3 % slower
+
+template <int NCH, int BQ, int RI>
+static hipError_t launch_i8(const ScanArgs& a, const int8_t* codes, const float* scales, const float* bq, uint32_t q0,
+                            uint32_t nq, hipStream_t st) {
+    I8ScanParams p;
+    p.rows = codes; p.scales = scales; p.n = a.n; p.n_pad = a.n_pad; p.dim = a.dim;
+    p.q = a.q + (size_t)q0 * a.dim;
+    p.scores = a.scores + (size_t)q0 * a.n_pad;
+    p.keep = a.keep; p.mode = a.mode; p.thr = a.threshold;
+    p.nq = nq;
+    p.tiers = a.tiers;
+    p.n_tasks = a.tiers.total();
+    p.gmax = a.gmax + (size_t)q0 * p.n_tasks;
+    p.gaux = a.gaux ? a.gaux + (size_t)q0 * p.n_tasks : nullptr;
+    p.bq = bq + q0;
+    const uint32_t wpb = 4u;
+    const dim3 grid((p.n_tasks + wpb - 1u) / wpb), block(64u * wpb);
+    const bool full = (a.dim == (uint32_t)NCH * 1024u);
+    if (a.nontemporal) {
+        if (full) hipLaunchKernelGGL((scan_i8_kernel<NCH, BQ, RI, true, true>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((scan_i8_kernel<NCH, BQ, RI, true, false>), grid, block, 0, st, p);
+    } else {
+        if (full) hipLaunchKernelGGL((scan_i8_kernel<NCH, BQ, RI, false, true>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((scan_i8_kernel<NCH, BQ, RI, false, false>), grid, block, 0, st, p);
+    }
+    return hipGetLastError();
+}
+
+template <int NCH>
+static hipError_t launch_i8_groups(const ScanArgs& a, const int8_t* codes, const float* scales, const float* bq, hipStream_t st) {
+    uint32_t done = 0;
+    while (done < a.b) {
+        const uint32_t left = a.b - done;
+        hipError_t e;
+        uint32_t g;
+        if (left >= 3) { g = left < 4u ? left : 4u; e = launch_i8<NCH, 4, 4>(a, codes, scales, bq, done, g, st); }   // (3 ride the 4-query pass)
+        else if (left >= 2) { g = 2; e = launch_i8<NCH, 2, 8>(a, codes, scales, bq, done, g, st); }
+        else { g = 1; e = launch_i8<NCH, 1, kI8RowsPerBatch>(a, codes, scales, bq, done, g, st); }
+        if (e != hipSuccess) return e;
+        done += g;
+    }
+    return hipSuccess;
+}
+
+hipError_t launch_scan_i8(const ScanArgs& a, const int8_t* codes, const float* scales, const float* bq, hipStream_t st) {
+    if (a.b == 0 || a.n == 0) return hipSuccess;
+    if (a.b > kShadowMaxQ || !i8_dim_ok(a.dim)) return hipErrorInvalidValue;
+    switch ((a.dim + 1023u) / 1024u) {
+        case 1: return launch_i8_groups<1>(a, codes, scales, bq, st);
+        case 2: return launch_i8_groups<2>(a, codes, scales, bq, st);
+        default: return hipErrorInvalidValue;
+    }
+}
+
+}  // namespace cqs

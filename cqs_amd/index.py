@@ -467,6 +467,12 @@ class HipIndex(VectorIndex):
         self._lib.cqs_hip_index_bf16_stats(self._h, C.byref(b), C.byref(c), C.byref(f))
         return int(b.value), int(c.value), int(f.value)
 
+    def i8_stats(self) -> Tuple[int, int, int]:
+        """(bytes of the shadow's int8 copy, 0 = not built; of bf16_stats' two counts, the queries whose block scanned it)."""
+        b, c, f = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._lib.cqs_hip_index_i8_stats(self._h, C.byref(b), C.byref(c), C.byref(f))
+        return int(b.value), int(c.value), int(f.value)
+
     def set_timing(self, on: bool) -> None:
         self._lib.cqs_hip_index_set_timing(self._h, 1 if on else 0)
 

@@ -253,11 +253,21 @@ void cqs_hip_index_combine_stats(const cqs_hip_index* idx, uint64_t* passes, uin
  * blocks) and `cqs_hip_index_search_device` blocks of b <= 8 (and of <= 32 queries where dim % 32 != 0);
  * matrix-core blocks, `cqs_hip_index_neighbors` and sharded handles are unchanged.  `extend` converts the
  * new rows (an outlier row there turns the shadow off); save does not persist it (load rebuilds it under
- * the rules above). */
+ * the rules above).
+ * The int8 copy.  Beside the bf16 copy the handle may keep a second, int8 copy of the corpus (n x dim B plus 4 B per row:
+ * with both, 0.75 B per f32 byte), which blocks of <= 4 queries at k <= 87 scan instead of the bf16 one: a quarter of the
+ * f32 bytes, the same rescore, proof and f32 fallback, the same answers.  Every other block the shadow takes scans the bf16
+ * copy.  It is built wherever a bf16 copy is built (create / create_device / load, and enable != 0 here) when
+ * CQS_HIP_SCAN_I8 allows: unset = f32 corpus of at least 1 GiB, =0 never, =1 beside every bf16 copy; dim % 16 == 0, and
+ * the free-memory rule holds with both copies.  Where only one copy fits, the bf16 one is kept (it serves every k) and
+ * last_error says so.  enable == 0 frees both copies; extend, save and load treat it as they treat the bf16 copy. */
 int32_t cqs_hip_index_set_bf16_scan(cqs_hip_index* idx, int32_t enable);
 /* bytes of the shadow (0 = off); queries answered by the certified path; queries that fell back to the f32
  * scan (host and device-API searches; waits for the device-API searches in flight).  Any pointer may be NULL. */
 void cqs_hip_index_bf16_stats(const cqs_hip_index* idx, uint64_t* bytes, uint64_t* certified, uint64_t* fallbacks);
+/* The int8 copy's share: its bytes (codes and row scales; 0 = not built), and of the two counts above the queries whose
+ * block scanned the int8 copy (bf16_stats counts every query once, whichever copy served it).  Any pointer may be NULL. */
+void cqs_hip_index_i8_stats(const cqs_hip_index* idx, uint64_t* bytes, uint64_t* certified, uint64_t* fallbacks);
 
 /* ---- profiling aid ---------------------------------------------------------
  * With timing enabled every search brackets its dominant scan kernel launch(es)

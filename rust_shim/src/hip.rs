@@ -81,6 +81,7 @@ extern "C" {
     fn cqs_hip_index_last_error(idx: *const CqsHipIndex, buf: *mut c_char, cap: usize) -> usize;
     fn cqs_hip_index_set_bf16_scan(idx: *mut CqsHipIndex, enable: i32) -> i32;
     fn cqs_hip_index_bf16_stats(idx: *const CqsHipIndex, bytes: *mut u64, certified: *mut u64, fallbacks: *mut u64);
+    fn cqs_hip_index_i8_stats(idx: *const CqsHipIndex, bytes: *mut u64, certified: *mut u64, fallbacks: *mut u64);
     fn cqs_hip_index_search(
         idx: *mut CqsHipIndex,
         queries: *const f32,
@@ -172,7 +173,9 @@ impl HipIndex {
         } else {
             let mut bytes = 0u64;
             unsafe { cqs_hip_index_bf16_stats(self.handle, &mut bytes, std::ptr::null_mut(), std::ptr::null_mut()) };
-            tracing::info!(bytes, "HIP bf16 shadow scan enabled");
+            let mut i8_bytes: u64 = 0;
+            unsafe { cqs_hip_index_i8_stats(self.handle, &mut i8_bytes, std::ptr::null_mut(), std::ptr::null_mut()) };
+            tracing::info!(bytes, i8_bytes, "HIP bf16 shadow scan enabled");
         }
     }
 
