@@ -419,4 +419,110 @@ int32_t cqs_hip_debug_shadow_bound(cqs_hip_index* x, const float* queries, uint3
     return CQS_HIP_OK;
 } CQS_ABI_CATCH(x)
 
+// Test hook: the same contract for the int8 copy's bound (launch_i8_bound against i8_query_bound with r8 / norm8).
+// INVALID without an int8 copy or for b > kShadowMaxQ.
+int32_t cqs_hip_debug_shadow_bound_i8(cqs_hip_index* x, const float* queries, uint32_t b, float* out_device, float* out_host) CQS_ABI_TRY {
+    if (!x || x->sh || !queries || !out_device || !out_host || b == 0) return CQS_HIP_ERR_INVALID;
+    std::lock_guard<std::mutex> g(x->mu);
+    const Shadow* s = x->shadow;
+    if (!s || !s->d_i8 || b > cqs::kShadowMaxQ) return CQS_HIP_ERR_INVALID;
+    HIP_TRY(x, hipSetDevice(x->device));
+    HIP_TRY(x, quiesce(x));   // d_bq belongs to the searches
+    float* d_q = nullptr;
+    HIP_TRY(x, hipMalloc(&d_q, (size_t)b * x->dim * sizeof(float)));
+    hipError_t e = hipMemcpyAsync(d_q, queries, (size_t)b * x->dim * sizeof(float), hipMemcpyHostToDevice, x->stream);
+    if (e == hipSuccess) e = cqs::launch_i8_bound(d_q, b, x->dim, s->r8, s->norm8, s->d_bq, x->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_device, s->d_bq, (size_t)b * sizeof(float), hipMemcpyDeviceToHost, x->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(x->stream);
+    hipFree(d_q);
+    HIP_TRY(x, e);
+    for (uint32_t i = 0; i < b; ++i) {
+        const float* q = queries + (size_t)i * x->dim;
+        double s2 = 0.0;
+        for (uint32_t d = 0; d < x->dim; ++d) s2 += (double)q[d] * (double)q[d];
+        out_host[i] = cqs::i8_query_bound(s2, s->r8, s->norm8, x->dim);
+    }
+    return CQS_HIP_OK;
+} CQS_ABI_CATCH(x)
+
+// Test hook: out[0..4) = r, norm, r8, norm8 as the handle holds them (after shadow_convert's factor; r8 = norm8 = 0 without an
+// int8 copy).  INVALID without a shadow.
+int32_t cqs_hip_debug_shadow_stats(cqs_hip_index* x, double* out) CQS_ABI_TRY {
+    if (!x || x->sh || !out) return CQS_HIP_ERR_INVALID;
+    std::lock_guard<std::mutex> g(x->mu);
+    const Shadow* s = x->shadow;
+    if (!s) return CQS_HIP_ERR_INVALID;
+    out[0] = s->r; out[1] = s->norm;
+    out[2] = s->d_i8 ? s->r8 : 0.0; out[3] = s->d_i8 ? s->norm8 : 0.0;
+    return CQS_HIP_OK;
+} CQS_ABI_CATCH(x)
+
+// Test hook: the stored copy of rows [row0, row0 + rows).  copy 1: out = [rows, dim] bf16 words (out_scales ignored);
+// copy 2: out = [rows, dim] int8 codes, out_scales = [rows] f32.  INVALID without that copy or past the index's rows.
+int32_t cqs_hip_debug_shadow_rows(cqs_hip_index* x, uint32_t copy, uint64_t row0, uint64_t rows, void* out, float* out_scales) CQS_ABI_TRY {
+    if (!x || x->sh || !out || (copy != 1u && copy != 2u) || (copy == 2u && !out_scales)) return CQS_HIP_ERR_INVALID;
+    std::lock_guard<std::mutex> g(x->mu);
+    const Shadow* s = x->shadow;
+    if (!s || (copy == 2u && !s->d_i8) || row0 > x->n || rows > x->n - row0) return CQS_HIP_ERR_INVALID;
+    if (rows == 0) return CQS_HIP_OK;
+    HIP_TRY(x, hipSetDevice(x->device));
+    HIP_TRY(x, quiesce(x));
+    if (copy == 1u) {
+        HIP_TRY(x, hipMemcpyAsync(out, s->d_bf16 + row0 * x->dim, (size_t)rows * x->dim * sizeof(uint16_t), hipMemcpyDeviceToHost, x->stream));
+    } else {
+        HIP_TRY(x, hipMemcpyAsync(out, s->d_i8 + row0 * x->dim, (size_t)rows * x->dim, hipMemcpyDeviceToHost, x->stream));
+        HIP_TRY(x, hipMemcpyAsync(out_scales, s->d_i8_scale + row0, (size_t)rows * sizeof(float), hipMemcpyDeviceToHost, x->stream));
+    }
+    HIP_TRY(x, hipStreamSynchronize(x->stream));
+    return CQS_HIP_OK;
+} CQS_ABI_CATCH(x)
+
+// Test hook: the score rows of one scan, before any select.  `b` host queries [b, dim] (b <= kMaxGemvQ; <= kI8MaxQ for the
+// int8 copy), the search's k, an optional host keep-bitset, mode and threshold: the bound kernel of the copy a search of
+// (b, k) would take (shadow_uses_i8), then exactly the scan launch of shadow_pass (copy 1 = bf16, 2 = int8: scan_args at
+// k' + 1) or of enqueue_search (copy 0 = f32), on the handle's stream.  out_scores [b, n] (dropped rows are -inf), out_bq [b]
+// (for copy 1 / 2 that copy's own B_q).  The work-queue heads are zeroed again, as the select leaves them.  INVALID without a
+// shadow, for a copy the handle does not have, or for a (b, k) that copy does not serve.
+int32_t cqs_hip_debug_shadow_scores(cqs_hip_index* x, uint32_t copy, const float* queries, uint32_t b, uint32_t k,
+                                    const uint32_t* keep_bitset, uint32_t mode, float threshold, float* out_scores,
+                                    float* out_bq) CQS_ABI_TRY {
+    if (!x || x->sh || !queries || !out_scores || !out_bq || b == 0 || copy > 2u || mode > CQS_HIP_MODE_PIPELINE) return CQS_HIP_ERR_INVALID;
+    if (k == 0 || k > cqs::kMaxK) return CQS_HIP_ERR_INVALID;
+    std::lock_guard<std::mutex> g(x->mu);
+    if (x->poisoned.load(std::memory_order_acquire)) return CQS_HIP_ERR_POISONED;
+    const Shadow* s = x->shadow;
+    if (!s || x->n == 0 || b > cqs::kMaxGemvQ || !shadow_takes(x, b, k, /*gemv_only=*/false)) return CQS_HIP_ERR_INVALID;
+    if (copy == 2u && !(s->d_i8 && b <= cqs::kI8MaxQ && cqs::i8_k_ok(k))) return CQS_HIP_ERR_INVALID;
+    HIP_TRY(x, hipSetDevice(x->device));
+    HIP_TRY(x, quiesce(x));   // the scratch belongs to the searches
+    const bool i8 = copy == 2u || (copy == 0u && shadow_uses_i8(x, b, k));
+    const uint32_t kp = copy == 2u ? cqs::i8_kprime(k) : cqs::shadow_kprime(k);
+    const uint32_t k_scan = copy == 0u ? k : kp + 1u;
+    int32_t rc = ensure_scratch(x, b, k_scan);
+    if (rc != CQS_HIP_OK) return rc;
+    const uint32_t* d_keep = nullptr;
+    if (keep_bitset) {
+        if ((rc = stage_keep(x, keep_bitset, (x->n + 31) / 32)) != CQS_HIP_OK) return rc;
+        d_keep = x->d_keep;
+    }
+    hipStream_t st = x->stream;
+    HIP_TRY(x, hipMemcpyAsync(x->d_q, queries, (size_t)b * x->dim * sizeof(float), hipMemcpyHostToDevice, st));
+    if (i8) HIP_TRY(x, cqs::launch_i8_bound(x->d_q, b, x->dim, s->r8, s->norm8, s->d_bq, st));
+    else HIP_TRY(x, cqs::launch_shadow_bound(x->d_q, b, x->dim, s->r, s->norm, s->d_bq, st));
+    if (copy == 0u) {
+        const cqs::ScanArgs a = scan_args(x, x->d_q, b, k, d_keep, mode, threshold, sizeof(float), false, x->d_dbg, nullptr);
+        HIP_TRY(x, cqs::launch_scan(a, st));
+    } else {
+        const cqs::ScanArgs a = scan_args(x, x->d_q, b, k_scan, d_keep, mode, threshold, i8 ? sizeof(int8_t) : sizeof(uint16_t), true, nullptr, nullptr);
+        if (i8) HIP_TRY(x, cqs::launch_scan_i8(a, s->d_i8, s->d_i8_scale, s->d_bq, st));
+        else HIP_TRY(x, cqs::launch_scan_bf16(a, s->d_bf16, s->d_bq, st));
+    }
+    HIP_TRY(x, hipMemsetAsync(x->d_work, 0, cqs::kWorkWords * sizeof(uint32_t), st));   // (what the select does after a scan)
+    const size_t row_b = (size_t)x->n * sizeof(float);
+    HIP_TRY(x, hipMemcpy2DAsync(out_scores, row_b, x->d_scores, (size_t)pad_rows(x->n) * sizeof(float), row_b, b, hipMemcpyDeviceToHost, st));
+    HIP_TRY(x, hipMemcpyAsync(out_bq, s->d_bq, (size_t)b * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIP_TRY(x, hipStreamSynchronize(st));
+    return CQS_HIP_OK;
+} CQS_ABI_CATCH(x)
+
 }  // extern "C"

@@ -8,6 +8,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from shadow_emul import bf16_round, f32_dot_chain
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "cqs_amd", "csrc", "scan_bf16.h")
 
@@ -65,19 +67,6 @@ def test_round_up_is_the_smallest_f32_above(driver):
         assert float(f32) == f and f >= v
         assert float(np.nextafter(f32, np.float32(0))) < v or f == v
     assert driver("roundup", "1e39") == ["inf"]
-
-
-def bf16_round(x):
-    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
-    return (((u + 0x7FFF + ((u >> 16) & 1)) >> 16) << 16).astype(np.uint32).view(np.float32)
-
-
-def f32_dot_chain(x, q):
-    """Sequential f32 FMA-free dot (one rounding per product and per add): the worst order the bound must cover."""
-    acc = np.zeros(x.shape[0], np.float32)
-    for i in range(x.shape[1]):
-        acc = (acc + (x[:, i] * q[i]).astype(np.float32)).astype(np.float32)
-    return acc
 
 
 @pytest.mark.parametrize("dim,scale", [(64, 1.0), (768, 1.0), (768, 37.0), (2048, 0.01)])

@@ -9,6 +9,8 @@ import subprocess
 import numpy as np
 import pytest
 
+from shadow_emul import adversarial_rows, build_i8, f32_dot_chain, r_and_norm, scan_i8
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "cqs_amd", "csrc")
 
@@ -50,81 +52,7 @@ def bound(driver, q, r_max, n_max, dim, which="bound"):
     return float.fromhex(driver(which, repr(q2), repr(float(r_max)), repr(float(n_max)), dim)[0])
 
 
-# ---- the kernels' arithmetic in numpy ------------------------------------------------------------------------------------
-def build_i8(x):
-    """i8_build_kernel: scale = max|x_i| / 127 in f32 (0 when that underflows), codes = clamp(rint(x_i / scale)) in f32."""
-    x = np.ascontiguousarray(x, dtype=np.float32)
-    scale = (np.abs(x).max(axis=1) / np.float32(127)).astype(np.float32)
-    with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
-        c = np.rint((x / scale[:, None]).astype(np.float32))
-    c = np.where(scale[:, None] > 0, c, np.float32(0))
-    return np.clip(c, -127, 127).astype(np.float32), scale
-
-
-def fma32(a, b, acc):
-    """f32 fma(a, b, acc) for a an int8 code: the product is exact in f64 (7 x 24 bits), the sum rounds once to f64 (53 bits)
-    and once more to f32 - the double rounding moves the result by at most 2^-29 of an f32 ulp, far inside the bound."""
-    return (a.astype(np.float64) * b.astype(np.float64) + acc.astype(np.float64)).astype(np.float32)
-
-
-def scan_i8(codes, scale, q):
-    """scan_i8_kernel for one query: lane L owns components [c*1024 + 16 L, +16) of chunk c; per 4-byte word two packed FMAs
-    into an (even, odd) accumulator pair, chunk after chunk; even + odd; xor butterfly 32 -> 1; times the row's scale."""
-    n, dim = codes.shape
-    nch = (dim + 1023) // 1024
-    pad = nch * 1024
-    cp = np.zeros((n, pad), np.float32); cp[:, :dim] = codes
-    qp = np.zeros(pad, np.float32); qp[:dim] = q                      # a partial chunk meets a zero query fragment
-    cp = cp.reshape(n, nch, 64, 4, 4)                                 # [row, chunk, lane, word, byte]
-    qp = qp.reshape(nch, 64, 4, 4)
-    ax = np.zeros((n, 64), np.float32); ay = np.zeros((n, 64), np.float32)
-    for c in range(nch):
-        for w in range(4):
-            ax = fma32(cp[:, c, :, w, 0], qp[c, :, w, 0][None], ax); ay = fma32(cp[:, c, :, w, 1], qp[c, :, w, 1][None], ay)
-            ax = fma32(cp[:, c, :, w, 2], qp[c, :, w, 2][None], ax); ay = fma32(cp[:, c, :, w, 3], qp[c, :, w, 3][None], ay)
-    v = (ax + ay).astype(np.float32)
-    lanes = np.arange(64)
-    for m in (32, 16, 8, 4, 2, 1):
-        v = (v + v[:, lanes ^ m]).astype(np.float32)
-    return (v[:, 0] * scale).astype(np.float32)
-
-
-def f32_dot_chain(x, q):
-    """Sequential f32 dot (one rounding per product and per add): the worst order the bound must cover for the f32 scan."""
-    acc = np.zeros(x.shape[0], np.float32)
-    for i in range(x.shape[1]):
-        acc = (acc + (x[:, i] * q[i]).astype(np.float32)).astype(np.float32)
-    return acc
-
-
-def r_and_norm(driver, x, codes, scale, dim):
-    """What the build folds into stats[0..1], from the stored codes and scale, in f64, with shadow_convert's 2^-30 slack."""
-    gam = float(driver("gamma", dim)[0])
-    xd = x.astype(np.float64)
-    td = codes.astype(np.float64) * scale.astype(np.float64)[:, None]
-    nx, nt = np.linalg.norm(xd, axis=1), np.linalg.norm(td, axis=1)
-    r = np.linalg.norm(xd - td, axis=1) + gam * (nx + nt)
-    return float(r.max()) * (1 + 2.0 ** -30), float(max(nx.max(), nt.max())) * (1 + 2.0 ** -30)
-
-
-def adversarial_rows(rng, dim):
-    x = (rng.standard_normal((64, dim)) * rng.uniform(0.1, 3.0, (64, 1))).astype(np.float32)
-    x[:8] = np.abs(x[:8])                                                   # signs aligned with an all-positive query
-    half = (rng.integers(-126, 126, dim) + 0.5).astype(np.float32)          # every component at a rounding midpoint
-    half[0] = 127.0
-    x[8] = half * np.float32(1.0 / 127)
-    x[9] = half * np.float32(3.0)
-    x[10] = 0.0; x[10, dim // 2] = 5.0                                      # one dominant component, the rest zero
-    x[11] = rng.standard_normal(dim).astype(np.float32) * np.float32(1e-3); x[11, 1] = 40.0   # ... the rest below half a step
-    x[12] = 0.0                                                             # a zero row (scale 0, codes 0)
-    x[13] = np.float32(1e-44)                                               # denormal: max / 127 underflows to 0, codes 0
-    x[19] = np.float32(1e-42); x[19, 3] = np.float32(3e-42)                 # denormal row with a denormal, nonzero scale
-    x[14] = x[14] * np.float32(1e-30)                                       # tiny scale
-    x[15] = x[15] * np.float32(1e-36)                                       # products with q underflow
-    x[16] = x[16] * np.float32(1e17)                                        # huge scale
-    x[17] = (x[17] / np.abs(x[17]).max()) * np.float32(2.0 ** 64 * (1 - 2.0 ** -20))   # just under the 2^64 refusal
-    x[18] = -x[17]
-    return x
+# the kernels' arithmetic in numpy: shadow_emul.py (shared with the device test of the same premises)
 
 
 @pytest.mark.parametrize("dim", [16, 128, 768, 1040, 2048])
