@@ -41,7 +41,10 @@ struct Shadow {
     uint64_t* d_ekeys = nullptr;          // [kShadowMaxQ, kMaxK - 1] rescored keys
     uint32_t* d_cert = nullptr;           // [kShadowMaxQ] certified flags (device-API searches: the f32 gate; host searches:
                                           // when h_cert is not mappable)
-    float* d_bq = nullptr;                // [kShadowMaxQ] B_q of each query of the block (launch_shadow_bound)
+    float* d_bq = nullptr;                // [kShadowMaxQ] B_q of each query of the block (the fused tail kernel; PIPELINE
+                                          // searches: launch_shadow_bound / launch_i8_bound, ahead of the scan that reads it)
+    uint32_t* d_tickets = nullptr;        // [kShadowMaxQ] arrival counts of the tail kernel's workgroups: zeroed here once,
+                                          // put back to zero by every launch (launch_rescore_certify)
     uint32_t* h_cert = nullptr;           // pinned [kShadowMaxQ]
     uint32_t* h_cert_dev = nullptr;       // its device-visible address (null: not mappable)
 };
@@ -77,7 +80,7 @@ void shadow_free(cqs_hip_index* x) {
     x->stat_i8_fallbacks.fetch_add(f, std::memory_order_relaxed);
     i8_free(s);
     hipFree(s->d_bf16); hipFree(s->d_stats); hipFree(s->d_akeys); hipFree(s->d_acounts); hipFree(s->d_ekeys);
-    hipFree(s->d_cert); hipFree(s->d_bq); hipHostFree(s->h_cert);
+    hipFree(s->d_cert); hipFree(s->d_bq); hipFree(s->d_tickets); hipHostFree(s->h_cert);
     delete s;
     x->shadow = nullptr;
 }
@@ -210,6 +213,8 @@ static int32_t shadow_enable(cqs_hip_index* x, const char* what) {
     if ((e = hipMalloc(&s->d_ekeys, (size_t)cqs::kShadowMaxQ * (cqs::kMaxK - 1) * sizeof(uint64_t))) != hipSuccess) return oom(e);
     if ((e = hipMalloc(&s->d_cert, (size_t)cqs::kShadowMaxQ * sizeof(uint32_t))) != hipSuccess) return oom(e);
     if ((e = hipMalloc(&s->d_bq, (size_t)cqs::kShadowMaxQ * sizeof(float))) != hipSuccess) return oom(e);
+    if ((e = hipMalloc(&s->d_tickets, (size_t)cqs::kShadowMaxQ * sizeof(uint32_t))) != hipSuccess) return oom(e);
+    if ((e = hipMemsetAsync(s->d_tickets, 0, (size_t)cqs::kShadowMaxQ * sizeof(uint32_t), x->stream)) != hipSuccess) return oom(e);
     if ((e = hipHostMalloc(&s->h_cert, (size_t)cqs::kShadowMaxQ * sizeof(uint32_t), hipHostMallocDefault)) != hipSuccess) return oom(e);
     if (hipHostGetDevicePointer((void**)&s->h_cert_dev, s->h_cert, 0) != hipSuccess) {
         (void)hipGetLastError();
@@ -305,9 +310,13 @@ bool shadow_uses_i8(const cqs_hip_index* x, uint32_t b, uint32_t k) {
     return x->shadow && x->shadow->d_i8 && b <= cqs::kI8MaxQ && cqs::i8_k_ok(k);
 }
 
-// The shadow half of a gemv block on `st`: B_q -> shadow scan -> select k' + 1 -> rescore + certify into out_keys /
-// out_counts.  device_gate (device-API searches): `st` is ordered after the last search here, certify counts outcomes on
-// the device, *device_gate = the verdicts that must gate the f32 launches next.  Null: host searches (shadow_verdicts).
+// The shadow half of a gemv block on `st`: shadow scan -> select k' + 1 -> one tail launch (B_q, rescore, certify) into
+// out_keys / out_counts.  PIPELINE searches alone launch the bound kernel first: only their scan reads B_q (its drop rule).
+// device_gate (device-API searches): `st` is ordered after the last search here, certify counts outcomes on the device,
+// *device_gate = the verdicts that must gate the f32 launches next.  Null: host searches (shadow_verdicts).
+// The tail kernel's last workgroup writes the verdicts before the kernel ends and nothing is launched between it and the
+// gated f32 scan (gate_closed).  Both callers record `done` after the pass, which orders the next search, on any stream,
+// after every user of d_bq, d_akeys, d_ekeys, d_cert and d_tickets.
 int32_t shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k, const uint32_t* d_keep, uint32_t mode,
                     float threshold, uint64_t* out_keys, uint32_t* out_counts, hipStream_t st, const uint32_t** device_gate) {
     const Shadow* s = x->shadow;
@@ -318,8 +327,12 @@ int32_t shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k,
     // scan like any other, not through the bf16 copy.
     const bool i8 = shadow_uses_i8(x, nb, k);
     const uint32_t kp = i8 ? cqs::i8_kprime(k) : cqs::shadow_kprime(k);
-    if (i8) HIP_TRY(x, cqs::launch_i8_bound(d_q, nb, x->dim, s->r8, s->norm8, s->d_bq, st));
-    else HIP_TRY(x, cqs::launch_shadow_bound(d_q, nb, x->dim, s->r, s->norm, s->d_bq, st));
+    const double r_max = i8 ? s->r8 : s->r, norm_max = i8 ? s->norm8 : s->norm;
+    const bool bound_first = mode == CQS_HIP_MODE_PIPELINE;
+    if (bound_first) {
+        if (i8) HIP_TRY(x, cqs::launch_i8_bound(d_q, nb, x->dim, r_max, norm_max, s->d_bq, st));
+        else HIP_TRY(x, cqs::launch_shadow_bound(d_q, nb, x->dim, r_max, norm_max, s->d_bq, st));
+    }
     // gemv passes over the copy's rows (non-uniform tiers, no debug stamps), top k' + 1; the select's (argmax, runner-up)
     // index from kGauxMinK on whatever CQS_HIP_SELECT_AUX says (that A/B hook is the f32 select's)
     const cqs::ScanArgs a = scan_args(x, d_q, nb, kp + 1u, d_keep, mode, threshold, i8 ? sizeof(int8_t) : sizeof(uint16_t), true, nullptr, nullptr);
@@ -327,7 +340,8 @@ int32_t shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k,
     const int32_t rc = scan_select(x, a, st, &rows, s->d_akeys, s->d_acounts);
     if (rc == CQS_HIP_OK)
         HIP_TRY(x, cqs::launch_rescore_certify(x->d_rows, x->dim, d_q, nb, k, kp, mode, threshold, (uint32_t)x->row_base,
-                                               s->d_bq, s->d_akeys, s->d_acounts, s->d_ekeys, out_keys, out_counts, cert,
+                                               bound_first ? 0u : (i8 ? 2u : 1u), r_max, norm_max, s->d_bq, s->d_tickets,
+                                               s->d_akeys, s->d_acounts, s->d_ekeys, out_keys, out_counts, cert,
                                                device_gate ? s->d_stats + kStatCounts : nullptr,
                                                device_gate && i8 ? s->d_stats + kStatI8Counts : nullptr, st));
     return rc;
@@ -442,6 +456,20 @@ int32_t cqs_hip_debug_shadow_bound_i8(cqs_hip_index* x, const float* queries, ui
         for (uint32_t d = 0; d < x->dim; ++d) s2 += (double)q[d] * (double)q[d];
         out_host[i] = cqs::i8_query_bound(s2, s->r8, s->norm8, x->dim);
     }
+    return CQS_HIP_OK;
+} CQS_ABI_CATCH(x)
+
+// Test hook: out[0, b) = d_bq as the last search left it (B_q of its queries, whichever launch computed it), once every
+// search has completed.  INVALID without a shadow or for b > kShadowMaxQ.
+int32_t cqs_hip_debug_shadow_bq(cqs_hip_index* x, uint32_t b, float* out) CQS_ABI_TRY {
+    if (!x || x->sh || !out || b == 0) return CQS_HIP_ERR_INVALID;
+    std::lock_guard<std::mutex> g(x->mu);
+    const Shadow* s = x->shadow;
+    if (!s || b > cqs::kShadowMaxQ) return CQS_HIP_ERR_INVALID;
+    HIP_TRY(x, hipSetDevice(x->device));
+    HIP_TRY(x, quiesce(x));
+    HIP_TRY(x, hipMemcpyAsync(out, s->d_bq, (size_t)b * sizeof(float), hipMemcpyDeviceToHost, x->stream));
+    HIP_TRY(x, hipStreamSynchronize(x->stream));
     return CQS_HIP_OK;
 } CQS_ABI_CATCH(x)
 

@@ -1,5 +1,5 @@
 // rank_sort.h — the select's in-LDS rank sort of <= 1024 distinct packed keys, shared by select_finish_kernel
-// (scan_kernels.hip) and the bf16 shadow's certify kernel (scan_bf16.hip).  Device code only; internal to libcqs_hip.so.
+// (scan_kernels.hip) and the finishing workgroup of the shadow's rescore + certify kernel (scan_bf16.hip).  Device code only; internal to libcqs_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -58,6 +58,21 @@ CQS_HD inline float shadow_query_bound(double q_norm2, double r_max, double norm
 }
 
 #if defined(__HIPCC__)
+// ||q||^2 of one query as one wave sums it, in every lane: lane l adds the squares of components l, l + 64, ... in f64 (each
+// square is exact), then an xor butterfly 32 -> 1.  One definition for the stand-alone bound kernels and the fused
+// rescore + certify kernel, so that B_q has the same bits whoever computes it.
+__device__ __forceinline__ double wave_q_norm2(const float* qp, uint32_t dim, uint32_t lane) {
+    double s2 = 0.0;
+    for (uint32_t d = lane; d < dim; d += 64u) s2 += (double)qp[d] * (double)qp[d];
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) s2 += __shfl_xor(s2, m, 64);
+    return s2;
+}
+// B_q of the bf16 copy from one wave (the value is meant for lane 0; NaN / inf in q: +inf).
+__device__ __forceinline__ float wave_shadow_bound(const float* qp, uint32_t dim, double r_max, double norm_max, uint32_t lane) {
+    return shadow_query_bound(wave_q_norm2(qp, dim, lane), r_max, norm_max, dim);
+}
+
 // Build: one pass over rows [row0, row0 + rows) of the f32 corpus -> bf16 rows (round to nearest even, NaN stays NaN),
 // and over the rows whose components are all finite the maxima of r = ||x - x~|| + gamma (||x|| + ||x~||) and of
 // max(||x||, ||x~||), as f64 bits (both >= 0, so the bits order like the values).  stats[0] / stats[1] must be zero (or
@@ -75,16 +90,22 @@ hipError_t launch_shadow_bound(const float* q, uint32_t b, uint32_t dim, double 
 // (a.b <= kShadowMaxQ), read by the PIPELINE drop rule only.
 hipError_t launch_scan_bf16(const ScanArgs& a, const uint16_t* shadow, const float* bq, hipStream_t st);
 
-// Rescore the first min(count, k') approximate keys of each query from the f32 rows (the gemv kernel's arithmetic and
-// epilogue), take the top k by the select's rank sort, write out_keys [b, k] / out_counts [b] as launch_select does, and
-// cert[b] = 1 when that answer is provably the f32 scan's (else the caller re-runs the query on the f32 scan).
-// akeys [b, k' + 1] / acounts [b]: the select's output; ekeys: [b, k'] scratch; bq: device [b] (launch_shadow_bound).
+// One launch for the tail of a shadow search (rescore_certify_kernel).  Rescore the first min(count, k') approximate keys of
+// each query from the f32 rows (the gemv kernel's arithmetic and epilogue), take the top k by the select's rank sort, write
+// out_keys [b, k] / out_counts [b] as launch_select does, and cert[b] = 1 when that answer is provably the f32 scan's (else
+// the caller re-runs the query on the f32 scan).  cert is written before the kernel ends.
+// akeys [b, k' + 1] / acounts [b]: the select's output; ekeys: [b, k'] scratch.
+// bound: 1 / 2 = compute B_q of the bf16 / int8 copy here (launch_shadow_bound's / launch_i8_bound's bits, from r_max and
+// norm_max) into bq [b]; 0 = bq already holds it (a launch_*_bound earlier on st: PIPELINE searches, whose scan reads it).
+// tickets: device [b], zero on entry (once, at allocation) and left zero: the workgroups of a query count their arrivals
+// there, and the last one certifies.
 // counters, counters2: nullable device [2] each: += certified, += not certified queries of the block (device-API searches,
 // whose outcome the host never sees; the second pair counts what the int8 copy served).
 hipError_t launch_rescore_certify(const float* rows, uint32_t dim, const float* q, uint32_t b, uint32_t k, uint32_t kprime,
-                                  uint32_t mode, float thr, uint32_t row_base, const float* bq, const uint64_t* akeys,
-                                  const uint32_t* acounts, uint64_t* ekeys, uint64_t* out_keys, uint32_t* out_counts,
-                                  uint32_t* cert, unsigned long long* counters, unsigned long long* counters2, hipStream_t st);
+                                  uint32_t mode, float thr, uint32_t row_base, uint32_t bound, double r_max, double norm_max,
+                                  float* bq, uint32_t* tickets, const uint64_t* akeys, const uint32_t* acounts,
+                                  uint64_t* ekeys, uint64_t* out_keys, uint32_t* out_counts, uint32_t* cert,
+                                  unsigned long long* counters, unsigned long long* counters2, hipStream_t st);
 #endif
 
 }  // namespace cqs

@@ -7,12 +7,14 @@
 //  scan_bf16_kernel      HBM-streaming dot of every bf16 row with 1..8 f32 queries: half the bytes of scan_gemv_kernel.
 //                        Same tasks / work queue / score + gmax (+ gaux) layout, so the unchanged select_finish_kernel
 //                        takes each query's top k' + 1 approximate keys.
-//  rescore_kernel        one wave per candidate: the exact f32 score, bit for bit what scan_gemv_kernel computes.
-//  certify_kernel        one workgroup per query: top k of the rescored candidates (the select's rank sort) and the
-//                        certificate that no row outside them can enter the top k.
+//  rescore_certify_kernel  one launch for a block's tail.  One wave per candidate: the exact f32 score, bit for bit what
+//                        scan_gemv_kernel computes; one wave per query: B_q, unless an earlier launch computed it; the
+//                        last workgroup of each query to arrive: top k of the rescored candidates (the select's rank
+//                        sort) and the certificate that no row outside them can enter the top k.
 //
 // Wave = 64 lanes.  gfx950 only.
 #include "scan_bf16.h"
+#include "scan_i8.h"
 #include "launch_util.h"
 #include "rank_sort.h"
 #include "scan_device.h"
@@ -86,16 +88,14 @@ hipError_t launch_shadow_build(const float* rows, uint16_t* shadow, uint64_t row
 
 // ---- per-query bound ----------------------------------------------------------------------------------------------
 // ||q||^2 as an f64 sum (the squares of f32 components are exact in f64; the order differs from a host loop, which the
-// 2^-40 slack of shadow_query_bound covers), then the same bound function the host compiles.
+// 2^-40 slack of shadow_query_bound covers), then the same bound function the host compiles: wave_shadow_bound, which the
+// fused rescore + certify kernel shares.  Stand-alone for PIPELINE searches (the scan's drop rule reads B_q) and the
+// debug hooks.
 __global__ __launch_bounds__(64) void shadow_bound_kernel(const float* __restrict__ q, uint32_t dim, double r_max,
                                                           double norm_max, float* __restrict__ bq) {
     const uint32_t lane = threadIdx.x;
-    const float* qp = q + (size_t)blockIdx.x * dim;
-    double s2 = 0.0;
-    for (uint32_t d = lane; d < dim; d += 64u) s2 += (double)qp[d] * (double)qp[d];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) s2 += __shfl_xor(s2, m, 64);
-    if (lane == 0) bq[blockIdx.x] = shadow_query_bound(s2, r_max, norm_max, dim);   // (NaN / inf in q: +inf)
+    const float v = wave_shadow_bound(q + (size_t)blockIdx.x * dim, dim, r_max, norm_max, lane);
+    if (lane == 0) bq[blockIdx.x] = v;
 }
 
 hipError_t launch_shadow_bound(const float* q, uint32_t b, uint32_t dim, double r_max, double norm_max, float* bq,
@@ -345,88 +345,115 @@ hipError_t launch_scan_bf16(const ScanArgs& a, const uint16_t* shadow, const flo
 }
 
 // ---- rescore + certify ------------------------------------------------------------------------------------------
-struct RescoreParams {
+struct TailParams {
     const float* rows;
     const float* q;
-    uint32_t dim, kprime, mode, row_base;
+    uint32_t dim, k, kprime, mode, row_base;
     float thr;
-    const uint64_t* akeys;     // [b, k' + 1]
+    const uint64_t* akeys;     // [b, k' + 1]  (written by the select, an earlier launch)
     const uint32_t* acounts;   // [b]
-    uint64_t* ekeys;           // [b, k']: exact key of candidate i, 0 = dropped by the f32 epilogue
-};
-
-// One wave per candidate, 4 per workgroup; blockIdx.y = query.  The score is scan_gemv_kernel's for this (row, query):
-// lane owns floats [c*256 + lane*4, +4) of chunk c (clamped address and zero query fragment past a partial last chunk),
-// an (even, odd) packed-FMA chain over the chunks in order, even + odd, then the xor butterfly at distances 32 -> 1 - the
-// tree treduce builds for every RI x BQ (each node adds the same two partial sums; IEEE addition commutes).
-template <int NCH>
-__global__ __launch_bounds__(256) void rescore_kernel(const RescoreParams p) {
-    const int lane = threadIdx.x & 63;
-    const uint32_t qi = blockIdx.y;
-    const uint32_t i = blockIdx.x * 4u + (threadIdx.x >> 6);
-    const uint32_t ac = p.acounts[qi];
-    const uint32_t cnt = ac < p.kprime ? ac : p.kprime;
-    if (i >= cnt) return;   // (wave-uniform)
-    const uint64_t key = p.akeys[(size_t)qi * (p.kprime + 1u) + i];
-    const uint32_t grow = 0xFFFFFFFFu - (uint32_t)key;
-    const uint32_t dim = p.dim;
-    const float* rp = p.rows + (size_t)(grow - p.row_base) * dim;
-    const float* qp = p.q + (size_t)qi * dim;
-    f4 x[NCH], qv[NCH];
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const uint32_t idx = (uint32_t)c * 256u + (uint32_t)lane * 4u;
-        const bool in = idx < dim;
-        const uint32_t off = in ? idx : dim - 4u;
-        x[c] = *(const f4*)(rp + off);
-        const f4 v = *(const f4*)(qp + off);
-        qv[c] = in ? v : (f4)(0.f);
-    }
-    f2 acc2 = (f2)(0.f);
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        const f2 xlo = __builtin_shufflevector(x[c], x[c], 0, 1);
-        const f2 xhi = __builtin_shufflevector(x[c], x[c], 2, 3);
-        acc2 = __builtin_elementwise_fma(xlo, __builtin_shufflevector(qv[c], qv[c], 0, 1), acc2);
-        acc2 = __builtin_elementwise_fma(xhi, __builtin_shufflevector(qv[c], qv[c], 2, 3), acc2);
-    }
-    float s = acc2.x + acc2.y;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
-    // scan_gemv_kernel's epilogue: non-finite dropped; PIPELINE: clamp(0, 1) then `>= threshold`
-    bool keep = __builtin_fabsf(s) <= 3.4028234664e38f;
-    if (keep && p.mode == 1u) {
-        s = s < 0.f ? 0.f : (s > 1.f ? 1.f : s);
-        keep = s >= p.thr;
-    }
-    if (lane == 0) p.ekeys[(size_t)qi * p.kprime + i] = keep ? pack_key(okey(s), grow) : 0ull;
-}
-
-struct CertifyParams {
-    const uint64_t* ekeys;
-    const uint64_t* akeys;
-    const uint32_t* acounts;
-    uint32_t k, kprime, mode;
+    uint64_t* ekeys;           // [b, k']: exact key of candidate i, 0 = dropped by the f32 epilogue.  Handed from the
+                               // rescoring waves to the finishing workgroup inside the launch (agent-scope accesses only)
+    float* bq;                 // [b] B_q; bound != 0: computed here and handed over like ekeys
+    uint32_t* tickets;         // [b] arrivals of each query's workgroups: 0 on entry, 0 again on exit
+    uint32_t bound;            // 0: bq holds the block's bounds (an earlier launch), 1: the bf16 copy's, 2: the int8 copy's
+    double r_max, norm_max;    // of that copy
     uint64_t* out_keys;        // [b, k]
     uint32_t* out_counts;      // [b]
     uint32_t* cert;            // [b]
-    const float* bq;           // [b]
     unsigned long long* counters;   // nullable [2]: certified, not certified
     unsigned long long* counters2;  // nullable [2]: the same again (the int8 copy's own counts)
 };
 
-__global__ __launch_bounds__(1024) void certify_kernel(const CertifyParams p) {
+constexpr uint32_t kTailWaves = 16;   // 1024 threads: the block shape rank_sort_keys is written for
+
+// One launch for a block's tail.  blockIdx.y = query; the query's waves are numbered slot = blockIdx.x * 16 + wave.
+//  slot 0           B_q of the query into bq (bound != 0), beside the rescoring waves, off their path.
+//  slot i + 1       candidate i < min(count, k'): its exact f32 score, scan_gemv_kernel's for this (row, query): lane owns
+//                   floats [c*256 + lane*4, +4) of chunk c (clamped address and zero query fragment past a partial last
+//                   chunk), an (even, odd) packed-FMA chain over the chunks in order, even + odd, then the xor butterfly at
+//                   distances 32 -> 1 - the tree treduce builds for every RI x BQ (each node adds the same two partial
+//                   sums; IEEE addition commutes) - and that kernel's epilogue.
+//  last workgroup   of the query to arrive certifies: top k of the rescored candidates (the select's rank sort) into
+//                   out_keys / out_counts, and cert = 1 when no row outside them can enter the top k.
+// Nobody waits for anybody: a workgroup adds one to the query's ticket when its waves have stored, and the one whose add
+// returns gridDim.x - 1 knows that every other has.  It puts the ticket back to 0 for the next search.
+// Visibility (per-XCD L2s are not coherent, a CU's L1 is never refreshed): every word handed over (ekeys, bq) is stored
+// write-through by an agent-scope atomic store, each wave drains its stores before the workgroup's barrier, one lane then
+// adds to the ticket, and the finisher reads those words by agent-scope atomic loads only, after the add has returned and a
+// barrier that the adding wave joins.  akeys / acounts come from an earlier launch and are read plainly.
+template <int NCH>
+__global__ __launch_bounds__(1024) void rescore_certify_kernel(const TailParams p) {
     __shared__ uint64_t s_keys[kShadowKMax];
     __shared__ uint64_t s_sorted[kShadowKMax];
     __shared__ __attribute__((aligned(16))) uint32_t s_ok[kShadowKMax + 4];
-    __shared__ uint32_t s_cnt, s_flag;
-    const uint32_t qi = blockIdx.x;
+    __shared__ uint32_t s_cnt, s_flag, s_last;
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint32_t qi = blockIdx.y;
+    const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * kTailWaves + (threadIdx.x >> 6)));
     const uint32_t ac = p.acounts[qi];
     const uint32_t nc = ac < p.kprime ? ac : p.kprime;
+    const uint32_t dim = p.dim;
+    const float* qp = p.q + (size_t)qi * dim;
     if (threadIdx.x == 0) s_cnt = 0u;
+    if (slot == 0u) {
+        if (p.bound != 0u) {
+            const float v = p.bound == 2u ? wave_i8_bound(qp, dim, p.r_max, p.norm_max, lane)
+                                          : wave_shadow_bound(qp, dim, p.r_max, p.norm_max, lane);
+            if (lane == 0u)
+                __hip_atomic_store((uint32_t*)p.bq + qi, __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    } else if (slot - 1u < nc) {
+        const uint32_t i = slot - 1u;
+        const uint64_t key = p.akeys[(size_t)qi * (p.kprime + 1u) + i];
+        const uint32_t grow = 0xFFFFFFFFu - (uint32_t)key;
+        const float* rp = p.rows + (size_t)(grow - p.row_base) * dim;
+        f4 x[NCH], qv[NCH];
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            const uint32_t idx = (uint32_t)c * 256u + lane * 4u;
+            const bool in = idx < dim;
+            const uint32_t off = in ? idx : dim - 4u;
+            x[c] = *(const f4*)(rp + off);
+            const f4 v = *(const f4*)(qp + off);
+            qv[c] = in ? v : (f4)(0.f);
+        }
+        f2 acc2 = (f2)(0.f);
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            const f2 xlo = __builtin_shufflevector(x[c], x[c], 0, 1);
+            const f2 xhi = __builtin_shufflevector(x[c], x[c], 2, 3);
+            acc2 = __builtin_elementwise_fma(xlo, __builtin_shufflevector(qv[c], qv[c], 0, 1), acc2);
+            acc2 = __builtin_elementwise_fma(xhi, __builtin_shufflevector(qv[c], qv[c], 2, 3), acc2);
+        }
+        float s = acc2.x + acc2.y;
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+        // scan_gemv_kernel's epilogue: non-finite dropped; PIPELINE: clamp(0, 1) then `>= threshold`
+        bool keep = __builtin_fabsf(s) <= 3.4028234664e38f;
+        if (keep && p.mode == 1u) {
+            s = s < 0.f ? 0.f : (s > 1.f ? 1.f : s);
+            keep = s >= p.thr;
+        }
+        if (lane == 0u)
+            __hip_atomic_store(p.ekeys + (size_t)qi * p.kprime + i, keep ? pack_key(okey(s), grow) : 0ull, __ATOMIC_RELAXED,
+                               __HIP_MEMORY_SCOPE_AGENT);
+    }
+    // hand-off: every wave drains its stores, the barrier, then one lane signals for the workgroup
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
+    if (threadIdx.x == 0) {
+        const uint32_t t = __hip_atomic_fetch_add(p.tickets + qi, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const bool last = t == gridDim.x - 1u;
+        if (last) __hip_atomic_store(p.tickets + qi, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // armed for the next search
+        s_last = last ? 1u : 0u;
+    }
+    __syncthreads();
+    if (s_last == 0u) return;   // (workgroup-uniform) not the last to arrive: done
+
+    // the finisher: every other workgroup of the query has stored, drained and signalled
     if (threadIdx.x < nc) {
-        const uint64_t key = p.ekeys[(size_t)qi * p.kprime + threadIdx.x];
+        const uint64_t key = __hip_atomic_load(p.ekeys + (size_t)qi * p.kprime + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (key != 0ull) s_keys[atomicAdd(&s_cnt, 1u)] = key;
     }
     __syncthreads();
@@ -437,7 +464,7 @@ __global__ __launch_bounds__(1024) void certify_kernel(const CertifyParams p) {
     for (uint32_t i = threadIdx.x; i < k; i += 1024u) p.out_keys[(size_t)qi * k + i] = (i < outc) ? s_sorted[i] : 0ull;
     if (threadIdx.x == 0) {
         p.out_counts[qi] = outc;
-        const float bq = p.bq[qi];
+        const float bq = __uint_as_float(__hip_atomic_load((uint32_t*)p.bq + qi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
         bool ok = false;
         if (__builtin_fabsf(bq) <= 3.4028234664e38f) {
             if (ac <= p.kprime) ok = true;   // (a) every row the approximate rules keep was rescored
@@ -447,36 +474,34 @@ __global__ __launch_bounds__(1024) void certify_kernel(const CertifyParams p) {
                 ok = t < key_score(s_sorted[k - 1u]);
             }
         }
-        p.cert[qi] = ok ? 1u : 0u;
+        p.cert[qi] = ok ? 1u : 0u;   // (before the kernel ends: the gated f32 launches that follow read it at entry)
         if (p.counters) atomicAdd(&p.counters[ok ? 0 : 1], 1ull);
         if (p.counters2) atomicAdd(&p.counters2[ok ? 0 : 1], 1ull);
     }
 }
 
 hipError_t launch_rescore_certify(const float* rows, uint32_t dim, const float* q, uint32_t b, uint32_t k, uint32_t kprime,
-                                  uint32_t mode, float thr, uint32_t row_base, const float* bq, const uint64_t* akeys,
-                                  const uint32_t* acounts, uint64_t* ekeys, uint64_t* out_keys, uint32_t* out_counts,
-                                  uint32_t* cert, unsigned long long* counters, unsigned long long* counters2, hipStream_t st) {
+                                  uint32_t mode, float thr, uint32_t row_base, uint32_t bound, double r_max, double norm_max,
+                                  float* bq, uint32_t* tickets, const uint64_t* akeys, const uint32_t* acounts,
+                                  uint64_t* ekeys, uint64_t* out_keys, uint32_t* out_counts, uint32_t* cert,
+                                  unsigned long long* counters, unsigned long long* counters2, hipStream_t st) {
     if (b == 0) return hipSuccess;
-    if (b > kShadowMaxQ || k == 0 || kprime < k || kprime >= kShadowKMax || dim % 8u != 0u || dim > kShadowMaxDim)
+    if (b > kShadowMaxQ || k == 0 || kprime < k || kprime >= kShadowKMax || dim % 8u != 0u || dim > kShadowMaxDim || bound > 2u)
         return hipErrorInvalidValue;
-    RescoreParams rp{rows, q, dim, kprime, mode, row_base, thr, akeys, acounts, ekeys};
-    const dim3 grid((kprime + 3u) / 4u, b), block(256);
+    const TailParams tp{rows, q, dim, k, kprime, mode, row_base, thr, akeys, acounts, ekeys, bq, tickets, bound, r_max, norm_max,
+                        out_keys, out_counts, cert, counters, counters2};
+    const dim3 grid((kprime + 1u + kTailWaves - 1u) / kTailWaves, b), block(64u * kTailWaves);   // (slot 0 + k' candidates)
     switch ((dim + 255u) / 256u) {
-        case 1: hipLaunchKernelGGL(rescore_kernel<1>, grid, block, 0, st, rp); break;
-        case 2: hipLaunchKernelGGL(rescore_kernel<2>, grid, block, 0, st, rp); break;
-        case 3: hipLaunchKernelGGL(rescore_kernel<3>, grid, block, 0, st, rp); break;
-        case 4: hipLaunchKernelGGL(rescore_kernel<4>, grid, block, 0, st, rp); break;
-        case 5: hipLaunchKernelGGL(rescore_kernel<5>, grid, block, 0, st, rp); break;
-        case 6: hipLaunchKernelGGL(rescore_kernel<6>, grid, block, 0, st, rp); break;
-        case 7: hipLaunchKernelGGL(rescore_kernel<7>, grid, block, 0, st, rp); break;
-        case 8: hipLaunchKernelGGL(rescore_kernel<8>, grid, block, 0, st, rp); break;
+        case 1: hipLaunchKernelGGL(rescore_certify_kernel<1>, grid, block, 0, st, tp); break;
+        case 2: hipLaunchKernelGGL(rescore_certify_kernel<2>, grid, block, 0, st, tp); break;
+        case 3: hipLaunchKernelGGL(rescore_certify_kernel<3>, grid, block, 0, st, tp); break;
+        case 4: hipLaunchKernelGGL(rescore_certify_kernel<4>, grid, block, 0, st, tp); break;
+        case 5: hipLaunchKernelGGL(rescore_certify_kernel<5>, grid, block, 0, st, tp); break;
+        case 6: hipLaunchKernelGGL(rescore_certify_kernel<6>, grid, block, 0, st, tp); break;
+        case 7: hipLaunchKernelGGL(rescore_certify_kernel<7>, grid, block, 0, st, tp); break;
+        case 8: hipLaunchKernelGGL(rescore_certify_kernel<8>, grid, block, 0, st, tp); break;
         default: return hipErrorInvalidValue;
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    CertifyParams cp{ekeys, akeys, acounts, k, kprime, mode, out_keys, out_counts, cert, bq, counters, counters2};
-    hipLaunchKernelGGL(certify_kernel, dim3(b), dim3(1024), 0, st, cp);
     return hipGetLastError();
 }
 

@@ -45,6 +45,12 @@ CQS_HD inline float i8_query_bound(double q_norm2, double r_max, double norm_max
 }
 
 #if defined(__HIPCC__)
+// B_q of the int8 copy from one wave: wave_shadow_bound with this copy's bound function (same f64 sum of squares, same
+// 2^-40 slack for its order).  Shared by i8_bound_kernel and the fused rescore + certify kernel.
+__device__ __forceinline__ float wave_i8_bound(const float* qp, uint32_t dim, double r_max, double norm_max, uint32_t lane) {
+    return i8_query_bound(wave_q_norm2(qp, dim, lane), r_max, norm_max, dim);
+}
+
 // Build: one pass over rows [row0, row0 + rows) of the f32 corpus.  Per row: scale = max|x_i| / 127 in f32 (0 for a row
 // whose maximum is zero or underflows: all codes 0; NaN for a row with a non-finite component: its score is non-finite in
 // the int8 scan as it is in the f32 one), c_i = round-to-nearest-even(x_i / scale) clamped to [-127, 127].  stats[0..2] as

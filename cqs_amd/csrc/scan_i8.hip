@@ -97,16 +97,12 @@ hipError_t launch_i8_build(const float* rows, int8_t* codes, float* scales, uint
 }
 
 // ---- per-query bound ----------------------------------------------------------------------------------------------
-// shadow_bound_kernel with the int8 copy's bound function (same f64 sum of squares, same 2^-40 slack for its order).
+// shadow_bound_kernel with the int8 copy's bound function (wave_i8_bound, which the fused rescore + certify kernel shares).
 __global__ __launch_bounds__(64) void i8_bound_kernel(const float* __restrict__ q, uint32_t dim, double r_max,
                                                       double norm_max, float* __restrict__ bq) {
     const uint32_t lane = threadIdx.x;
-    const float* qp = q + (size_t)blockIdx.x * dim;
-    double s2 = 0.0;
-    for (uint32_t d = lane; d < dim; d += 64u) s2 += (double)qp[d] * (double)qp[d];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) s2 += __shfl_xor(s2, m, 64);
-    if (lane == 0) bq[blockIdx.x] = i8_query_bound(s2, r_max, norm_max, dim);   // (NaN / inf in q: +inf)
+    const float v = wave_i8_bound(q + (size_t)blockIdx.x * dim, dim, r_max, norm_max, lane);
+    if (lane == 0) bq[blockIdx.x] = v;
 }
 
 hipError_t launch_i8_bound(const float* q, uint32_t b, uint32_t dim, double r_max, double norm_max, float* bq, hipStream_t st) {

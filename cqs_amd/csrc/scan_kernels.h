@@ -88,10 +88,11 @@ bool scan_dim_supported(uint32_t dim);
 // The f32 fallback gate of the device-API shadow search (index.hip, cqs_hip_index_search_device): true when gate[0, b)
 // are all 1.  Invariants, kept by every kernel that takes a gate:
 //  - the gemv scan and the select decide the same way from the same words (this function, at entry, in every wave;
-//    the words were written by an earlier kernel of the stream and do not change during the launch);
+//    the words were written by an earlier kernel of the stream - the last workgroup of the shadow's tail kernel, before
+//    that kernel ended - and do not change during the launch);
 //  - a skipped scan never touches the work-queue heads: the shadow pass's select has re-zeroed them already, and the
 //    skipped select has nothing to re-zero;
-//  - the launches between the certify kernel and the gated select include no memset (gemv blocks of <= 32 queries stay
+//  - the launches between the shadow's tail kernel (rescore_certify_kernel) and the gated select include no memset (gemv blocks of <= 32 queries stay
 //    under kWorkWords launches); a memset added there must be gated too.
 __device__ __forceinline__ bool gate_closed(const uint32_t* gate, uint32_t b) {
     uint32_t all = 1u;

@@ -6,7 +6,7 @@
 The bench's seeded corpus distribution (bench_legs.common.make_unit_rows: Gaussian unit rows; seed 0xC950001 at 1M rows is
 bench.py's own corpus) and its 330 seeded queries (0xC950002).  The corpus is quantised as i8_build_kernel does (scale =
 max|x_i| / 127 in f32, round to nearest even, clamp), R_8 = max ||x - x~|| + gamma' (||x|| + ||x~||) in f64, B_q = ||q|| R_8,
-and for each k the needed k' of a query is the smallest k' with  s~_(k'+1) + B_q < s_(k)  (certify_kernel's rule (b)).
+and for each k the needed k' of a query is the smallest k' with  s~_(k'+1) + B_q < s_(k)  (the certificate's rule (b), rescore_certify_kernel).
 Scores come from torch's f32 matmul, not the scan kernels: they differ from the kernels' by ~1e-7, against B_q ~ 1.3e-2.
 Prints one JSON object: per (rows, k) the median / p99 / max needed k' over the queries."""
 import argparse
