@@ -155,7 +155,7 @@ int32_t scan_select(cqs_hip_index* x, const cqs::ScanArgs& a, hipStream_t st, co
         HIP_TRY(x, hipEventRecord(x->ev[x->ev_used + 1], st));
         x->ev_used += 2;
     }
-    HIP_TRY(x, cqs::launch_select(a, (uint32_t)x->row_base, out_keys, out_counts, st));
+    if (out_keys) HIP_TRY(x, cqs::launch_select(a, (uint32_t)x->row_base, out_keys, out_counts, st));
     return CQS_HIP_OK;
 }
 

@@ -124,7 +124,8 @@ cqs::ScanArgs scan_args(const cqs_hip_index* x, const float* d_q, uint32_t b, ui
                         uint32_t mode, float thr, size_t elem_bytes, bool gemv_only, void* dbg, const uint32_t* gate);
 // The rows a shadow scan reads: the bf16 copy, or (bf16 null) the int8 codes and their row scales; bq: B_q of the block.
 struct ShadowRows { const uint16_t* bf16; const int8_t* i8; const float* i8_scale; const float* bq; };
-// The scan of `a` on st (over `shadow` when set; timed unless a.gate: the shadow scan was), then the select.
+// The scan of `a` on st (over `shadow` when set; timed unless a.gate: the shadow scan was), then the select (out_keys null:
+// the scan alone - the shadow's tail kernel selects, and zeroes the work-queue heads as the select does).
 int32_t scan_select(cqs_hip_index* x, const cqs::ScanArgs& a, hipStream_t st, const ShadowRows* shadow,
                     uint64_t* out_keys, uint32_t* out_counts);
 // Searches share one scratch: order `st` after the last search / record `done` on `st` at the end of one.  Caller holds mu.

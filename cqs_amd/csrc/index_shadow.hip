@@ -36,8 +36,6 @@ struct Shadow {
     unsigned long long* d_stats = nullptr;   // [kStatWords] the build pass's maxima (f64 bits) and outlier flag, the
                                              // device-API searches' certified / fallback counts (certify adds), then the
                                              // same five words of the int8 copy
-    uint64_t* d_akeys = nullptr;          // [kShadowMaxQ, kMaxK] approximate keys of the select
-    uint32_t* d_acounts = nullptr;        // [kShadowMaxQ]
     uint64_t* d_ekeys = nullptr;          // [kShadowMaxQ, kMaxK - 1] rescored keys
     uint32_t* d_cert = nullptr;           // [kShadowMaxQ] certified flags (device-API searches: the f32 gate; host searches:
                                           // when h_cert is not mappable)
@@ -79,7 +77,7 @@ void shadow_free(cqs_hip_index* x) {
     x->stat_i8_certified.fetch_add(c, std::memory_order_relaxed);
     x->stat_i8_fallbacks.fetch_add(f, std::memory_order_relaxed);
     i8_free(s);
-    hipFree(s->d_bf16); hipFree(s->d_stats); hipFree(s->d_akeys); hipFree(s->d_acounts); hipFree(s->d_ekeys);
+    hipFree(s->d_bf16); hipFree(s->d_stats); hipFree(s->d_ekeys);
     hipFree(s->d_cert); hipFree(s->d_bq); hipFree(s->d_tickets); hipHostFree(s->h_cert);
     delete s;
     x->shadow = nullptr;
@@ -208,8 +206,6 @@ static int32_t shadow_enable(cqs_hip_index* x, const char* what) {
     if ((e = hipMalloc(&stats, kStatWords * sizeof(unsigned long long))) != hipSuccess) return oom(e);
     if ((e = hipMemsetAsync(stats, 0, kStatWords * sizeof(unsigned long long), x->stream)) != hipSuccess) { hipFree(stats); return oom(e); }
     s->d_stats = stats;
-    if ((e = hipMalloc(&s->d_akeys, (size_t)cqs::kShadowMaxQ * cqs::kMaxK * sizeof(uint64_t))) != hipSuccess) return oom(e);
-    if ((e = hipMalloc(&s->d_acounts, (size_t)cqs::kShadowMaxQ * sizeof(uint32_t))) != hipSuccess) return oom(e);
     if ((e = hipMalloc(&s->d_ekeys, (size_t)cqs::kShadowMaxQ * (cqs::kMaxK - 1) * sizeof(uint64_t))) != hipSuccess) return oom(e);
     if ((e = hipMalloc(&s->d_cert, (size_t)cqs::kShadowMaxQ * sizeof(uint32_t))) != hipSuccess) return oom(e);
     if ((e = hipMalloc(&s->d_bq, (size_t)cqs::kShadowMaxQ * sizeof(float))) != hipSuccess) return oom(e);
@@ -286,7 +282,7 @@ int32_t shadow_auto(cqs_hip_index* x) {
         return CQS_HIP_OK;
     }
     const uint64_t cap = x->cap_rows ? x->cap_rows : 1;
-    const uint64_t need = cap * x->dim * sizeof(uint16_t) + (2ull * cqs::kMaxK + 2ull) * cqs::kShadowMaxQ * sizeof(uint64_t);
+    const uint64_t need = cap * x->dim * sizeof(uint16_t) + (cqs::kMaxK + 2ull) * cqs::kShadowMaxQ * sizeof(uint64_t);
     const uint64_t frac = (uint64_t)(kShadowFreeFrac * (double)total_b);
     const uint64_t reserve = frac > kShadowFreeMinBytes ? frac : kShadowFreeMinBytes;
     if (free_b < need || free_b - need < reserve) {
@@ -310,13 +306,13 @@ bool shadow_uses_i8(const cqs_hip_index* x, uint32_t b, uint32_t k) {
     return x->shadow && x->shadow->d_i8 && b <= cqs::kI8MaxQ && cqs::i8_k_ok(k);
 }
 
-// The shadow half of a gemv block on `st`: shadow scan -> select k' + 1 -> one tail launch (B_q, rescore, certify) into
+// The shadow half of a gemv block on `st`: shadow scan -> one tail launch (select k' + 1, B_q, rescore, certify) into
 // out_keys / out_counts.  PIPELINE searches alone launch the bound kernel first: only their scan reads B_q (its drop rule).
 // device_gate (device-API searches): `st` is ordered after the last search here, certify counts outcomes on the device,
 // *device_gate = the verdicts that must gate the f32 launches next.  Null: host searches (shadow_verdicts).
-// The tail kernel's last workgroup writes the verdicts before the kernel ends and nothing is launched between it and the
-// gated f32 scan (gate_closed).  Both callers record `done` after the pass, which orders the next search, on any stream,
-// after every user of d_bq, d_akeys, d_ekeys, d_cert and d_tickets.
+// The tail kernel's last workgroup writes the verdicts, and its first the zeroed work-queue heads, before the kernel ends,
+// and nothing is launched between it and the gated f32 scan (gate_closed).  Both callers record `done` after the pass,
+// which orders the next search, on any stream, after every user of d_bq, d_ekeys, d_cert and d_tickets.
 int32_t shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k, const uint32_t* d_keep, uint32_t mode,
                     float threshold, uint64_t* out_keys, uint32_t* out_counts, hipStream_t st, const uint32_t** device_gate) {
     const Shadow* s = x->shadow;
@@ -337,11 +333,10 @@ int32_t shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k,
     // index from kGauxMinK on whatever CQS_HIP_SELECT_AUX says (that A/B hook is the f32 select's)
     const cqs::ScanArgs a = scan_args(x, d_q, nb, kp + 1u, d_keep, mode, threshold, i8 ? sizeof(int8_t) : sizeof(uint16_t), true, nullptr, nullptr);
     const ShadowRows rows{i8 ? nullptr : s->d_bf16, i8 ? s->d_i8 : nullptr, s->d_i8_scale, s->d_bq};
-    const int32_t rc = scan_select(x, a, st, &rows, s->d_akeys, s->d_acounts);
+    const int32_t rc = scan_select(x, a, st, &rows, nullptr, nullptr);   // (the scan alone: the tail kernel selects)
     if (rc == CQS_HIP_OK)
-        HIP_TRY(x, cqs::launch_rescore_certify(x->d_rows, x->dim, d_q, nb, k, kp, mode, threshold, (uint32_t)x->row_base,
-                                               bound_first ? 0u : (i8 ? 2u : 1u), r_max, norm_max, s->d_bq, s->d_tickets,
-                                               s->d_akeys, s->d_acounts, s->d_ekeys, out_keys, out_counts, cert,
+        HIP_TRY(x, cqs::launch_rescore_certify(a, (uint32_t)x->row_base, k, kp, bound_first ? 0u : (i8 ? 2u : 1u), r_max, norm_max,
+                                               s->d_bq, s->d_tickets, s->d_ekeys, out_keys, out_counts, cert,
                                                device_gate ? s->d_stats + kStatCounts : nullptr,
                                                device_gate && i8 ? s->d_stats + kStatI8Counts : nullptr, st));
     return rc;

@@ -86,26 +86,27 @@ hipError_t launch_shadow_bound(const float* q, uint32_t b, uint32_t dim, double 
                                hipStream_t st);
 
 // Approximate scan of the shadow: the scores / gmax / gaux layout of launch_scan (gemv passes of <= 8 queries), so the
-// unchanged launch_select picks each query's top k' + 1.  a.rows is ignored; bq: device [a.b], B_q of each query
+// select's unchanged body (inside launch_rescore_certify's kernel) picks each query's top k' + 1.  a.rows is ignored; bq: device [a.b], B_q of each query
 // (a.b <= kShadowMaxQ), read by the PIPELINE drop rule only.
 hipError_t launch_scan_bf16(const ScanArgs& a, const uint16_t* shadow, const float* bq, hipStream_t st);
 
-// One launch for the tail of a shadow search (rescore_certify_kernel).  Rescore the first min(count, k') approximate keys of
-// each query from the f32 rows (the gemv kernel's arithmetic and epilogue), take the top k by the select's rank sort, write
-// out_keys [b, k] / out_counts [b] as launch_select does, and cert[b] = 1 when that answer is provably the f32 scan's (else
-// the caller re-runs the query on the f32 scan).  cert is written before the kernel ends.
-// akeys [b, k' + 1] / acounts [b]: the select's output; ekeys: [b, k'] scratch.
+// One launch for the tail of a shadow search (rescore_certify_kernel), after the shadow scan `a` describes (launch_scan_bf16 /
+// launch_scan_i8 with these very arguments: a.k = k' + 1, a.rows = the f32 rows).  Select each query's top k' + 1 approximate
+// keys from the scan's scores / gmax / gaux (select_finish_kernel's body, run by every workgroup of the query for itself),
+// rescore the first min(count, k') from the f32 rows (the gemv kernel's arithmetic and epilogue), take the top k by the
+// select's rank sort, write out_keys [b, k] / out_counts [b] as launch_select does, and cert[b] = 1 when that answer is
+// provably the f32 scan's (else the caller re-runs the query on the f32 scan).  cert is written before the kernel ends.
+// Leaves the work-queue heads (a.work) zeroed for the next scan, as launch_select does.  ekeys: [b, k'] scratch.
 // bound: 1 / 2 = compute B_q of the bf16 / int8 copy here (launch_shadow_bound's / launch_i8_bound's bits, from r_max and
 // norm_max) into bq [b]; 0 = bq already holds it (a launch_*_bound earlier on st: PIPELINE searches, whose scan reads it).
 // tickets: device [b], zero on entry (once, at allocation) and left zero: the workgroups of a query count their arrivals
 // there, and the last one certifies.
 // counters, counters2: nullable device [2] each: += certified, += not certified queries of the block (device-API searches,
 // whose outcome the host never sees; the second pair counts what the int8 copy served).
-hipError_t launch_rescore_certify(const float* rows, uint32_t dim, const float* q, uint32_t b, uint32_t k, uint32_t kprime,
-                                  uint32_t mode, float thr, uint32_t row_base, uint32_t bound, double r_max, double norm_max,
-                                  float* bq, uint32_t* tickets, const uint64_t* akeys, const uint32_t* acounts,
-                                  uint64_t* ekeys, uint64_t* out_keys, uint32_t* out_counts, uint32_t* cert,
-                                  unsigned long long* counters, unsigned long long* counters2, hipStream_t st);
+hipError_t launch_rescore_certify(const ScanArgs& a, uint32_t row_base, uint32_t k, uint32_t kprime, uint32_t bound,
+                                  double r_max, double norm_max, float* bq, uint32_t* tickets, uint64_t* ekeys,
+                                  uint64_t* out_keys, uint32_t* out_counts, uint32_t* cert, unsigned long long* counters,
+                                  unsigned long long* counters2, hipStream_t st);
 #endif
 
 }  // namespace cqs

@@ -18,6 +18,7 @@
 #include "launch_util.h"
 #include "rank_sort.h"
 #include "scan_device.h"
+#include "select_device.h"
 
 namespace cqs {
 
@@ -344,14 +345,19 @@ hipError_t launch_scan_bf16(const ScanArgs& a, const uint16_t* shadow, const flo
     }
 }
 
-// ---- rescore + certify ------------------------------------------------------------------------------------------
+// ---- select + rescore + certify ---------------------------------------------------------------------------------
 struct TailParams {
     const float* rows;
     const float* q;
     uint32_t dim, k, kprime, mode, row_base;
     float thr;
-    const uint64_t* akeys;     // [b, k' + 1]  (written by the select, an earlier launch)
-    const uint32_t* acounts;   // [b]
+    const float* scores;       // [b, n_pad]   the shadow scan's output (an earlier launch): approximate scores,
+    const float* gmax;         // [b, n_tasks] task maxima,
+    const uint64_t* gaux;      // nullable [b, n_tasks] (argmax, runner-up)
+    uint32_t n_pad;
+    TaskTiers tiers;
+    uint32_t bins;             // select_body's `linear`
+    uint32_t* work;            // [kWorkWords] the scans' work-queue heads: zeroed here, as the select launch did
     uint64_t* ekeys;           // [b, k']: exact key of candidate i, 0 = dropped by the f32 epilogue.  Handed from the
                                // rescoring waves to the finishing workgroup inside the launch (agent-scope accesses only)
     float* bq;                 // [b] B_q; bound != 0: computed here and handed over like ekeys
@@ -365,9 +371,14 @@ struct TailParams {
     unsigned long long* counters2;  // nullable [2]: the same again (the int8 copy's own counts)
 };
 
-constexpr uint32_t kTailWaves = 16;   // 1024 threads: the block shape rank_sort_keys is written for
+constexpr uint32_t kTailWaves = 16;   // 1024 threads: the block shape select_body and rank_sort_keys are written for
 
-// One launch for a block's tail.  blockIdx.y = query; the query's waves are numbered slot = blockIdx.x * 16 + wave.
+// One launch for a block's tail.  blockIdx.y = query; the query's waves are numbered w = blockIdx.x * 16 + wave and take
+// the slots w, w + #waves, ... of 0 .. min(count, k').
+//  every workgroup  the select of its query for the top k' + 1 approximate keys (select_body on the scan's scores / gmax /
+//                   gaux, as select_finish_kernel runs it): nobody can wait for a select workgroup, so each does the
+//                   select itself.  All of them read the same words an earlier launch wrote and run the same code, so all
+//                   hold the same sorted list and nothing is handed between workgroups before the ticket below.
 //  slot 0           B_q of the query into bq (bound != 0), beside the rescoring waves, off their path.
 //  slot i + 1       candidate i < min(count, k'): its exact f32 score, scan_gemv_kernel's for this (row, query): lane owns
 //                   floats [c*256 + lane*4, +4) of chunk c (clamped address and zero query fragment past a partial last
@@ -376,12 +387,14 @@ constexpr uint32_t kTailWaves = 16;   // 1024 threads: the block shape rank_sort
 //                   sums; IEEE addition commutes) - and that kernel's epilogue.
 //  last workgroup   of the query to arrive certifies: top k of the rescored candidates (the select's rank sort) into
 //                   out_keys / out_counts, and cert = 1 when no row outside them can enter the top k.
+//  workgroup (0, 0) zeroes the work-queue heads for the next scan (visible at the kernel boundary; the scan that advanced
+//                   them is an earlier launch).
 // Nobody waits for anybody: a workgroup adds one to the query's ticket when its waves have stored, and the one whose add
 // returns gridDim.x - 1 knows that every other has.  It puts the ticket back to 0 for the next search.
 // Visibility (per-XCD L2s are not coherent, a CU's L1 is never refreshed): every word handed over (ekeys, bq) is stored
 // write-through by an agent-scope atomic store, each wave drains its stores before the workgroup's barrier, one lane then
 // adds to the ticket, and the finisher reads those words by agent-scope atomic loads only, after the add has returned and a
-// barrier that the adding wave joins.  akeys / acounts come from an earlier launch and are read plainly.
+// barrier that the adding wave joins.  scores / gmax / gaux come from an earlier launch and are read plainly.
 template <int NCH>
 __global__ __launch_bounds__(1024) void rescore_certify_kernel(const TailParams p) {
     __shared__ uint64_t s_keys[kShadowKMax];
@@ -390,22 +403,36 @@ __global__ __launch_bounds__(1024) void rescore_certify_kernel(const TailParams 
     __shared__ uint32_t s_cnt, s_flag, s_last;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t qi = blockIdx.y;
-    const uint32_t slot = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * kTailWaves + (threadIdx.x >> 6)));
-    const uint32_t ac = p.acounts[qi];
-    const uint32_t nc = ac < p.kprime ? ac : p.kprime;
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * kTailWaves + (threadIdx.x >> 6)));
+    const uint32_t n_waves = gridDim.x * kTailWaves;
     const uint32_t dim = p.dim;
     const float* qp = p.q + (size_t)qi * dim;
     if (threadIdx.x == 0) s_cnt = 0u;
-    if (slot == 0u) {
-        if (p.bound != 0u) {
-            const float v = p.bound == 2u ? wave_i8_bound(qp, dim, p.r_max, p.norm_max, lane)
-                                          : wave_shadow_bound(qp, dim, p.r_max, p.norm_max, lane);
-            if (lane == 0u)
-                __hip_atomic_store((uint32_t*)p.bq + qi, __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (qi == 0u && blockIdx.x == 0u)
+        for (uint32_t i = threadIdx.x; i < kWorkWords; i += 1024u) p.work[i] = 0u;
+
+    // the approximate top k' + 1, sorted: what select_finish_kernel wrote to akeys / acounts when it was a launch of its own
+    const uint32_t n_tasks = p.tiers.total();
+    uint32_t found;
+    const uint64_t* akeys = select_body(p.scores + (size_t)qi * p.n_pad, p.gmax + (size_t)qi * n_tasks,
+                                        p.gaux ? p.gaux + (size_t)qi * n_tasks : nullptr, p.n_pad, p.tiers, p.kprime + 1u,
+                                        p.row_base, p.bins, nullptr, found);
+    const uint32_t ac = found < p.kprime + 1u ? found : p.kprime + 1u;
+    const uint32_t nc = ac < p.kprime ? ac : p.kprime;
+    const uint64_t key_next = ac > p.kprime ? akeys[p.kprime] : 0ull;   // the (k' + 1)-th approximate key (the finisher's)
+
+    for (uint32_t slot = wave; slot <= nc; slot += n_waves) {
+        if (slot == 0u) {
+            if (p.bound != 0u) {
+                const float v = p.bound == 2u ? wave_i8_bound(qp, dim, p.r_max, p.norm_max, lane)
+                                              : wave_shadow_bound(qp, dim, p.r_max, p.norm_max, lane);
+                if (lane == 0u)
+                    __hip_atomic_store((uint32_t*)p.bq + qi, __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            continue;
         }
-    } else if (slot - 1u < nc) {
         const uint32_t i = slot - 1u;
-        const uint64_t key = p.akeys[(size_t)qi * (p.kprime + 1u) + i];
+        const uint64_t key = akeys[i];
         const uint32_t grow = 0xFFFFFFFFu - (uint32_t)key;
         const float* rp = p.rows + (size_t)(grow - p.row_base) * dim;
         f4 x[NCH], qv[NCH];
@@ -469,7 +496,7 @@ __global__ __launch_bounds__(1024) void rescore_certify_kernel(const TailParams 
         if (__builtin_fabsf(bq) <= 3.4028234664e38f) {
             if (ac <= p.kprime) ok = true;   // (a) every row the approximate rules keep was rescored
             else if (m >= k) {               // (b) every outsider j: s_j <= s~_j + B_q <= s~_(k'+1) + B_q < s_(k)
-                float t = key_score(p.akeys[(size_t)qi * (p.kprime + 1u) + p.kprime]) + bq;
+                float t = key_score(key_next) + bq;
                 if (p.mode == 1u) t = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);
                 ok = t < key_score(s_sorted[k - 1u]);
             }
@@ -480,17 +507,29 @@ __global__ __launch_bounds__(1024) void rescore_certify_kernel(const TailParams 
     }
 }
 
-hipError_t launch_rescore_certify(const float* rows, uint32_t dim, const float* q, uint32_t b, uint32_t k, uint32_t kprime,
-                                  uint32_t mode, float thr, uint32_t row_base, uint32_t bound, double r_max, double norm_max,
-                                  float* bq, uint32_t* tickets, const uint64_t* akeys, const uint32_t* acounts,
-                                  uint64_t* ekeys, uint64_t* out_keys, uint32_t* out_counts, uint32_t* cert,
-                                  unsigned long long* counters, unsigned long long* counters2, hipStream_t st) {
+#ifndef CQS_TAIL_MAX_BLOCKS_PER_CU
+#define CQS_TAIL_MAX_BLOCKS_PER_CU 1u   // the select's LDS leaves room for one workgroup per CU: the grid stays one round
+#endif
+
+hipError_t launch_rescore_certify(const ScanArgs& a, uint32_t row_base, uint32_t k, uint32_t kprime, uint32_t bound,
+                                  double r_max, double norm_max, float* bq, uint32_t* tickets, uint64_t* ekeys,
+                                  uint64_t* out_keys, uint32_t* out_counts, uint32_t* cert, unsigned long long* counters,
+                                  unsigned long long* counters2, hipStream_t st) {
+    const uint32_t b = a.b, dim = a.dim;
     if (b == 0) return hipSuccess;
-    if (b > kShadowMaxQ || k == 0 || kprime < k || kprime >= kShadowKMax || dim % 8u != 0u || dim > kShadowMaxDim || bound > 2u)
+    if (b > kShadowMaxQ || k == 0 || kprime < k || kprime >= kShadowKMax || a.k != kprime + 1u || dim % 8u != 0u ||
+        dim > kShadowMaxDim || bound > 2u)
         return hipErrorInvalidValue;
-    const TailParams tp{rows, q, dim, k, kprime, mode, row_base, thr, akeys, acounts, ekeys, bq, tickets, bound, r_max, norm_max,
+    const TailParams tp{a.rows, a.q, dim, k, kprime, a.mode, row_base, a.threshold, a.scores, a.gmax, a.gaux, a.n_pad, a.tiers,
+                        a.range_bins ? 2u : (a.linear_bins ? 1u : 0u), a.work, ekeys, bq, tickets, bound, r_max, norm_max,
                         out_keys, out_counts, cert, counters, counters2};
-    const dim3 grid((kprime + 1u + kTailWaves - 1u) / kTailWaves, b), block(64u * kTailWaves);   // (slot 0 + k' candidates)
+    // One wave per slot (B_q + k' candidates) while the block's workgroups fit the device in one round; beyond that
+    // (b * ceil((k' + 1) / 16) > CUs: from b = 4 at k = 500) fewer workgroups whose waves take several slots each, because
+    // every workgroup repeats the select's front end and a second round would repeat it behind the first.
+    const uint32_t want = (kprime + 1u + kTailWaves - 1u) / kTailWaves;
+    uint32_t cap = a.n_cu * CQS_TAIL_MAX_BLOCKS_PER_CU / b;
+    if (cap < 1u) cap = 1u;
+    const dim3 grid(want < cap ? want : cap, b), block(64u * kTailWaves);
     switch ((dim + 255u) / 256u) {
         case 1: hipLaunchKernelGGL(rescore_certify_kernel<1>, grid, block, 0, st, tp); break;
         case 2: hipLaunchKernelGGL(rescore_certify_kernel<2>, grid, block, 0, st, tp); break;

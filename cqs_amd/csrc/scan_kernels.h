@@ -16,7 +16,7 @@ constexpr uint32_t kMaxK = 1024;
 constexpr uint32_t kMaxGemvQ = 8;         // queries per HBM-streaming scan pass
 constexpr uint32_t kDbgWaves = 4096;      // per-wave start/end stamps kept by the scan when ScanArgs.dbg is set
 constexpr uint32_t kWorkWords = 64;       // work-queue heads (one per scan launch of a search); zero on entry,
-                                          // re-zeroed by select_finish
+                                          // re-zeroed by select_finish (a shadow search: by its tail kernel)
 
 // Work-queue tasks in row order: nA tasks of 64 rows, then nB of 32, then nC of 16 (64 nA + 32 nB +
 // 16 nC = n_pad).  One task = one wave's unit of work = one group of the select's maxima index.
@@ -61,7 +61,8 @@ struct ScanArgs {
                             // per-wave start/end stamps (CQS_HIP_DEBUG_STAMPS=1)
     const uint32_t* gate = nullptr;  // nullable device [b] (gemv passes, b <= 64): every workgroup of the gemv scan and of
                             // the select reads gate[0, b) at entry and returns at once when all are 1 (the bf16 shadow has
-                            // certified every query of the block; see gate_closed)
+                            // certified every query of the block; see gate_closed).  A gated scan is launched on the
+                            // persistent grid where that has fewer workgroups than one per task (launch_gemv)
 };
 
 // scores[q][row] = dot(rows[row], q) (+ mode / bitset / non-finite handling; dropped
@@ -90,10 +91,13 @@ bool scan_dim_supported(uint32_t dim);
 //  - the gemv scan and the select decide the same way from the same words (this function, at entry, in every wave;
 //    the words were written by an earlier kernel of the stream - the last workgroup of the shadow's tail kernel, before
 //    that kernel ended - and do not change during the launch);
-//  - a skipped scan never touches the work-queue heads: the shadow pass's select has re-zeroed them already, and the
-//    skipped select has nothing to re-zero;
-//  - the launches between the shadow's tail kernel (rescore_certify_kernel) and the gated select include no memset (gemv blocks of <= 32 queries stay
-//    under kWorkWords launches); a memset added there must be gated too.
+//  - a skipped scan never touches the work-queue heads, and the skipped select has nothing to re-zero: the shadow's tail
+//    kernel (rescore_certify_kernel, which contains the shadow pass's select) has zeroed them already - exactly one of its
+//    workgroups, (0, 0), after the shadow scan that advanced them has ended and before the gated scan can start (kernel
+//    boundaries on one stream either side).  A gated scan runs on the persistent grid (launch_gemv) and does dequeue from
+//    them when its gate is open; the gated select that follows then re-zeroes them;
+//  - the launches between the shadow's tail kernel and the gated select include no memset (gemv blocks of <= 32 queries
+//    stay under kWorkWords launches); a memset added there must be gated too.
 __device__ __forceinline__ bool gate_closed(const uint32_t* gate, uint32_t b) {
     uint32_t all = 1u;
     for (uint32_t i = 0; i < b; ++i) all &= gate[i];   // (uniform: scalar loads, no vector registers at entry)

@@ -21,8 +21,8 @@
 // Wave = 64 lanes.  gfx950 only.
 #include "scan_kernels.h"
 #include "launch_util.h"
-#include "rank_sort.h"
 #include "scan_device.h"
+#include "select_device.h"
 
 namespace cqs {
 
@@ -30,82 +30,6 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(1))) uint32_t gu32;
 
-// Histogram bin of a valid score; monotone non-decreasing in the score.
-// linear: 4096 bins of width 2^-11 over [-1,1] (cosine / clamped scores: fine
-// resolution exactly where the top-k threshold lives); else the top 12 bits of
-// the ordered key (log-spaced, any range: raw dot products).
-__device__ __forceinline__ uint32_t bin_of(float s, bool linear) {
-    if (linear) {
-        const float t = (s + 1.0f) * 2048.0f;
-        const int b = (int)t;  // t >= 0 for s >= -1; negatives truncate toward 0 and clamp below
-        return (uint32_t)(b < 0 ? 0 : (b > 4095 ? 4095 : b));
-    }
-    return okey(s) >> 20;
-}
-// Third form (select mode 2, the sparse index): linear bins over the range the GROUP MAXIMA of this very row span - sums of
-// SPLADE products crowd into two or three octaves, where the log-spaced bins above put thousands of groups into the
-// threshold bin.  Any monotone map is correct (the candidates are re-ranked on their full keys); this one is sharp where
-// the top-k lives.  Scores below `lo` fall into bin 0.
-__device__ __forceinline__ uint32_t bin_of_range(float s, float lo, float scale) {
-    if (!(scale > 0.f)) return 0u;                        // degenerate range: one bin
-    const float t = (s - lo) * scale;
-    if (!(t < 4095.0f)) return 4095u;                     // (also an overflowed difference)
-    return t > 0.f ? (uint32_t)(int)t : 0u;
-}
-__device__ __forceinline__ uint32_t bin_any(float s, uint32_t mode, float lo, float scale) {
-    return mode == 2u ? bin_of_range(s, lo, scale) : bin_of(s, mode != 0u);
-}
-
-// ---- block-wide "find the bin holding the k-th largest" ---------------------
-// hist: kHistBins counters (global or LDS).  Finds T = the highest bin such
-// that count(bins >= T) >= k_rem.  res[0]=T res[1]=count(bins > T) res[2]=hist[T]
-// res[3]=total count.  If total < k_rem: T = 0, res[1] = total - hist[0].
-template <int THREADS>
-__device__ void block_decide(const uint32_t* hist, uint32_t k_rem, uint32_t* s_part /*>= THREADS/64*/,
-                             uint32_t* res /*4, LDS*/) {
-    constexpr int BPT = kHistBins / THREADS;
-    constexpr int NW = THREADS / 64;
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    uint32_t h[BPT];
-    uint32_t sum = 0;
-#pragma unroll
-    for (int i = 0; i < BPT; ++i) {
-        h[i] = hist[t * BPT + i];
-        sum += h[i];
-    }
-    // inclusive suffix scan over threads (thread THREADS-1 owns the top bins):
-    // shuffles inside a wave, then the totals of the higher waves through LDS
-    uint32_t incl = sum;
-#pragma unroll
-    for (int off = 1; off < 64; off <<= 1) {
-        const uint32_t v = __shfl_down(incl, off, 64);
-        if (lane + off < 64) incl += v;
-    }
-    if (lane == 0) s_part[w] = incl;
-    __syncthreads();
-    for (int ww = w + 1; ww < NW; ++ww) incl += s_part[ww];
-    uint32_t above = incl - sum;  // count in bins owned by higher threads
-    if (t == 0) {
-        res[3] = incl;
-        if (incl < k_rem) {  // fewer entries than requested: take them all
-            res[0] = 0;
-            res[1] = incl - h[0];
-            res[2] = h[0];
-        }
-    }
-    if (above < k_rem && incl >= k_rem) {  // exactly one thread
-#pragma unroll
-        for (int i = BPT - 1; i >= 0; --i) {
-            if (above < k_rem && above + h[i] >= k_rem) {
-                res[0] = (uint32_t)(t * BPT + i);
-                res[1] = above;
-                res[2] = h[i];
-            }
-            above += h[i];
-        }
-    }
-    __syncthreads();
-}
 
 // ---- scan ------------------------------------------------------------------
 struct ScanParams {
@@ -335,67 +259,7 @@ __global__ __launch_bounds__(256, OCC) void scan_gemv_kernel(const ScanParams p)
     if (p.dbg && lane == 0 && wave_id < kDbgWaves) p.dbg[17u + 2u * wave_id] = __builtin_amdgcn_s_memrealtime();
 }
 
-// ---- one-block exact select (fallback for heavy ties / crowded bins) --------
-// Radix select on the full 64-bit packed key (score bits then row bits: all
-// keys distinct), 12-bit digits, streaming the whole score row per pass.
-// Leaves <= kCandCap candidates in s_keys and returns their count.
-__device__ uint32_t slow_select(const float* __restrict__ s, uint32_t n_pad, uint32_t k, uint32_t row_base,
-                                uint64_t* s_keys, uint32_t* s_hist, uint32_t* s_part, uint32_t* s_res,
-                                uint32_t* s_cnt) {
-    uint64_t prefix = 0;  // digits decided so far (top bits of the key)
-    int bits_done = 0;
-    uint32_t k_rem = k, sel_above = 0;
-    uint64_t lb = 0;
-    while (bits_done < 64) {
-        const int w = (64 - bits_done) >= 12 ? 12 : (64 - bits_done);
-        for (int i = threadIdx.x; i < (int)kHistBins; i += 1024) s_hist[i] = 0;
-        __syncthreads();
-        for (uint32_t i = threadIdx.x; i < n_pad; i += 1024u) {
-            const uint32_t kk = okey(s[i]);
-            if (kk <= kInvalidKey) continue;
-            const uint64_t key = pack_key(kk, row_base + i);
-            if (bits_done == 0 || (key >> (64 - bits_done)) == prefix)
-                atomicAdd(&s_hist[(uint32_t)(key >> (64 - bits_done - w)) & ((1u << w) - 1u)], 1u);
-        }
-        __syncthreads();
-        block_decide<1024>(s_hist, k_rem, s_part, s_res);
-        const uint32_t T = s_res[0], above = s_res[1], cnt = s_res[2], total = s_res[3];
-        __syncthreads();
-        if (bits_done == 0 && total <= k) { lb = 0; break; }
-        prefix = (prefix << w) | T;
-        bits_done += w;
-        sel_above += above;
-        k_rem -= above;
-        lb = prefix << (64 - bits_done);
-        if (sel_above + cnt <= kCandCap) break;
-    }
-    if (threadIdx.x == 0) *s_cnt = 0;
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < n_pad; i += 1024u) {
-        const uint32_t kk = okey(s[i]);
-        if (kk <= kInvalidKey) continue;
-        const uint64_t key = pack_key(kk, row_base + i);
-        if (key >= lb) {
-            const uint32_t slot = atomicAdd(s_cnt, 1u);
-            if (slot < kCandCap) s_keys[slot] = key;
-        }
-    }
-    __syncthreads();
-    const uint32_t c = *s_cnt;
-    return c < kCandCap ? c : kCandCap;
-}
-
-// ---- select: one workgroup per query -----------------------------------------
-// Two-level exact top-k.  The scan left (a) every score and (b) the maximum of each
-// 64-row group.  The workgroup histograms the group maxima (LDS), takes T = the highest
-// bin with at least k maxima at or above it - then at least k scores have bin >= T, so
-// every top-k entry has bin >= T and lives in a group whose maximum has bin >= T - reads
-// back only those groups (about k of them), and sorts their entries with bin >= T
-// (bitonic, packed keys).  Global loads are issued GB per thread at a time so the phases
-// are bandwidth- not latency-paced.
-constexpr uint32_t kGroupCap = 8192;
-constexpr int kGB = 16;  // independent loads in flight per thread
-
+// ---- select: one workgroup per query (the body: select_device.h) ---------------
 __global__ __launch_bounds__(1024) void select_finish_kernel(const float* __restrict__ scores,
                                                              const float* __restrict__ gmax,
                                                              const uint64_t* __restrict__ gaux, uint32_t n_pad,
@@ -407,243 +271,18 @@ __global__ __launch_bounds__(1024) void select_finish_kernel(const float* __rest
                                                              unsigned long long* __restrict__ dbg,
                                                              const uint32_t* __restrict__ gate, uint32_t gate_n) {
     if (gate && gate_closed(gate, gate_n)) return;   // (same words, same decision as the gated scan; before any barrier)
-    __shared__ uint64_t s_keys[kCandCap];
-    __shared__ uint32_t s_groups[kGroupCap];
-    __shared__ __attribute__((aligned(16))) uint32_t s_hist[kHistBins];
-    __shared__ uint32_t s_part[1024];
-    __shared__ uint32_t s_res[4];
-    __shared__ uint32_t s_cnt, s_ng, s_ng2;
     const uint32_t qi = blockIdx.x;
     const uint32_t n_tasks = tiers.total();
-    const float* s = scores + (size_t)qi * n_pad;
-    const float* gm = gmax + (size_t)qi * n_tasks;
-    const int lane = threadIdx.x & 63;
-    float r_lo = 0.f, r_scale = 0.f;                       // mode 2: the bins' range (see bin_of_range)
-
-#define CQS_STAMP(i) do { if (dbg && threadIdx.x == 0 && blockIdx.x == 0) dbg[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
-    CQS_STAMP(0);
-    for (uint32_t i = threadIdx.x; i < kHistBins; i += 1024u) s_hist[i] = 0u;
-    if (threadIdx.x == 0) { s_cnt = 0; s_ng = 0; s_ng2 = 0; }
-    __syncthreads();
-    if (linear == 2u) {                                    // phase 0: smallest and largest finite group maximum
-        float lo = INFINITY, hi = -INFINITY;
-        for (uint32_t t0 = 0; t0 < n_tasks; t0 += 1024u * kGB) {   // kGB unconditional loads in flight (a conditional one per trip waited for each)
-            float v[kGB];
-#pragma unroll
-            for (int u = 0; u < kGB; ++u) {
-                const uint32_t t = t0 + (uint32_t)u * 1024u + threadIdx.x;
-                v[u] = gm[t < n_tasks ? t : n_tasks - 1u];
-            }
-#pragma unroll
-            for (int u = 0; u < kGB; ++u)
-                if (v[u] != -INFINITY) { lo = fminf(lo, v[u]); hi = fmaxf(hi, v[u]); }   // (a clamped repeat of the last group changes neither)
-        }
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) {
-            lo = fminf(lo, __shfl_xor(lo, off, 64));
-            hi = fmaxf(hi, __shfl_xor(hi, off, 64));
-        }
-        float* const f_part = reinterpret_cast<float*>(s_part);
-        if (lane == 0) { f_part[threadIdx.x >> 6] = lo; f_part[16 + (threadIdx.x >> 6)] = hi; }
-        __syncthreads();
-        lo = f_part[0]; hi = f_part[16];
-        for (int w = 1; w < 16; ++w) { lo = fminf(lo, f_part[w]); hi = fmaxf(hi, f_part[16 + w]); }
-        __syncthreads();                                   // s_part is reused by block_decide
-        r_lo = lo;
-        r_scale = (hi > lo) ? 4096.0f / (hi - lo) : 0.f;   // (no finite maximum at all: nothing is histogrammed below)
-        if (!(r_scale < INFINITY)) r_scale = 0.f;          // a range narrower than 4096 ulps of a subnormal: one bin, the exact path sorts it out
-    }
-
-    // phase 1: histogram of the group maxima
-    float m[kGB];
-    const bool one_pass = n_tasks <= 1024u * kGB;  // the maxima then stay in registers for phase 2
-    for (uint32_t t0 = 0; t0 < n_tasks; t0 += 1024u * kGB) {
-#pragma unroll
-        for (int u = 0; u < kGB; ++u) {
-            const uint32_t t = t0 + (uint32_t)u * 1024u + threadIdx.x;
-            const float v = gm[t < n_tasks ? t : n_tasks - 1u];  // unconditional load, clamped
-            m[u] = t < n_tasks ? v : -INFINITY;
-        }
-#pragma unroll
-        for (int u = 0; u < kGB; ++u)
-            if (m[u] != -INFINITY) atomicAdd(&s_hist[bin_any(m[u], linear, r_lo, r_scale)], 1u);
-    }
-    __syncthreads();
-    CQS_STAMP(1);
-    block_decide<1024>(s_hist, k, s_part, s_res);
-    const uint32_t T = (s_res[3] < k) ? 0u : s_res[0];  // fewer groups than k: every valid score is a candidate
-    __syncthreads();
-    CQS_STAMP(2);
-
-    // phase 2: groups whose maximum reaches the threshold bin
-    for (uint32_t t0 = 0; t0 < n_tasks; t0 += 1024u * kGB) {
-        if (!one_pass) {
-#pragma unroll
-            for (int u = 0; u < kGB; ++u) {
-                const uint32_t t = t0 + (uint32_t)u * 1024u + threadIdx.x;
-                const float v = gm[t < n_tasks ? t : n_tasks - 1u];
-                m[u] = t < n_tasks ? v : -INFINITY;
-            }
-        }
-        // list positions by ballot + mbcnt, one LDS atomic per wave (round 5; until then a 6-step shuffle scan over 16 flags)
-        bool take[kGB];
-        uint64_t mk[kGB];
-        uint32_t pre[kGB], tot = 0;
-#pragma unroll
-        for (int u = 0; u < kGB; ++u) {
-            take[u] = (m[u] != -INFINITY) && (bin_any(m[u], linear, r_lo, r_scale) >= T);
-            mk[u] = __ballot(take[u]);
-            pre[u] = tot;
-            tot += (uint32_t)__popcll(mk[u]);
-        }
-        uint32_t base = 0;
-        if (tot) {                                       // wave-uniform
-            if (lane == 0) base = atomicAdd(&s_ng, tot);
-            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-        }
-#pragma unroll
-        for (int u = 0; u < kGB; ++u) {
-            const uint32_t slot = base + pre[u] + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk[u] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk[u], 0u));
-            if (take[u] && slot < kGroupCap) s_groups[slot] = t0 + (uint32_t)u * 1024u + threadIdx.x;
-        }
-    }
-    __syncthreads();
-    CQS_STAMP(3);
-    const uint32_t ng = s_ng;
-    uint32_t count = kCandCap + 1u;
-    if (ng <= kGroupCap) {
-        // phase 3: their scores (L2 / Infinity Cache hits: the scan just wrote them).  Round 5: ONE WAVE PER GROUP -
-        // lane <-> row of the group, so a group is one coalesced load at a wave-uniform base (no per-element
-        // slot -> (group, offset) arithmetic), kGU groups in flight per wave, and the survivors are appended with
-        // ballot + mbcnt ranks and ONE LDS atomic per kGU groups.  (Round 4 spread group x slot over all threads:
-        // 2 rounds of 16 loads per thread with a 6-step shuffle scan each - 11 us of one CU's issue slots at k = 500.)
-        // Round 5, producers that also left `gaux` (the gemv scan, the sparse index): a selected group whose runner-up
-        // misses the threshold bin IS its maximum - the candidate (gm, base + arg) goes straight to the list and the
-        // group's rows are never read; only groups with a second entry at or above the threshold (a few per cent at
-        // k = 500, all of them under heavy ties) are gathered.
-        const uint32_t* glist = s_groups;
-        uint32_t n2 = ng;
-        if (gaux) {
-            uint32_t* const s_list2 = s_hist;              // the histogram is dead (T lives in a register)
-            const uint64_t* const ga = gaux + (size_t)qi * n_tasks;
-            for (uint32_t i0 = 0; i0 < ng; i0 += 1024u) {
-                const uint32_t i = i0 + threadIdx.x;
-                const bool valid = i < ng;
-                const uint32_t t = s_groups[valid ? i : ng - 1u];
-                const uint64_t ax = ga[t];
-                const float mx = gm[t];
-                const float sec = __uint_as_float((uint32_t)ax);
-                const bool need = valid && (sec != -INFINITY) && (bin_any(sec, linear, r_lo, r_scale) >= T);
-                const bool direct = valid && !need;
-                const uint64_t mn = __ballot(need), md = __ballot(direct);
-                uint32_t bn = 0, bd = 0;
-                if (lane == 0) {
-                    if (mn) bn = atomicAdd(&s_ng2, (uint32_t)__popcll(mn));
-                    if (md) bd = atomicAdd(&s_cnt, (uint32_t)__popcll(md));
-                }
-                bn = (uint32_t)__builtin_amdgcn_readfirstlane((int)bn);
-                bd = (uint32_t)__builtin_amdgcn_readfirstlane((int)bd);
-                if (need) {
-                    const uint32_t slot = bn + __builtin_amdgcn_mbcnt_hi((uint32_t)(mn >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mn, 0u));
-                    if (slot < kHistBins) s_list2[slot] = t;
-                }
-                if (direct) {
-                    const uint32_t slot = bd + __builtin_amdgcn_mbcnt_hi((uint32_t)(md >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)md, 0u));
-                    uint32_t grows;
-                    const uint32_t gbase = tiers.locate(t, grows);
-                    if (slot < kCandCap) s_keys[slot] = pack_key(okey(mx), row_base + gbase + (uint32_t)(ax >> 32));
-                }
-            }
-            __syncthreads();
-            if (s_ng2 <= kHistBins) { glist = s_list2; n2 = s_ng2; }
-            else {                                         // more groups to read than the second list holds: read them all
-                __syncthreads();
-                if (threadIdx.x == 0) s_cnt = 0;
-                __syncthreads();
-            }
-        }
-        constexpr int kGU = 8;
-        const uint32_t wv = threadIdx.x >> 6;
-        for (uint32_t g0 = wv * kGU; g0 < n2; g0 += 16u * kGU) {
-            float v[kGU];
-            uint32_t idx[kGU];
-            bool in[kGU];
-#pragma unroll
-            for (int u = 0; u < kGU; ++u) {
-                const uint32_t g = g0 + (uint32_t)u;
-                uint32_t grows;
-                const uint32_t gbase = tiers.locate((uint32_t)__builtin_amdgcn_readfirstlane((int)glist[g < n2 ? g : n2 - 1u]), grows);
-                in[u] = g < n2 && (uint32_t)lane < grows;
-                idx[u] = gbase + (in[u] ? (uint32_t)lane : 0u);
-            }
-#pragma unroll
-            for (int u = 0; u < kGU; ++u) v[u] = s[idx[u]];
-            uint64_t mask[kGU];
-            uint32_t pre[kGU], tot = 0;
-            bool take[kGU];
-#pragma unroll
-            for (int u = 0; u < kGU; ++u) {
-                take[u] = in[u] && (v[u] != -INFINITY) && (bin_any(v[u], linear, r_lo, r_scale) >= T);
-                mask[u] = __ballot(take[u]);
-                pre[u] = tot;
-                tot += (uint32_t)__popcll(mask[u]);
-            }
-            uint32_t base = 0;
-            if (tot) {                                   // wave-uniform
-                if (lane == 0) base = atomicAdd(&s_cnt, tot);
-                base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-            }
-#pragma unroll
-            for (int u = 0; u < kGU; ++u) {
-                const uint32_t slot = base + pre[u] +
-                    __builtin_amdgcn_mbcnt_hi((uint32_t)(mask[u] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask[u], 0u));
-                if (take[u] && slot < kCandCap) s_keys[slot] = pack_key(okey(v[u]), row_base + idx[u]);
-            }
-        }
-        __syncthreads();
-        count = s_cnt;
-    }
-    if (count > kCandCap)  // heavy ties / crowded threshold bin: exact radix select over the whole row
-        count = slow_select(s, n_pad, k, row_base, s_keys, s_hist, s_part, s_res, &s_cnt);
-
-    CQS_STAMP(4);
-    if (dbg && threadIdx.x == 0 && blockIdx.x == 0) { dbg[8] = ng; dbg[9] = count; }
-    const uint64_t* sorted = s_keys;
-    if (count <= 1024u) {
-        uint64_t* s_sorted = reinterpret_cast<uint64_t*>(s_groups);  // group list is dead by now
-        uint32_t* s_ok = s_hist;                                      // histogram is dead by now (slow_select included)
-        rank_sort_keys(s_keys, count, s_sorted, s_ok, s_res);         // (rank_sort.h, shared with the bf16 certify kernel)
-        sorted = s_sorted;
-    } else {
-        // Bitonic sort, descending (slow path sizes: up to kCandCap).
-        uint32_t P = 2048;
-        while (P < count) P <<= 1;
-        for (uint32_t i = count + threadIdx.x; i < P; i += 1024u) s_keys[i] = 0ull;
-        __syncthreads();
-        for (uint32_t size = 2; size <= P; size <<= 1) {
-            for (uint32_t stride = size >> 1; stride > 0; stride >>= 1) {
-                for (uint32_t t = threadIdx.x; t < P / 2; t += 1024u) {
-                    const uint32_t i = 2u * t - (t & (stride - 1u));  // lower index of the pair
-                    const uint32_t j = i + stride;
-                    const uint64_t a = s_keys[i], b = s_keys[j];
-                    const bool desc = ((i & size) == 0u);
-                    if ((a < b) == desc) {
-                        s_keys[i] = b;
-                        s_keys[j] = a;
-                    }
-                }
-                __syncthreads();
-            }
-        }
-    }
-    CQS_STAMP(5);
+    uint32_t count;
+    const uint64_t* sorted = select_body(scores + (size_t)qi * n_pad, gmax + (size_t)qi * n_tasks,
+                                         gaux ? gaux + (size_t)qi * n_tasks : nullptr, n_pad, tiers, k, row_base, linear, dbg,
+                                         count);
     const uint32_t outc = count < k ? count : k;
     for (uint32_t i = threadIdx.x; i < k; i += 1024u) out_keys[(size_t)qi * k + i] = (i < outc) ? sorted[i] : 0ull;
     if (threadIdx.x == 0) out_counts[qi] = outc;
     // re-arm the scan work-queue heads for the next search (visible at the kernel boundary)
     if (qi == 0) for (uint32_t i = threadIdx.x; i < kWorkWords; i += 1024u) work[i] = 0u;
-    CQS_STAMP(6);
-#undef CQS_STAMP
+    if (dbg && threadIdx.x == 0 && blockIdx.x == 0) dbg[6] = __builtin_amdgcn_s_memrealtime();
 }
 
 // ---- launchers -------------------------------------------------------------
@@ -715,13 +354,15 @@ static hipError_t launch_gemv(const ScanArgs& a, uint32_t q0, uint32_t nq, uint3
     // ~1.5M rows) or, for huge corpora, a persistent grid that continues from the work queue (beats the
     // one-shot grid by 3 % at 10M rows).
     const bool small = a.tiers.nA == 0u && a.tiers.nB == 0u;  // 16-row tasks only
-    const bool one_shot = p.n_tasks <= a.n_cu * 4u * CQS_SCAN_ONE_SHOT;
-    uint32_t wpb = 4u, blocks = a.n_cu * CQS_SCAN_BLOCKS_PER_CU;
-    if (one_shot) {
-        wpb = small ? CQS_SCAN_BLOCK_WAVES_SMALL : CQS_SCAN_BLOCK_WAVES;
-        blocks = (p.n_tasks + wpb - 1u) / wpb;
-    }
-    if (!one_shot && PIPE == 1 && CQS_SCAN_CAP_OCCUPANCY) blocks = a.n_cu;  // (one resident workgroup per CU, see below)
+    // A gated launch (the f32 fallback behind a certified shadow search) finds its gate closed in almost every search, and
+    // then costs what it takes to dispatch its workgroups: it takes the persistent grid wherever that is the smaller one
+    // (1M rows: 256 workgroups instead of 7.8k; an open gate pays the ~4 % the one-shot grid wins at that size).
+    const uint32_t wpb1 = small ? CQS_SCAN_BLOCK_WAVES_SMALL : CQS_SCAN_BLOCK_WAVES;
+    const uint32_t blocks1 = (p.n_tasks + wpb1 - 1u) / wpb1;
+    const uint32_t blocks_p = (PIPE == 1 && CQS_SCAN_CAP_OCCUPANCY) ? a.n_cu   // (one resident workgroup per CU, see below)
+                                                                    : a.n_cu * CQS_SCAN_BLOCKS_PER_CU;
+    const bool one_shot = p.n_tasks <= a.n_cu * 4u * CQS_SCAN_ONE_SHOT && !(a.gate && blocks1 > blocks_p);
+    const uint32_t wpb = one_shot ? wpb1 : 4u, blocks = one_shot ? blocks1 : blocks_p;
     const dim3 grid(blocks), block(64u * wpb);
     // Streaming a corpus far larger than the caches runs best with ONE wave per SIMD (each with two
     // 8-row batches in flight): a second wave per SIMD costs 2-3 % of the HBM rate (DRAM page
