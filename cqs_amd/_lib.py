@@ -133,6 +133,12 @@ SIGNATURES = [
     ("cqs_hip_sparse_index_last_error", C.c_size_t, [_c_idx, C.c_char_p, C.c_size_t]),
 ]
 
+# Test hooks the library exports beside the header's symbols (embedder.hip; not part of include/cqs_hip.h).
+DEBUG_SIGNATURES = [
+    ("cqs_hip_debug_embedder_query_state", C.c_int32,
+     [_c_idx, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _pp(C.c_int32)]),
+]
+
 BERT_HEAD_MLM = 0
 BERT_HEAD_CLASSIFIER = 1
 BERT_HEAD_NONE = 2
@@ -181,7 +187,7 @@ def load() -> C.CDLL:
         except Exception:
             pass
     lib = C.CDLL(LIB_PATH)
-    for name, res, args in SIGNATURES:
+    for name, res, args in SIGNATURES + DEBUG_SIGNATURES:
         fn = getattr(lib, name)  # AttributeError if the header and the library disagree
         fn.restype = res
         fn.argtypes = args

@@ -1125,6 +1125,38 @@ uint64_t cqs_hip_debug_query_stamps(cqs_hip_embedder* e, uint32_t ctx, unsigned 
     return words;
 } CQS_ABI_CATCH_VAL(0)
 
+// Test hook (not part of the public header): what the search-time chain left in context `ctx`'s scratch - the state a
+// query's sentence vector is pooled from and that never leaves the device otherwise.  Call it after a blocking query of
+// T tokens on that context.  Waits for the context's stream, then copies out the first T rows of
+//   x    f32  [T, hidden]   the residual stream entering the head (q_x0 or q_x1; *which_x says which: 0 or 1),
+//   y    bf16 [T, hidden]   the last layer's down projection (the head adds rms(y, post_ffw) to x itself),
+//   qkv  bf16 [T, (heads + 2 kv_heads) * 256] and h bf16 [T, intermediate] of the last layer,
+// and d1 bf16 [dense_hidden], the Dense 1 output.  Any pointer may be NULL.  Only reads: launches nothing, writes no device
+// memory, so the scratch stays as the query left it.
+int32_t cqs_hip_debug_embedder_query_state(cqs_hip_embedder* e, uint32_t ctx, uint32_t T, float* x, uint16_t* y, uint16_t* qkv,
+                                           uint16_t* h, uint16_t* d1, int32_t* which_x) CQS_ABI_TRY {
+    if (!e || ctx >= (uint32_t)cqs_hip_embedder::kCtx) return CQS_HIP_ERR_INVALID;
+    std::lock_guard<std::mutex> lk(e->mu);
+    Ctx& c = e->ctx[ctx];
+    if (!e->finalized || !e->query_path || !c.q_meta) return efail(e, CQS_HIP_ERR_INVALID, "query_state: no search-time query has run on this context");
+    if (T < 1u || T > e->query_max_tokens) return efail(e, CQS_HIP_ERR_INVALID, "query_state: T outside the search-time chain's lengths");
+    const cqs::EmbedGeom& g = e->g;
+    // launch_query_forward's buffer walk: layer 0 gathers into x0 and its GeGLU prologue moves on to x1; every later layer
+    // moves twice (QKV prologue, GeGLU prologue) - the head reads the buffer the last GeGLU prologue wrote
+    int cur = 0;
+    for (uint32_t l = 0; l < g.layers; ++l) cur ^= (l == 0 ? 1 : 0);
+    E_TRY(e, hipSetDevice(e->device));
+    E_TRY(e, hipStreamSynchronize(c.stream));
+    const size_t H = g.hidden;
+    if (x) E_TRY(e, hipMemcpy(x, cur ? c.q_x1 : c.q_x0, (size_t)T * H * sizeof(float), hipMemcpyDeviceToHost));
+    if (y) E_TRY(e, hipMemcpy(y, c.q_y, (size_t)T * H * sizeof(bf16_t), hipMemcpyDeviceToHost));
+    if (qkv) E_TRY(e, hipMemcpy(qkv, c.q_qkv, (size_t)T * nqkv(g) * sizeof(bf16_t), hipMemcpyDeviceToHost));
+    if (h) E_TRY(e, hipMemcpy(h, c.q_h, (size_t)T * g.inter * sizeof(bf16_t), hipMemcpyDeviceToHost));
+    if (d1) E_TRY(e, hipMemcpy(d1, c.q_d1, (size_t)g.dense_hidden * sizeof(bf16_t), hipMemcpyDeviceToHost));
+    if (which_x) *which_x = cur;
+    return CQS_HIP_OK;
+} CQS_ABI_CATCH(e)
+
 // Test / tuning aid (not part of the public header): one GEMM launch on caller-provided device buffers
 // (bf16 A [M,K], bf16 W [N,K], C per out_kind) on `stream`; the kernel is chosen like in the forward
 // (CQS_HIP_GEMM_TILE forces one).

@@ -63,6 +63,11 @@ def pad_2d_i64(rows: Sequence[Sequence[int]], max_len: int, pad_value: int) -> n
     return arr
 
 
+def bf16_to_f32(bits: np.ndarray) -> np.ndarray:
+    """bf16 bit patterns (uint16) -> f32, exactly."""
+    return (np.ascontiguousarray(bits, dtype=np.uint16).astype(np.uint32) << np.uint32(16)).view(np.float32)
+
+
 def default_config() -> _lib.EmbedConfig:
     cfg = _lib.EmbedConfig()
     _lib.load().cqs_hip_embed_config_default(C.byref(cfg))
@@ -196,6 +201,25 @@ class HipEmbedEngine:
                                             ids.shape[0], ids.shape[1], out.ctypes.data_as(C.c_void_p))
         if rc != _lib.OK:
             raise EmbedderError(f"InferenceFailed: {self.last_error()} ({rc})")
+        return out
+
+    def debug_query_state(self, tokens: int, ctx: int = 0) -> dict:
+        """Test hook `cqs_hip_debug_embedder_query_state`: what the search-time chain left on the device after a
+        blocking query of `tokens` tokens (a blocking call runs on context 0).  -> {"x": f32 [T, hidden] residual
+        stream entering the head, "which_x": 0 | 1 (q_x0 / q_x1), "y" / "qkv" / "h": the last layer's down projection,
+        QKV rows and GeGLU output as bf16 bit patterns (uint16), "d1": the Dense 1 output (uint16 [dense_hidden])}.
+        bf16 arrays are returned as bits so that callers can compare bytes; `bf16_to_f32` widens them."""
+        c, T = self.cfg, int(tokens)
+        nq = (c.heads + 2 * c.kv_heads) * c.head_dim
+        out = {"x": np.zeros((T, c.hidden), np.float32), "y": np.zeros((T, c.hidden), np.uint16),
+               "qkv": np.zeros((T, nq), np.uint16), "h": np.zeros((T, c.intermediate), np.uint16),
+               "d1": np.zeros(c.dense_hidden, np.uint16)}
+        which = C.c_int32(-1)
+        rc = self._lib.cqs_hip_debug_embedder_query_state(self._h, int(ctx), T, *[out[k].ctypes.data_as(C.c_void_p) for k in ("x", "y", "qkv", "h", "d1")],
+                                                          C.byref(which))
+        if rc != _lib.OK:
+            raise HipError(rc, self.last_error())
+        out["which_x"] = int(which.value)
         return out
 
     def close(self) -> None:

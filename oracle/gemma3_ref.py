@@ -120,9 +120,18 @@ def round_bf16(x: np.ndarray) -> np.ndarray:
 
 
 def forward(cfg: GemmaConfig, w: Dict[str, np.ndarray], input_ids: np.ndarray, attention_mask: np.ndarray,
-            return_hidden: bool = False):
+            return_hidden: bool = False, tap=None):
     """fp32 forward on CPU (torch).  input_ids / attention_mask: int64 [B, L].  -> f32 [B, hidden]
-    (`sentence_embedding` before L2 normalisation)."""
+    (`sentence_embedding` before L2 normalisation).
+
+    tap: optional callback `tap(stage, layer, tensor) -> tensor | None`, called once per layer at
+      "qkv"       [B, L, (heads + 2 kv_heads) * head_dim]: the q | k | v projections side by side, before q/k norm and RoPE
+      "attn"      [B, L, heads * head_dim]: softmax(scores) v, the heads side by side, before o_proj
+      "post_attn" [B, L, hidden]: the residual stream after the attention branch was added
+      "ffn"       [B, L, hidden]: the down projection, before its post-ffw norm
+      "layer_out" [B, L, hidden]: the residual stream after the layer
+    A returned tensor replaces the value at that point (tests plant errors this way); None keeps it.  Without a
+    callback the forward is what it was."""
     import torch
     torch.set_grad_enabled(False)
     ids = torch.from_numpy(np.ascontiguousarray(input_ids, dtype=np.int64))
@@ -147,6 +156,12 @@ def forward(cfg: GemmaConfig, w: Dict[str, np.ndarray], input_ids: np.ndarray, a
         emb = torch.cat([fr, fr], dim=-1)
         return emb.cos(), emb.sin()
 
+    def tapped(stage, layer, t):
+        if tap is None:
+            return t
+        r = tap(stage, layer, t)
+        return t if r is None else r
+
     tables = {True: rope_tables(cfg.rope_theta_global), False: rope_tables(cfg.rope_theta_local)}
 
     def rot(t):
@@ -157,9 +172,12 @@ def forward(cfg: GemmaConfig, w: Dict[str, np.ndarray], input_ids: np.ndarray, a
         p = f"layers.{i}."
         full = cfg.is_full(i)
         h = rms(x, W[p + "input_layernorm.weight"])
-        q = (h @ W[p + "self_attn.q_proj.weight"].T).view(B, L, nh, D).transpose(1, 2)
-        k = (h @ W[p + "self_attn.k_proj.weight"].T).view(B, L, nkv, D).transpose(1, 2)
-        v = (h @ W[p + "self_attn.v_proj.weight"].T).view(B, L, nkv, D).transpose(1, 2)
+        qkv = torch.cat([h @ W[p + "self_attn.q_proj.weight"].T, h @ W[p + "self_attn.k_proj.weight"].T,
+                         h @ W[p + "self_attn.v_proj.weight"].T], dim=-1)
+        qkv = tapped("qkv", i, qkv)
+        q = qkv[..., : nh * D].reshape(B, L, nh, D).transpose(1, 2)
+        k = qkv[..., nh * D: (nh + nkv) * D].reshape(B, L, nkv, D).transpose(1, 2)
+        v = qkv[..., (nh + nkv) * D:].reshape(B, L, nkv, D).transpose(1, 2)
         q = rms(q, W[p + "self_attn.q_norm.weight"])
         k = rms(k, W[p + "self_attn.k_norm.weight"])
         cos, sin = tables[full]
@@ -171,12 +189,12 @@ def forward(cfg: GemmaConfig, w: Dict[str, np.ndarray], input_ids: np.ndarray, a
         allow = key_ok if full else (key_ok & (dist < cfg.window)[None, None])
         s = s.masked_fill(~allow, neg)
         a = torch.softmax(s, dim=-1) @ v
-        a = a.transpose(1, 2).reshape(B, L, nh * D) @ W[p + "self_attn.o_proj.weight"].T
-        x = x + rms(a, W[p + "post_attention_layernorm.weight"])
+        a = tapped("attn", i, a.transpose(1, 2).reshape(B, L, nh * D)) @ W[p + "self_attn.o_proj.weight"].T
+        x = tapped("post_attn", i, x + rms(a, W[p + "post_attention_layernorm.weight"]))
         h = rms(x, W[p + "pre_feedforward_layernorm.weight"])
         g = torch.nn.functional.gelu(h @ W[p + "mlp.gate_proj.weight"].T, approximate="tanh")
-        m = (g * (h @ W[p + "mlp.up_proj.weight"].T)) @ W[p + "mlp.down_proj.weight"].T
-        x = x + rms(m, W[p + "post_feedforward_layernorm.weight"])
+        m = tapped("ffn", i, (g * (h @ W[p + "mlp.up_proj.weight"].T)) @ W[p + "mlp.down_proj.weight"].T)
+        x = tapped("layer_out", i, x + rms(m, W[p + "post_feedforward_layernorm.weight"]))
     x = rms(x, W["norm.weight"])
     if return_hidden:
         return x.numpy()
