@@ -64,7 +64,11 @@ SIGNATURES = [
     ("cqs_hip_index_search_device", C.c_int32,
      [_c_idx, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float,
       C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("cqs_hip_index_search_filtered", C.c_int32,
+     [_c_idx, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_float,
+      C.c_void_p, C.c_void_p, C.c_void_p]),
     ("cqs_hip_index_combine_stats", None, [_c_idx, _pp(C.c_uint64), _pp(C.c_uint64)]),
+    ("cqs_hip_index_combine_filter_stats", None, [_c_idx, _pp(C.c_uint64), _pp(C.c_uint64)]),
     ("cqs_hip_index_set_bf16_scan", C.c_int32, [_c_idx, C.c_int32]),
     ("cqs_hip_index_bf16_stats", None, [_c_idx, _pp(C.c_uint64), _pp(C.c_uint64), _pp(C.c_uint64)]),
     ("cqs_hip_index_i8_stats", None, [_c_idx, _pp(C.c_uint64), _pp(C.c_uint64), _pp(C.c_uint64)]),

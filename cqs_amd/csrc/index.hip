@@ -111,7 +111,8 @@ uint32_t max_query_block(const cqs_hip_index* x) {
 }
 
 cqs::ScanArgs scan_args(const cqs_hip_index* x, const float* d_q, uint32_t b, uint32_t k, const uint32_t* d_keep,
-                        uint32_t mode, float thr, size_t elem_bytes, bool gemv_only, void* dbg, const uint32_t* gate) {
+                        uint32_t mode, float thr, size_t elem_bytes, bool gemv_only, void* dbg, const uint32_t* gate,
+                        const KeepTab* tab) {
     cqs::ScanArgs a;
     a.rows = x->d_rows;
     a.n = (uint32_t)x->n;
@@ -134,6 +135,7 @@ cqs::ScanArgs scan_args(const cqs_hip_index* x, const float* d_q, uint32_t b, ui
     a.gemv_only = gemv_only;
     a.tiers = cqs::plan_tiers(a.n_pad, x->n_cu, !gemv_only && cqs::uniform_groups(b, x->dim));
     a.gate = gate;
+    if (tab) { a.keep_tab = tab->d_tab; a.keep_stride = tab->stride; a.keep_slot = tab->slot; }
     return a;
 }
 
@@ -162,7 +164,7 @@ int32_t scan_select(cqs_hip_index* x, const cqs::ScanArgs& a, hipStream_t st, co
 // Enqueue scan + select for queries already on the device.  Caller holds mu.
 int32_t enqueue_search(cqs_hip_index* x, const float* d_q, uint32_t b, uint32_t k, const uint32_t* d_keep,
                        uint32_t mode, float thr, uint64_t* d_out_keys, uint32_t* d_out_counts, hipStream_t st, bool gemv_only,
-                       const uint32_t* gate) {
+                       const uint32_t* gate, const KeepTab* tab) {
     HIP_TRY(x, order_after_last(x, st));   // the previous search may still be running on another stream and owns the same scratch
     if (!gemv_only && cqs::use_mfma(b, x->dim)) {
         // the matrix-core path reads whole query tiles: stage the block in d_q with a zero tail
@@ -171,7 +173,7 @@ int32_t enqueue_search(cqs_hip_index* x, const float* d_q, uint32_t b, uint32_t 
         HIP_TRY(x, hipMemsetAsync((char*)x->d_q + qbytes, 0, (size_t)256 * x->dim * sizeof(float), st));
         d_q = x->d_q;
     }
-    cqs::ScanArgs a = scan_args(x, d_q, b, k, d_keep, mode, thr, sizeof(float), gemv_only, x->d_dbg, gate);
+    cqs::ScanArgs a = scan_args(x, d_q, b, k, d_keep, mode, thr, sizeof(float), gemv_only, x->d_dbg, gate, tab);
     static const bool use_gaux = [] { const char* e = getenv("CQS_HIP_SELECT_AUX"); return !(e && e[0] == '0'); }();   // A/B hook
     // The index only where the gather it replaces is long (scan_args): at k = 20 it costs what it saves (same-box A/B, 1M x 768,
     // scan + select per step: k = 20 0.4698 with / 0.4667 ms without; k = 500 0.4783 / 0.4825 - tools/ab_select_aux.sh).
@@ -202,8 +204,31 @@ int32_t stage_keep(cqs_hip_index* x, const uint32_t* host_words, uint64_t words)
     return CQS_HIP_OK;
 }
 
+void free_keep_tab(cqs_hip_index* x) {
+    hipFree(x->d_keep_tab);
+    hipHostFree(x->h_keep_tab);
+    x->d_keep_tab = nullptr; x->h_keep_tab = nullptr; x->keep_tab_stride = 0;
+}
+
+bool ensure_keep_tab(cqs_hip_index* x) {
+    const uint64_t cap = x->cap_rows > x->n ? x->cap_rows : x->n;
+    const uint64_t stride = (cap + 31) / 32;
+    if (x->d_keep_tab && x->keep_tab_stride >= stride) return true;
+    if (stride > 0xFFFFFFFFull || quiesce(x) != hipSuccess) return false;   // (a search in flight may read the old table)
+    free_keep_tab(x);
+    const size_t bytes = (size_t)kCombineCap * stride * sizeof(uint32_t);
+    if (hipMalloc(&x->d_keep_tab, bytes) != hipSuccess || hipHostMalloc(&x->h_keep_tab, bytes, hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        free_keep_tab(x);
+        return false;
+    }
+    x->keep_tab_stride = stride;
+    return true;
+}
+
 void read_combine_env(cqs_hip_index* x) {                                              // read once per handle
     if (const char* ce = getenv("CQS_HIP_COMBINE")) x->combine = ce[0] != '0';
+    if (const char* cf = getenv("CQS_HIP_COMBINE_FILTERED")) x->combine_filtered = cf[0] != '0';
     if (const char* cw = getenv("CQS_HIP_COMBINE_WAIT_US")) x->combine_wait_us = (uint32_t)atoi(cw);
     if (const char* cb = getenv("CQS_HIP_COMBINE_BITS")) x->combine_relaxed = cb[0] == 'r';
 }
@@ -351,6 +376,7 @@ int32_t cqs_hip_index_extend(cqs_hip_index* x, const float* rows, uint64_t n_new
         hipFree(x->d_rows);
         x->d_rows = nd;
         x->cap_rows = cap;
+        if (x->d_keep_tab) (void)ensure_keep_tab(x);   // (a failure leaves no table: filtered calls run one by one)
     }
     HIP_TRY(x, hipMemcpyAsync(x->d_rows + x->n * x->dim, rows, n_new * row_bytes, hipMemcpyHostToDevice, x->stream));
     HIP_TRY(x, hipStreamSynchronize(x->stream));
@@ -561,6 +587,7 @@ void cqs_hip_index_destroy(cqs_hip_index* x) CQS_ABI_TRY {
     free_scratch(x);
     shadow_free(x);
     hipFree(x->d_keep);
+    free_keep_tab(x);
     hipFree(x->d_dbg);
     if (!x->borrow) hipFree(x->d_rows);
     for (hipEvent_t e : x->ev) hipEventDestroy(e);
@@ -687,9 +714,10 @@ static void print_debug_stamps(cqs_hip_index* x) {
 
 // The nq queries staged in h_q (row i answers qs[i]; null: non-finite, a zero row, no answer), one wait: the f32 scan, or
 // with redo the bf16 shadow, whose uncovered queries go to *redo, restaged in order in h_q[0, redo->size()).  Caller holds
-// mu; x->stream is ordered after the last search.
+// mu; x->stream is ordered after the last search.  tab (with a null d_keep): query i is filtered by its own row of the table.
 static int32_t host_block(cqs_hip_index* x, const cqs_combine_req* const* qs, uint32_t nq, uint32_t k, const uint32_t* d_keep,
-                          uint32_t mode, float thr, bool gemv_only, std::vector<const cqs_combine_req*>* redo) {
+                          uint32_t mode, float thr, bool gemv_only, std::vector<const cqs_combine_req*>* redo,
+                          const KeepTab* tab = nullptr) {
     HIP_TRY(x, hipMemcpyAsync(x->d_q, x->h_q, (size_t)nq * x->dim * sizeof(float), hipMemcpyHostToDevice, x->stream));
     // Small blocks: the select kernel writes keys and counts straight into the pinned host buffers (device-visible
     // addresses): no copy calls behind the kernels, one wait.  Large blocks keep the device buffers + two copies
@@ -697,8 +725,8 @@ static int32_t host_block(cqs_hip_index* x, const cqs_combine_req* const* qs, ui
     const bool direct = x->h_out_keys_dev && x->h_out_counts_dev && (size_t)nq * k <= kDirectOutKeys;
     uint64_t* const keys = direct ? x->h_out_keys_dev : x->d_out_keys;
     uint32_t* const counts = direct ? x->h_out_counts_dev : x->d_out_counts;
-    int32_t rc = redo ? shadow_pass(x, x->d_q, nq, k, d_keep, mode, thr, keys, counts, x->stream, nullptr)
-                      : enqueue_search(x, x->d_q, nq, k, d_keep, mode, thr, keys, counts, x->stream, gemv_only);
+    int32_t rc = redo ? shadow_pass(x, x->d_q, nq, k, d_keep, mode, thr, keys, counts, x->stream, nullptr, tab)
+                      : enqueue_search(x, x->d_q, nq, k, d_keep, mode, thr, keys, counts, x->stream, gemv_only, nullptr, tab);
     if (rc != CQS_HIP_OK) return rc;
     if (redo) HIP_TRY(x, record_done(x, x->stream));
     if (!direct) {
@@ -795,17 +823,95 @@ static int32_t search_host_locked(cqs_hip_index* x, const cqs_combine_req* qs, u
     return CQS_HIP_OK;
 }
 
+// Kept rows of a host bitset over the handle's n rows (src/cagra.rs:747-775).
+static uint64_t count_kept(const cqs_hip_index* x, const uint32_t* keep_bitset) {
+    const uint64_t words = (x->n + 31) / 32;
+    uint64_t included = 0;
+    for (uint64_t w = 0; w < words; ++w) {
+        uint32_t v = keep_bitset[w];
+        if (w == words - 1 && (x->n % 32)) v &= (1u << (x->n % 32)) - 1u;
+        included += (uint64_t)__builtin_popcount(v);
+    }
+    return included;
+}
+
+// `b` queries with one (k, mode, threshold) and a bitset EACH (qs[i].keep), every one answered with the bytes of
+// search_host_locked(&qs[i], 1, k, qs[i].keep, ...): blocks of <= kCombineCap queries whose bitsets are staged in the
+// handle's table, run as gemv passes that read a batch of rows when any query of the pass keeps one of them and mask each
+// query's scores with its own row (scan_gemv_kernel, PQ).  The block runs at the callers' k: a query that keeps fewer rows
+// gets them all, as its lone call at k = kept rows does (filtered-out rows are -inf and never candidates).  A query that
+// keeps nothing or is not finite is answered with count 0 and takes no slot.  Through the shadow copies under the rules of
+// unfiltered blocks; the uncertified queries are redone on the f32 scan with their own table rows.  Caller holds mu, has
+// checked the arguments and zeroed the counts.
+static int32_t search_filtered_locked(cqs_hip_index* x, const cqs_combine_req* qs, uint32_t b, uint32_t k, uint32_t mode,
+                                      float threshold) {
+    if (b == 1) return search_host_locked(x, qs, 1, k, qs[0].keep, mode, threshold, /*gemv_only=*/true);   // a lone call: the shared-bitset kernels
+    if (x->n == 0 || k == 0) {
+        if (x->inject_fail.exchange(0, std::memory_order_acq_rel) != 0)
+            return fail(x, CQS_HIP_ERR_DEVICE, "search: injected device failure (test hook)");
+        return CQS_HIP_OK;
+    }
+    HIP_TRY(x, hipSetDevice(x->device));
+    if (!ensure_keep_tab(x)) {   // no memory for the table: one by one over d_keep
+        for (uint32_t i = 0; i < b; ++i) {
+            const int32_t rc = search_host_locked(x, &qs[i], 1, k, qs[i].keep, mode, threshold, true);
+            if (rc != CQS_HIP_OK) return rc;
+        }
+        return CQS_HIP_OK;
+    }
+    if (x->inject_fail.exchange(0, std::memory_order_acq_rel) != 0)
+        return fail(x, CQS_HIP_ERR_DEVICE, "search: injected device failure (test hook)");
+    HIP_TRY(x, order_after_last(x, x->stream));
+    const uint64_t words = (x->n + 31) / 32;
+    std::vector<const cqs_combine_req*> staged, redo;
+    std::vector<uint8_t> slot, rslot;
+    for (uint32_t done = 0; done < b;) {
+        // the next block: up to kCombineCap queries that have an answer, query i in h_q row i and table row i
+        staged.clear();
+        int32_t rc = ensure_scratch(x, (b - done) < kCombineCap ? (b - done) : kCombineCap, k);
+        if (rc != CQS_HIP_OK) return rc;
+        for (; done < b && staged.size() < kCombineCap; ++done) {
+            const cqs_combine_req& r = qs[done];
+            bool ok = true;
+            for (uint32_t d = 0; d < x->dim; ++d) ok &= std::isfinite(r.q[d]);
+            if (!ok || count_kept(x, r.keep) == 0) continue;          // src/cagra.rs:464-470, :765-767
+            memcpy(x->h_q + staged.size() * x->dim, r.q, (size_t)x->dim * sizeof(float));
+            memcpy(x->h_keep_tab + staged.size() * x->keep_tab_stride, r.keep, words * sizeof(uint32_t));
+            staged.push_back(&r);
+        }
+        if (staged.empty()) continue;
+        uint32_t nb = (uint32_t)staged.size();
+        HIP_TRY(x, hipMemcpyAsync(x->d_keep_tab, x->h_keep_tab, ((size_t)(nb - 1u) * x->keep_tab_stride + words) * sizeof(uint32_t),
+                                  hipMemcpyHostToDevice, x->stream));
+        slot.resize(nb);
+        for (uint32_t i = 0; i < nb; ++i) slot[i] = (uint8_t)i;
+        KeepTab tab{x->d_keep_tab, (uint32_t)x->keep_tab_stride, slot.data()};
+        if (shadow_takes(x, nb, k, /*gemv_only=*/true)) {
+            if ((rc = host_block(x, staged.data(), nb, k, nullptr, mode, threshold, true, &redo, &tab)) != CQS_HIP_OK) return rc;
+            // the queries the certificate did not cover, restaged in order in h_q: they keep their table rows
+            rslot.clear();
+            for (uint32_t i = 0, j = 0; i < nb && j < redo.size(); ++i)
+                if (staged[i] == redo[j]) { rslot.push_back(slot[i]); ++j; }
+            staged.swap(redo);
+            slot.swap(rslot);
+            tab.slot = slot.data();
+            nb = (uint32_t)staged.size();
+        }
+        if (nb && (rc = host_block(x, staged.data(), nb, k, nullptr, mode, threshold, true, nullptr, &tab)) != CQS_HIP_OK) return rc;
+    }
+    return CQS_HIP_OK;
+}
+
 // ---- the combining queue --------------------------------------------------------------------------------------------
 // Concurrent single-query callers of cqs_hip_index_search (the daemon's client threads, src/cli/watch/daemon.rs:273,
 // on one Arc<dyn VectorIndex>) used to queue on the handle mutex for one 0.5 ms pass EACH, although one pass scans up to
 // 8 queries for 0.50-0.54 ms.  Now a caller parks its query; whoever leads next takes the device, gathers
 // the parked queries with the same (k, mode, threshold) and runs them as ONE block of gemv passes; every caller gets
-// exactly the bits a lone call would have produced (search_host_locked, gemv_only).  Bitsets, multi-query blocks and
-// sharded handles keep the serial path.
-constexpr uint32_t kCombineCap = 32;     // queries per combined block (4 passes of 8)
-
-static bool same_params(const cqs_combine_req* a, const cqs_combine_req* b) {
-    return a->k == b->k && a->mode == b->mode && memcmp(&a->thr, &b->thr, sizeof(float)) == 0;
+// exactly the bits a lone call would have produced (search_host_locked, gemv_only).  Callers with a bitset park too, on a
+// single-device handle, and form blocks of their own (search_filtered_locked: one bitset per query).  Multi-query blocks,
+// and bitsets on a sharded handle, keep the serial path.
+static bool same_params(const cqs_combine_req* a, const cqs_combine_req* b) {   // (callers with a bitset form blocks of their own)
+    return a->k == b->k && a->mode == b->mode && memcmp(&a->thr, &b->thr, sizeof(float)) == 0 && !a->keep == !b->keep;
 }
 static uint32_t count_like_front(const cqs_hip_index* x) {
     uint32_t n = 0;
@@ -823,6 +929,7 @@ static int32_t combine_run_single(cqs_hip_index* x, cqs_combine_req* const* batc
     // block of >= 9 callers take the matrix-core kernel instead - 32 queries per corpus sweep instead of 8, scores in another
     // summation order (|delta| <= 2e-6 on unit vectors, inside the parity tolerance; the reference's GPU backend promises no
     // bit-reproducibility across calls either, src/cagra.rs:443-492)
+    if (batch[0]->keep) return search_filtered_locked(x, rq, nb, batch[0]->k, batch[0]->mode, batch[0]->thr);
     const bool gemv_only = !(x->combine_relaxed && nb >= cqs::kMfmaMinQueries);
     return search_host_locked(x, rq, nb, batch[0]->k, nullptr, batch[0]->mode, batch[0]->thr, gemv_only);
 }
@@ -872,8 +979,8 @@ static void combine_lead(cqs_hip_index* x, std::unique_lock<std::mutex>& lk) {
     } catch (...) {
         rc = fail(x, CQS_HIP_ERR_INVALID, "search: unexpected C++ exception");
     }
-    x->stat_passes.fetch_add(1, std::memory_order_relaxed);
-    x->stat_queries.fetch_add(nb, std::memory_order_relaxed);
+    (batch[0]->keep ? x->stat_fpasses : x->stat_passes).fetch_add(1, std::memory_order_relaxed);
+    (batch[0]->keep ? x->stat_fqueries : x->stat_queries).fetch_add(nb, std::memory_order_relaxed);
     const bool poisoned = x->sh ? cqs_sharded::poisoned(x) != 0 : x->poisoned.load(std::memory_order_acquire);
 
     lk.lock();
@@ -924,10 +1031,10 @@ int32_t cqs_hip_index_search(cqs_hip_index* x, const float* queries, uint32_t b,
                              float* out_scores, uint32_t* out_counts) CQS_ABI_TRY {
     CQS_ROCTX_RANGE("cqs_hip_index_search");
     if (!x) return CQS_HIP_ERR_INVALID;
-    // One query, no filter, arguments in order: the combining queue (dim is immutable; everything else the locked
+    // One query, arguments in order: the combining queue (dim is immutable; everything else the locked
     // path would check is checked here or inside the pass).  Round 5: a row-sharded parent takes it too - what a
     // multi-GPU daemon binds - its block runs through every shard and the host merge (cqs_sharded::search_combined).
-    if (x->combine && b == 1 && !keep_bitset && queries && out_counts && out_rows && out_scores && query_dim == x->dim &&
+    if (x->combine && b == 1 && (!keep_bitset || (x->combine_filtered && !x->sh)) && queries && out_counts && out_rows && out_scores && query_dim == x->dim &&
         k >= 1 && k <= kMaxK && mode <= CQS_HIP_MODE_PIPELINE) {
         if (x->sh ? cqs_sharded::poisoned(x) != 0 : x->poisoned.load(std::memory_order_acquire))
             return CQS_HIP_ERR_POISONED;                                               // src/cagra.rs:486-490
@@ -936,6 +1043,7 @@ int32_t cqs_hip_index_search(cqs_hip_index* x, const float* queries, uint32_t b,
         for (uint32_t d = 0; d < query_dim; ++d) finite &= std::isfinite(queries[d]);
         if (!finite) return CQS_HIP_OK;                                                // src/cagra.rs:464-470
         cqs_combine_req r{queries, k, mode, threshold, out_rows, out_scores, out_counts};
+        r.keep = keep_bitset;
         return combine_search(x, r);
     }
     if (x->sh) return cqs_sharded::search(x, queries, b, query_dim, k, keep_bitset, mode, threshold, out_rows, out_scores, out_counts);
@@ -964,6 +1072,54 @@ void cqs_hip_index_combine_stats(const cqs_hip_index* x, uint64_t* passes, uint6
     if (passes) *passes = x ? x->stat_passes.load(std::memory_order_relaxed) : 0;
     if (queries) *queries = x ? x->stat_queries.load(std::memory_order_relaxed) : 0;
 } CQS_ABI_CATCH_VOID
+
+// The same counters for the blocks of callers with a bitset (and nothing else: cqs_hip_index_search_filtered does not count).
+void cqs_hip_index_combine_filter_stats(const cqs_hip_index* x, uint64_t* passes, uint64_t* queries) CQS_ABI_TRY {
+    if (passes) *passes = x ? x->stat_fpasses.load(std::memory_order_relaxed) : 0;
+    if (queries) *queries = x ? x->stat_fqueries.load(std::memory_order_relaxed) : 0;
+} CQS_ABI_CATCH_VOID
+
+// `b` queries, each with its own keep-bitset: per query the bytes of cqs_hip_index_search(…, 1, …, that bitset, …).
+int32_t cqs_hip_index_search_filtered(cqs_hip_index* x, const float* queries, uint32_t b, uint32_t query_dim, uint32_t k,
+                                      const uint32_t* keep_bitsets, uint64_t keep_stride_words, uint32_t mode,
+                                      float threshold, uint64_t* out_rows, float* out_scores, uint32_t* out_counts) CQS_ABI_TRY {
+    CQS_ROCTX_RANGE("cqs_hip_index_search_filtered");
+    if (!x) return CQS_HIP_ERR_INVALID;
+    if (x->sh) {   // a row-sharded parent: correct, not combined - one by one through its filtered search
+        if (b == 0) return CQS_HIP_OK;
+        if (!queries || !out_counts || !keep_bitsets) return CQS_HIP_ERR_INVALID;
+        for (uint32_t i = 0; i < b; ++i) out_counts[i] = 0;
+        if (query_dim != x->dim) return CQS_HIP_OK;
+        if (keep_stride_words < (cqs_sharded::len(x) + 31) / 32) return CQS_HIP_ERR_INVALID;
+        for (uint32_t i = 0; i < b; ++i) {
+            const int32_t rc = cqs_sharded::search(x, queries + (size_t)i * x->dim, 1, query_dim, k, keep_bitsets + (size_t)i * keep_stride_words,
+                                                   mode, threshold, out_rows ? out_rows + (size_t)i * k : nullptr,
+                                                   out_scores ? out_scores + (size_t)i * k : nullptr, out_counts + i);
+            if (rc != CQS_HIP_OK) return rc;
+        }
+        return CQS_HIP_OK;
+    }
+    std::lock_guard<std::mutex> g(x->mu);
+    if (x->poisoned.load(std::memory_order_acquire)) return CQS_HIP_ERR_POISONED;  // src/cagra.rs:486-490
+    if (b == 0) return CQS_HIP_OK;
+    if (!queries || !out_counts || !keep_bitsets) return fail(x, CQS_HIP_ERR_INVALID, "search_filtered: null buffer");
+    for (uint32_t i = 0; i < b; ++i) out_counts[i] = 0;
+    if (x->n == 0 || k == 0) return CQS_HIP_OK;               // src/cagra.rs:445-447
+    if (query_dim != x->dim) {                                  // src/cagra.rs:449-456
+        x->last_error = "search: query dimension mismatch (empty result)";
+        return CQS_HIP_OK;
+    }
+    if (k > kMaxK) return fail(x, CQS_HIP_ERR_INVALID, "search_filtered: k > max_k");
+    if (mode > CQS_HIP_MODE_PIPELINE) return fail(x, CQS_HIP_ERR_INVALID, "search_filtered: bad mode");
+    if (!out_rows || !out_scores) return fail(x, CQS_HIP_ERR_INVALID, "search_filtered: null output buffer");
+    if (keep_stride_words < (x->n + 31) / 32) return fail(x, CQS_HIP_ERR_INVALID, "search_filtered: bitset stride shorter than the index");
+    std::vector<cqs_combine_req> rq(b);
+    for (uint32_t i = 0; i < b; ++i) {
+        rq[i] = cqs_combine_req{queries + (size_t)i * x->dim, k, mode, threshold, out_rows + (size_t)i * k, out_scores + (size_t)i * k, out_counts + i};
+        rq[i].keep = keep_bitsets + (size_t)i * keep_stride_words;
+    }
+    return search_filtered_locked(x, rq.data(), b, k, mode, threshold);
+} CQS_ABI_CATCH(x)
 
 // `find_neighbors` (src/cli/commands/search/neighbors.rs:86-132) for a row of this index: the query is the
 // target row where it already lies in HBM (no H2D), the scan asks for limit + 1 and the target itself is
@@ -1063,6 +1219,38 @@ double cqs_hip_debug_client_storm(cqs_hip_index* x, const float* queries, uint32
             for (uint32_t i = 0; i < per_thread; ++i) {
                 const int32_t rc = cqs_hip_index_search(x, queries + (size_t)qi * dim, 1, dim, k, nullptr, CQS_HIP_MODE_RAW, 0.f,
                                                         out_rows + (size_t)qi * k, out_scores + (size_t)qi * k, out_counts + qi);
+                if (rc != CQS_HIP_OK) { bad.store(rc); break; }
+                qi = (qi + n_threads) % n_queries;
+            }
+        });
+    while (ready.load() < n_threads) std::this_thread::yield();
+    const auto t0 = std::chrono::steady_clock::now();
+    go.store(true, std::memory_order_release);
+    for (std::thread& t : th) t.join();
+    const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+    return bad.load() ? -1.0 : el;
+} CQS_ABI_CATCH_VAL(-1.0)
+
+// The same storm with one bitset per query row: thread t's call for query qi passes keep_bitsets + qi * keep_stride_words.
+double cqs_hip_debug_client_storm_filtered(cqs_hip_index* x, const float* queries, uint32_t n_queries, uint32_t dim, uint32_t k,
+                                           const uint32_t* keep_bitsets, uint64_t keep_stride_words, uint32_t n_threads,
+                                           uint32_t per_thread, uint64_t* out_rows, float* out_scores,
+                                           uint32_t* out_counts) CQS_ABI_TRY {
+    if (!x || !queries || !n_queries || !n_threads || !keep_bitsets || !out_rows || !out_scores || !out_counts) return -1.0;
+    std::atomic<int32_t> bad{0};
+    std::atomic<uint32_t> ready{0};
+    std::atomic<bool> go{false};
+    std::vector<std::thread> th;
+    th.reserve(n_threads);
+    for (uint32_t t = 0; t < n_threads; ++t)
+        th.emplace_back([&, t]() {
+            ready.fetch_add(1);
+            while (!go.load(std::memory_order_acquire)) std::this_thread::yield();
+            uint32_t qi = t % n_queries;
+            for (uint32_t i = 0; i < per_thread; ++i) {
+                const int32_t rc = cqs_hip_index_search(x, queries + (size_t)qi * dim, 1, dim, k, keep_bitsets + (size_t)qi * keep_stride_words,
+                                                        CQS_HIP_MODE_RAW, 0.f, out_rows + (size_t)qi * k, out_scores + (size_t)qi * k,
+                                                        out_counts + qi);
                 if (rc != CQS_HIP_OK) { bad.store(rc); break; }
                 qi = (qi + n_threads) % n_queries;
             }

@@ -28,6 +28,7 @@ struct cqs_combine_req {
     uint32_t* out_count;
     int32_t rc = 0;
     bool done = false;
+    const uint32_t* keep = nullptr;   // nullable host keep-bitset of this query, ceil(len/32) words (filtered blocks)
 };
 
 struct cqs_hip_index {
@@ -56,6 +57,12 @@ struct cqs_hip_index {
     uint32_t* d_out_counts = nullptr;
     uint32_t* d_keep = nullptr;
     uint64_t keep_words_cap = 0;
+    // One bitset per query of a filtered block (index.hip, search_filtered_locked): kCombineCap rows of keep_tab_stride
+    // words = ceil(cap_rows / 32), and the pinned twin the rows are staged in.  Made on first use; null = none (the
+    // filtered calls then run one by one over d_keep).
+    uint32_t* d_keep_tab = nullptr;
+    uint32_t* h_keep_tab = nullptr;
+    uint64_t keep_tab_stride = 0;
     // pinned host staging
     float* h_q = nullptr;
     uint64_t* h_out_keys = nullptr;
@@ -95,9 +102,11 @@ struct cqs_hip_index {
     bool combine = true;                  // CQS_HIP_COMBINE=0: every caller takes the serial path
     bool combine_relaxed = false;         // CQS_HIP_COMBINE_BITS=relaxed: blocks of >= 9 callers may run on the matrix cores (32 queries per
                                           // sweep instead of 8): answers within the parity tolerance of the lone call's, not its bits
+    bool combine_filtered = true;         // CQS_HIP_COMBINE_FILTERED=0: single-query callers with a bitset take the serial path
     uint32_t combine_wait_us = 100;       // CQS_HIP_COMBINE_WAIT_US: how long after the END of a pass the next leader waits for the callers that pass carried
     std::chrono::steady_clock::time_point last_pass_end{};   // guarded by cmu (epoch until the first pass: nobody waits)
-    std::atomic<uint64_t> stat_passes{0}, stat_queries{0};   // combined passes run / queries they carried
+    std::atomic<uint64_t> stat_passes{0}, stat_queries{0};   // combined passes run / queries they carried (unfiltered callers)
+    std::atomic<uint64_t> stat_fpasses{0}, stat_fqueries{0}; // the same for the blocks of callers with a bitset
     std::atomic<int32_t> inject_fail{0};  // test hook (cqs_hip_debug_index_fail_next): the next host search fails as a device error
 
     // bf16 shadow (index_shadow.hip; null = off).  Its certified / fallback counts outlive it: they live on the handle.
@@ -112,6 +121,7 @@ constexpr size_t kMaxTimingEvents = 8192;
 constexpr uint64_t kNtBytes = 200ull << 20;  // corpus larger than this streams past L2/MALL
 constexpr uint32_t kGauxQueries = 32;        // query blocks up to this size (every gemv block the host paths form) carry the select's (argmax, runner-up) index
 constexpr uint32_t kGauxMinK = 100;          // ... and only from this k on (below it the gather it replaces is a few groups)
+constexpr uint32_t kCombineCap = 32;         // queries per combined block (4 passes of 8) = rows of the handle's bitset table
 constexpr size_t kDirectOutKeys = 8192;      // host searches of up to this many result keys have them written straight to pinned host memory
 
 uint64_t pad_rows(uint64_t n);
@@ -119,9 +129,13 @@ int32_t fail(cqs_hip_index* idx, int32_t code, const char* what, hipError_t e = 
 void free_scratch(cqs_hip_index* x);
 int32_t ensure_scratch(cqs_hip_index* x, uint32_t b, uint32_t k);
 uint32_t max_query_block(const cqs_hip_index* x);
+// One bitset per query of a gemv block: the device table, its row stride in words and the table row of each query (host
+// [b]; ScanArgs::keep_tab).  Passed beside a null d_keep.
+struct KeepTab { const uint32_t* d_tab; uint32_t stride; const uint8_t* slot; };
 // Scan + select arguments over the handle's corpus.  elem_bytes (4 f32, 2 the bf16 shadow) sizes `nontemporal`.
 cqs::ScanArgs scan_args(const cqs_hip_index* x, const float* d_q, uint32_t b, uint32_t k, const uint32_t* d_keep,
-                        uint32_t mode, float thr, size_t elem_bytes, bool gemv_only, void* dbg, const uint32_t* gate);
+                        uint32_t mode, float thr, size_t elem_bytes, bool gemv_only, void* dbg, const uint32_t* gate,
+                        const KeepTab* tab = nullptr);
 // The rows a shadow scan reads: the bf16 copy, or (bf16 null) the int8 codes and their row scales; bq: B_q of the block.
 struct ShadowRows { const uint16_t* bf16; const int8_t* i8; const float* i8_scale; const float* bq; };
 // The scan of `a` on st (over `shadow` when set; timed unless a.gate: the shadow scan was), then the select (out_keys null:
@@ -140,12 +154,15 @@ inline hipError_t record_done(cqs_hip_index* x, hipStream_t st) {
 // Enqueue scan + select for queries already on the device.  Caller holds mu.  gate: ScanArgs::gate (gemv blocks only).
 int32_t enqueue_search(cqs_hip_index* x, const float* d_q, uint32_t b, uint32_t k, const uint32_t* d_keep,
                        uint32_t mode, float thr, uint64_t* d_out_keys, uint32_t* d_out_counts, hipStream_t st,
-                       bool gemv_only = false, const uint32_t* gate = nullptr);
+                       bool gemv_only = false, const uint32_t* gate = nullptr, const KeepTab* tab = nullptr);
 hipError_t quiesce(cqs_hip_index* x);
 // cqs_hip_index_create without the bf16 shadow policy (the shards of a row-sharded parent stay on f32)
 int32_t create_owned(const float* rows, uint64_t n, uint32_t dim, uint32_t metric, int32_t device, uint64_t row_base,
                      cqs_hip_index** out);
 int32_t stage_keep(cqs_hip_index* x, const uint32_t* host_words, uint64_t words);
+// The handle's bitset table sized for cap_rows (made or regrown here; false = none: not enough memory).  Caller holds mu.
+bool ensure_keep_tab(cqs_hip_index* x);
+void free_keep_tab(cqs_hip_index* x);
 int32_t create_common(uint64_t n, uint32_t dim, uint32_t metric, int32_t device, uint64_t row_base,
                       cqs_hip_index** out, cqs_hip_index** made);
 void read_combine_env(cqs_hip_index* x);
@@ -156,7 +173,8 @@ void shadow_free(cqs_hip_index* x);
 bool shadow_takes(const cqs_hip_index* x, uint32_t b, uint32_t k, bool gemv_only);
 bool shadow_uses_i8(const cqs_hip_index* x, uint32_t b, uint32_t k);   // of a block shadow_takes: the int8 copy serves it
 int32_t shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k, const uint32_t* d_keep, uint32_t mode,
-                    float thr, uint64_t* out_keys, uint32_t* out_counts, hipStream_t st, const uint32_t** device_gate);
+                    float thr, uint64_t* out_keys, uint32_t* out_counts, hipStream_t st, const uint32_t** device_gate,
+                    const KeepTab* tab = nullptr);
 // The last host shadow pass's verdicts, pinned, valid after x->stream's wait (queues their copy when not mappable).
 hipError_t shadow_verdicts(cqs_hip_index* x, uint32_t nb, const uint32_t** h_cert);
 

@@ -314,7 +314,8 @@ bool shadow_uses_i8(const cqs_hip_index* x, uint32_t b, uint32_t k) {
 // and nothing is launched between it and the gated f32 scan (gate_closed).  Both callers record `done` after the pass,
 // which orders the next search, on any stream, after every user of d_bq, d_ekeys, d_cert and d_tickets.
 int32_t shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k, const uint32_t* d_keep, uint32_t mode,
-                    float threshold, uint64_t* out_keys, uint32_t* out_counts, hipStream_t st, const uint32_t** device_gate) {
+                    float threshold, uint64_t* out_keys, uint32_t* out_counts, hipStream_t st, const uint32_t** device_gate,
+                    const KeepTab* tab) {
     const Shadow* s = x->shadow;
     uint32_t* const cert = device_gate || !s->h_cert_dev ? s->d_cert : s->h_cert_dev;
     if (device_gate) *device_gate = cert;
@@ -331,7 +332,7 @@ int32_t shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k,
     }
     // gemv passes over the copy's rows (non-uniform tiers, no debug stamps), top k' + 1; the select's (argmax, runner-up)
     // index from kGauxMinK on whatever CQS_HIP_SELECT_AUX says (that A/B hook is the f32 select's)
-    const cqs::ScanArgs a = scan_args(x, d_q, nb, kp + 1u, d_keep, mode, threshold, i8 ? sizeof(int8_t) : sizeof(uint16_t), true, nullptr, nullptr);
+    const cqs::ScanArgs a = scan_args(x, d_q, nb, kp + 1u, d_keep, mode, threshold, i8 ? sizeof(int8_t) : sizeof(uint16_t), true, nullptr, nullptr, tab);
     const ShadowRows rows{i8 ? nullptr : s->d_bf16, i8 ? s->d_i8 : nullptr, s->d_i8_scale, s->d_bq};
     const int32_t rc = scan_select(x, a, st, &rows, nullptr, nullptr);   // (the scan alone: the tail kernel selects)
     if (rc == CQS_HIP_OK)

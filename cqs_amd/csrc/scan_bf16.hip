@@ -28,6 +28,7 @@ typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f2 __attribute__((ext_vector_type(2)));
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
+typedef __attribute__((address_space(4))) uint32_t kc32;
 
 __device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }          // component 2i
 __device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 0xFFFF0000u); }  // component 2i + 1
@@ -123,12 +124,15 @@ struct Bf16ScanParams {
     float* gmax;
     uint64_t* gaux;         // nullable
     const float* bq;        // [nq] B_q of each query of the pass (device)
+    uint32_t keep_stride;   // PQ: `keep` is a table of bitsets, this many words per row ...
+    uint8_t slot[kMaxGemvQ];// ... and query b of the pass is filtered by row slot[b] (ScanArgs::keep_tab)
 };
 
 // NCH = ceil(dim / 512): 1-KiB bf16 chunks per row; lane owns components [c*512 + lane*8, +8) of chunk c (one 16-byte load).
 // A partial last chunk (FULL = false, 768-d: lanes 32..63 of chunk 1) reads a clamped in-row address against a zero query
 // fragment, as scan_gemv_kernel does.  Batch by batch (loads, then math); occupancy keeps the HBM busy.
-template <int NCH, int BQ, int RI, bool NT, bool FULL>
+// PQ: one keep-bitset per query, as in scan_gemv_kernel.
+template <int NCH, int BQ, int RI, bool NT, bool FULL, bool PQ>
 __global__ __launch_bounds__(256) void scan_bf16_kernel(const Bf16ScanParams p) {
     constexpr int NV = RI * BQ;
     constexpr int LPV = 64 / NV;
@@ -209,13 +213,15 @@ __global__ __launch_bounds__(256) void scan_bf16_kernel(const Bf16ScanParams p) 
             if (lane / RI == j) sc[b] = t;
         }
     };
+    uint64_t qmask[PQ ? BQ : 1];   // PQ: the rows of the task each query keeps (task_mask)
     // The f32 epilogue's drop rules, made one-sided: a row is dropped only if its exact score is dropped too.  No clamp on
     // the stored score (bin_of clamps; the select only needs a monotone map).
     auto epilogue = [&](uint32_t cur, uint32_t base, uint32_t trows, uint64_t mask, float (&sc)[BQ]) {
         const uint32_t row = base + (uint32_t)lane;
-        const bool live = (uint32_t)lane < trows && ((mask >> lane) & 1ull);
+        const bool live_all = (uint32_t)lane < trows && ((mask >> lane) & 1ull);
 #pragma unroll
         for (int b = 0; b < BQ; ++b) {
+            const bool live = PQ ? (uint32_t)lane < trows && ((qmask[PQ ? b : 0] >> lane) & 1ull) : live_all;
             float s = sc[b];
             if (!live || !(__builtin_fabsf(s) <= 3.4028234664e38f)) s = -INFINITY;
             else if (p.mode == 1u && (uint32_t)b < p.nq) {
@@ -239,6 +245,27 @@ __global__ __launch_bounds__(256) void scan_bf16_kernel(const Bf16ScanParams p) 
         const uint64_t all = trows == 64u ? ~0ull : ((1ull << trows) - 1ull);
         uint64_t mask = all;
         if (base + trows > n) mask = (base >= n) ? 0ull : (all >> (trows - (n - base)));
+        if constexpr (PQ) {   // (scan_gemv_kernel's: read what any query of the pass keeps, qmask[b] = what query b keeps)
+            const uint32_t w = base / 32u;
+            uint64_t any = 0ull;
+#pragma unroll
+            for (int b = 0; b < BQ; ++b) {
+                uint64_t m = 0ull;
+                if ((uint32_t)b < p.nq) {
+                    // (constant address space: nothing writes the table during the launch, so the uniform address is
+                    // enough for scalar loads; the shared bitset's plain loads are vector loads behind the row stores)
+                    const kc32* kp = (const kc32*)(p.keep + (size_t)p.slot[b] * p.keep_stride);
+                    const uint32_t w0 = (w < nwords) ? kp[w] : 0u;
+                    const uint32_t w1 = (w + 1u < nwords) ? kp[w + 1u] : 0u;
+                    m = mask & ((((uint64_t)w1 << 32) | (uint64_t)w0) >> (base & 31u));
+                }
+                const uint32_t mlo = __builtin_amdgcn_readfirstlane((uint32_t)m);
+                const uint32_t mhi = __builtin_amdgcn_readfirstlane((uint32_t)(m >> 32));
+                qmask[b] = ((uint64_t)mhi << 32) | mlo;
+                any |= qmask[b];
+            }
+            return any;
+        }
         if (p.keep) {
             const uint32_t w = base / 32u;
             const uint32_t w0 = (w < nwords) ? p.keep[w] : 0u;
@@ -280,14 +307,16 @@ __global__ __launch_bounds__(256) void scan_bf16_kernel(const Bf16ScanParams p) 
 #define CQS_BF16_BLOCKS_PER_CU 2u
 #endif
 
-template <int NCH, int BQ, int RI>
+template <int NCH, int BQ, int RI, bool PQ>
 static hipError_t launch_bf16(const ScanArgs& a, const uint16_t* shadow, const float* bq, uint32_t q0, uint32_t nq,
                               uint32_t work_slot, hipStream_t st) {
     Bf16ScanParams p;
     p.rows = shadow; p.n = a.n; p.n_pad = a.n_pad; p.dim = a.dim;
     p.q = a.q + (size_t)q0 * a.dim;
     p.scores = a.scores + (size_t)q0 * a.n_pad;
-    p.keep = a.keep; p.mode = a.mode; p.thr = a.threshold;
+    p.keep = PQ ? a.keep_tab : a.keep; p.mode = a.mode; p.thr = a.threshold;
+    p.keep_stride = PQ ? a.keep_stride : 0u;
+    for (uint32_t i = 0; i < kMaxGemvQ; ++i) p.slot[i] = (PQ && i < nq) ? a.keep_slot[q0 + i] : (uint8_t)0;
     p.nq = nq;
     p.work = a.work + work_slot;
     p.tiers = a.tiers;
@@ -301,16 +330,16 @@ static hipError_t launch_bf16(const ScanArgs& a, const uint16_t* shadow, const f
     const dim3 grid(blocks), block(64u * wpb);
     const bool full = (a.dim == (uint32_t)NCH * 512u);
     if (a.nontemporal) {
-        if (full) hipLaunchKernelGGL((scan_bf16_kernel<NCH, BQ, RI, true, true>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((scan_bf16_kernel<NCH, BQ, RI, true, false>), grid, block, 0, st, p);
+        if (full) hipLaunchKernelGGL((scan_bf16_kernel<NCH, BQ, RI, true, true, PQ>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((scan_bf16_kernel<NCH, BQ, RI, true, false, PQ>), grid, block, 0, st, p);
     } else {
-        if (full) hipLaunchKernelGGL((scan_bf16_kernel<NCH, BQ, RI, false, true>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((scan_bf16_kernel<NCH, BQ, RI, false, false>), grid, block, 0, st, p);
+        if (full) hipLaunchKernelGGL((scan_bf16_kernel<NCH, BQ, RI, false, true, PQ>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((scan_bf16_kernel<NCH, BQ, RI, false, false, PQ>), grid, block, 0, st, p);
     }
     return hipGetLastError();
 }
 
-template <int NCH>
+template <int NCH, bool PQ>
 static hipError_t launch_bf16_groups(const ScanArgs& a, const uint16_t* shadow, const float* bq, hipStream_t st) {
     uint32_t done = 0, slot = 0;
     while (done < a.b) {
@@ -318,13 +347,13 @@ static hipError_t launch_bf16_groups(const ScanArgs& a, const uint16_t* shadow, 
         hipError_t e;
         uint32_t g;
         if constexpr (NCH <= 2) {   // (5..7 queries ride the 8-query pass, as in the f32 scan)
-            if (left >= 5) { g = left < 8u ? left : 8u; e = launch_bf16<NCH, 8, 2>(a, shadow, bq, done, g, slot, st); }
-            else if (left >= 4) { g = 4; e = launch_bf16<NCH, 4, 4>(a, shadow, bq, done, g, slot, st); }
-            else if (left >= 2) { g = 2; e = launch_bf16<NCH, 2, 8>(a, shadow, bq, done, g, slot, st); }
-            else { g = 1; e = launch_bf16<NCH, 1, 16>(a, shadow, bq, done, g, slot, st); }
+            if (left >= 5) { g = left < 8u ? left : 8u; e = launch_bf16<NCH, 8, 2, PQ>(a, shadow, bq, done, g, slot, st); }
+            else if (left >= 4) { g = 4; e = launch_bf16<NCH, 4, 4, PQ>(a, shadow, bq, done, g, slot, st); }
+            else if (left >= 2) { g = 2; e = launch_bf16<NCH, 2, 8, PQ>(a, shadow, bq, done, g, slot, st); }
+            else { g = 1; e = launch_bf16<NCH, 1, 16, PQ>(a, shadow, bq, done, g, slot, st); }
         } else {
-            if (left >= 2) { g = 2; e = launch_bf16<NCH, 2, 4>(a, shadow, bq, done, g, slot, st); }
-            else { g = 1; e = launch_bf16<NCH, 1, 8>(a, shadow, bq, done, g, slot, st); }
+            if (left >= 2) { g = 2; e = launch_bf16<NCH, 2, 4, PQ>(a, shadow, bq, done, g, slot, st); }
+            else { g = 1; e = launch_bf16<NCH, 1, 8, PQ>(a, shadow, bq, done, g, slot, st); }
         }
         if (e != hipSuccess) return e;
         done += g;
@@ -336,11 +365,12 @@ static hipError_t launch_bf16_groups(const ScanArgs& a, const uint16_t* shadow, 
 hipError_t launch_scan_bf16(const ScanArgs& a, const uint16_t* shadow, const float* bq, hipStream_t st) {
     if (a.b == 0 || a.n == 0) return hipSuccess;
     if (a.b > kShadowMaxQ || a.dim % 8u != 0u || a.dim > kShadowMaxDim) return hipErrorInvalidValue;
+    if (a.keep_tab && (a.keep || !a.keep_slot || a.keep_stride < (a.n + 31u) / 32u)) return hipErrorInvalidValue;
     switch ((a.dim + 511u) / 512u) {
-        case 1: return launch_bf16_groups<1>(a, shadow, bq, st);
-        case 2: return launch_bf16_groups<2>(a, shadow, bq, st);
-        case 3: return launch_bf16_groups<3>(a, shadow, bq, st);
-        case 4: return launch_bf16_groups<4>(a, shadow, bq, st);
+        case 1: return a.keep_tab ? launch_bf16_groups<1, true>(a, shadow, bq, st) : launch_bf16_groups<1, false>(a, shadow, bq, st);
+        case 2: return a.keep_tab ? launch_bf16_groups<2, true>(a, shadow, bq, st) : launch_bf16_groups<2, false>(a, shadow, bq, st);
+        case 3: return a.keep_tab ? launch_bf16_groups<3, true>(a, shadow, bq, st) : launch_bf16_groups<3, false>(a, shadow, bq, st);
+        case 4: return a.keep_tab ? launch_bf16_groups<4, true>(a, shadow, bq, st) : launch_bf16_groups<4, false>(a, shadow, bq, st);
         default: return hipErrorInvalidValue;
     }
 }

@@ -14,6 +14,7 @@
 namespace cqs {
 
 typedef float f4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(4))) uint32_t kc32;
 typedef float f2 __attribute__((ext_vector_type(2)));
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
 
@@ -128,6 +129,8 @@ struct I8ScanParams {
     float* gmax;
     uint64_t* gaux;         // nullable
     const float* bq;        // [nq] B_q of each query of the pass (device)
+    uint32_t keep_stride;   // PQ: `keep` is a table of bitsets, this many words per row ...
+    uint8_t slot[kMaxGemvQ];// ... and query b of the pass is filtered by row slot[b] (ScanArgs::keep_tab)
 };
 
 // NCH = ceil(dim / 1024): 1-KiB chunks per row; lane owns components [c*1024 + lane*16, +16) of chunk c (one 16-byte load).
@@ -137,7 +140,8 @@ struct I8ScanParams {
 // One task per wave at every size, no persistent grid + work queue: with the queue a search took 0.26 ms against 0.158 at
 // 1M rows and 2.11 against 1.24 at 10M - both about 14 ns per dequeued task, whatever the blocks per CU,
 // which points at the one returning atomic per task on an address every XCD shares; this scan needs a task every 8 ns.
-template <int NCH, int BQ, int RI, bool NT, bool FULL>
+// PQ: one keep-bitset per query, as in scan_gemv_kernel.
+template <int NCH, int BQ, int RI, bool NT, bool FULL, bool PQ>
 __global__ __launch_bounds__(256) void scan_i8_kernel(const I8ScanParams p) {
     constexpr int NV = RI * BQ;
     constexpr int LPV = 64 / NV;
@@ -216,13 +220,15 @@ __global__ __launch_bounds__(256) void scan_i8_kernel(const I8ScanParams p) {
             if (lane / RI == j) sc[b] = t;
         }
     };
+    uint64_t qmask[PQ ? BQ : 1];   // PQ: the rows of the task each query keeps (task_mask)
     // scan_bf16_kernel's epilogue after the scale: the f32 drop rules made one-sided with this copy's B_q.  A row with a
     // non-finite component has a NaN scale, so its score is dropped here as the f32 scan drops it.
     auto epilogue = [&](uint32_t cur, uint32_t base, uint32_t trows, uint64_t mask, float scale, float (&sc)[BQ]) {
         const uint32_t row = base + (uint32_t)lane;
-        const bool live = (uint32_t)lane < trows && ((mask >> lane) & 1ull);
+        const bool live_all = (uint32_t)lane < trows && ((mask >> lane) & 1ull);
 #pragma unroll
         for (int b = 0; b < BQ; ++b) {
+            const bool live = PQ ? (uint32_t)lane < trows && ((qmask[PQ ? b : 0] >> lane) & 1ull) : live_all;
             float s = sc[b] * scale;
             if (!live || !(__builtin_fabsf(s) <= 3.4028234664e38f)) s = -INFINITY;
             else if (p.mode == 1u && (uint32_t)b < p.nq) {
@@ -245,6 +251,27 @@ __global__ __launch_bounds__(256) void scan_i8_kernel(const I8ScanParams p) {
         const uint64_t all = trows == 64u ? ~0ull : ((1ull << trows) - 1ull);
         uint64_t mask = all;
         if (base + trows > n) mask = (base >= n) ? 0ull : (all >> (trows - (n - base)));
+        if constexpr (PQ) {   // (scan_gemv_kernel's: read what any query of the pass keeps, qmask[b] = what query b keeps)
+            const uint32_t w = base / 32u;
+            uint64_t any = 0ull;
+#pragma unroll
+            for (int b = 0; b < BQ; ++b) {
+                uint64_t m = 0ull;
+                if ((uint32_t)b < p.nq) {
+                    // (constant address space: nothing writes the table during the launch, so the uniform address is
+                    // enough for scalar loads; the shared bitset's plain loads are vector loads behind the row stores)
+                    const kc32* kp = (const kc32*)(p.keep + (size_t)p.slot[b] * p.keep_stride);
+                    const uint32_t w0 = (w < nwords) ? kp[w] : 0u;
+                    const uint32_t w1 = (w + 1u < nwords) ? kp[w + 1u] : 0u;
+                    m = mask & ((((uint64_t)w1 << 32) | (uint64_t)w0) >> (base & 31u));
+                }
+                const uint32_t mlo = __builtin_amdgcn_readfirstlane((uint32_t)m);
+                const uint32_t mhi = __builtin_amdgcn_readfirstlane((uint32_t)(m >> 32));
+                qmask[b] = ((uint64_t)mhi << 32) | mlo;
+                any |= qmask[b];
+            }
+            return any;
+        }
         if (p.keep) {
             const uint32_t w = base / 32u;
             const uint32_t w0 = (w < nwords) ? p.keep[w] : 0u;
@@ -277,14 +304,16 @@ __global__ __launch_bounds__(256) void scan_i8_kernel(const I8ScanParams p) {
 
 constexpr int kI8RowsPerBatch = 16;   // of the single-query pass (divides the 16-row task); 8 measured 3 % slower
 
-template <int NCH, int BQ, int RI>
+template <int NCH, int BQ, int RI, bool PQ>
 static hipError_t launch_i8(const ScanArgs& a, const int8_t* codes, const float* scales, const float* bq, uint32_t q0,
                             uint32_t nq, hipStream_t st) {
     I8ScanParams p;
     p.rows = codes; p.scales = scales; p.n = a.n; p.n_pad = a.n_pad; p.dim = a.dim;
     p.q = a.q + (size_t)q0 * a.dim;
     p.scores = a.scores + (size_t)q0 * a.n_pad;
-    p.keep = a.keep; p.mode = a.mode; p.thr = a.threshold;
+    p.keep = PQ ? a.keep_tab : a.keep; p.mode = a.mode; p.thr = a.threshold;
+    p.keep_stride = PQ ? a.keep_stride : 0u;
+    for (uint32_t i = 0; i < kMaxGemvQ; ++i) p.slot[i] = (PQ && i < nq) ? a.keep_slot[q0 + i] : (uint8_t)0;
     p.nq = nq;
     p.tiers = a.tiers;
     p.n_tasks = a.tiers.total();
@@ -295,25 +324,25 @@ static hipError_t launch_i8(const ScanArgs& a, const int8_t* codes, const float*
     const dim3 grid((p.n_tasks + wpb - 1u) / wpb), block(64u * wpb);
     const bool full = (a.dim == (uint32_t)NCH * 1024u);
     if (a.nontemporal) {
-        if (full) hipLaunchKernelGGL((scan_i8_kernel<NCH, BQ, RI, true, true>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((scan_i8_kernel<NCH, BQ, RI, true, false>), grid, block, 0, st, p);
+        if (full) hipLaunchKernelGGL((scan_i8_kernel<NCH, BQ, RI, true, true, PQ>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((scan_i8_kernel<NCH, BQ, RI, true, false, PQ>), grid, block, 0, st, p);
     } else {
-        if (full) hipLaunchKernelGGL((scan_i8_kernel<NCH, BQ, RI, false, true>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((scan_i8_kernel<NCH, BQ, RI, false, false>), grid, block, 0, st, p);
+        if (full) hipLaunchKernelGGL((scan_i8_kernel<NCH, BQ, RI, false, true, PQ>), grid, block, 0, st, p);
+        else hipLaunchKernelGGL((scan_i8_kernel<NCH, BQ, RI, false, false, PQ>), grid, block, 0, st, p);
     }
     return hipGetLastError();
 }
 
-template <int NCH>
+template <int NCH, bool PQ>
 static hipError_t launch_i8_groups(const ScanArgs& a, const int8_t* codes, const float* scales, const float* bq, hipStream_t st) {
     uint32_t done = 0;
     while (done < a.b) {
         const uint32_t left = a.b - done;
         hipError_t e;
         uint32_t g;
-        if (left >= 3) { g = left < 4u ? left : 4u; e = launch_i8<NCH, 4, 4>(a, codes, scales, bq, done, g, st); }   // (3 ride the 4-query pass)
-        else if (left >= 2) { g = 2; e = launch_i8<NCH, 2, 8>(a, codes, scales, bq, done, g, st); }
-        else { g = 1; e = launch_i8<NCH, 1, kI8RowsPerBatch>(a, codes, scales, bq, done, g, st); }
+        if (left >= 3) { g = left < 4u ? left : 4u; e = launch_i8<NCH, 4, 4, PQ>(a, codes, scales, bq, done, g, st); }   // (3 ride the 4-query pass)
+        else if (left >= 2) { g = 2; e = launch_i8<NCH, 2, 8, PQ>(a, codes, scales, bq, done, g, st); }
+        else { g = 1; e = launch_i8<NCH, 1, kI8RowsPerBatch, PQ>(a, codes, scales, bq, done, g, st); }
         if (e != hipSuccess) return e;
         done += g;
     }
@@ -323,9 +352,10 @@ static hipError_t launch_i8_groups(const ScanArgs& a, const int8_t* codes, const
 hipError_t launch_scan_i8(const ScanArgs& a, const int8_t* codes, const float* scales, const float* bq, hipStream_t st) {
     if (a.b == 0 || a.n == 0) return hipSuccess;
     if (a.b > kShadowMaxQ || !i8_dim_ok(a.dim)) return hipErrorInvalidValue;
+    if (a.keep_tab && (a.keep || !a.keep_slot || a.keep_stride < (a.n + 31u) / 32u)) return hipErrorInvalidValue;
     switch ((a.dim + 1023u) / 1024u) {
-        case 1: return launch_i8_groups<1>(a, codes, scales, bq, st);
-        case 2: return launch_i8_groups<2>(a, codes, scales, bq, st);
+        case 1: return a.keep_tab ? launch_i8_groups<1, true>(a, codes, scales, bq, st) : launch_i8_groups<1, false>(a, codes, scales, bq, st);
+        case 2: return a.keep_tab ? launch_i8_groups<2, true>(a, codes, scales, bq, st) : launch_i8_groups<2, false>(a, codes, scales, bq, st);
         default: return hipErrorInvalidValue;
     }
 }

@@ -42,6 +42,10 @@ struct ScanArgs {
     uint32_t b;             // queries
     float* scores;          // [b, n_pad] f32, device
     const uint32_t* keep;   // nullable device bitset, ceil(n/32) words
+    const uint32_t* keep_tab = nullptr;   // nullable device table [rows][keep_stride] of bitsets, one row per query (gemv
+                            // passes only; `keep` must be null): query i of the block is filtered by row keep_slot[i]
+    uint32_t keep_stride = 0;             // words per table row (>= ceil(n/32)); 0 = the shared bitset `keep`
+    const uint8_t* keep_slot = nullptr;   // host [b]: table row of each query (passed to the kernels by value, pass by pass)
     uint32_t mode;          // CQS_HIP_MODE_*
     float threshold;
     bool nontemporal;       // stream the corpus past L2 (corpus >> Infinity Cache)

@@ -29,6 +29,7 @@ namespace cqs {
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef float f2 __attribute__((ext_vector_type(2)));
 typedef __attribute__((address_space(1))) uint32_t gu32;
+typedef __attribute__((address_space(4))) uint32_t kc32;
 
 
 // ---- scan ------------------------------------------------------------------
@@ -49,6 +50,8 @@ struct ScanParams {
     unsigned long long* dbg;  // CQS_HIP_DEBUG_STAMPS: [16 + 2*wave] = start / end realtime of each wave
     const uint32_t* gate;     // nullable, [gate_n]: skip the launch when all are 1 (ScanArgs::gate)
     uint32_t gate_n;
+    uint32_t keep_stride;     // PQ: `keep` is a table of bitsets, this many words per row ...
+    uint8_t slot[kMaxGemvQ];  // ... and query b of the pass is filtered by row slot[b] (ScanArgs::keep_tab)
 };
 
 // NCH = ceil(dim / 256): 1-KiB chunks per row.  BQ queries, RI rows per batch (RI*BQ partial
@@ -59,7 +62,11 @@ struct ScanParams {
 // OCC:  workgroups per CU the register allocation must leave room for.  The pipelined single-query
 //       variant wants > 256 VGPRs (one wave per SIMD); corpora with fewer tasks than 2 waves per SIMD
 //       use an OCC = 2 build instead so that every task is resident at once.
-template <int NCH, int BQ, int RI, bool NT, bool FULL, int PIPE, int OCC>
+// PQ:   one keep-bitset per query (ScanParams::slot).  A batch is read when ANY query of the pass keeps one of its rows, the
+//       pipelined path runs when together they keep the whole task; each query's own mask decides, in the epilogue, which
+//       rows it scores.  Every mask is wave-uniform and lives in a scalar register pair.  The arithmetic is untouched: a
+//       query's scores are those of a pass of its own with its bitset shared.
+template <int NCH, int BQ, int RI, bool NT, bool FULL, int PIPE, int OCC, bool PQ>
 __global__ __launch_bounds__(256, OCC) void scan_gemv_kernel(const ScanParams p) {
     if (p.gate && gate_closed(p.gate, p.gate_n)) return;   // the bf16 shadow certified the block (before any load or dequeue)
     constexpr int NV = RI * BQ;
@@ -160,14 +167,16 @@ __global__ __launch_bounds__(256, OCC) void scan_gemv_kernel(const ScanParams p)
         }
     };
 
+    uint64_t qmask[PQ ? BQ : 1];   // PQ: the rows of the current task each query keeps (task_mask)
     // emit the scores of task `cur` (lane <-> row base+lane, lanes < trows): one coalesced store per
     // query and the task maximum for the select's pruning index
     auto epilogue = [&](uint32_t cur, uint32_t base, uint32_t trows, uint64_t mask, float (&sc)[BQ]) {
         const uint32_t row = base + (uint32_t)lane;
-        const bool live = (uint32_t)lane < trows && ((mask >> lane) & 1ull);
+        bool live = (uint32_t)lane < trows && ((mask >> lane) & 1ull);
 #pragma unroll
         for (int b = 0; b < BQ; ++b) {
             float s = sc[b];
+            if constexpr (PQ) live = (uint32_t)lane < trows && ((qmask[b] >> lane) & 1ull);
             // non-finite scores are never emitted (src/math.rs:23-27, src/cagra.rs:649-651)
             if (!live || !(__builtin_fabsf(s) <= 3.4028234664e38f)) s = -INFINITY;
             else if (p.mode == 1u) {
@@ -196,10 +205,32 @@ __global__ __launch_bounds__(256, OCC) void scan_gemv_kernel(const ScanParams p)
     };
 
     // wave-uniform mask of the rows of a task this wave must score: inside the corpus, kept by the filter
+    // (PQ: by the filter of at least one query of the pass; qmask[b] = the rows query b keeps, none for a padding slot)
     auto task_mask = [&](uint32_t base, uint32_t trows) -> uint64_t {
         const uint64_t all = trows == 64u ? ~0ull : ((1ull << trows) - 1ull);
         uint64_t mask = all;
         if (base + trows > n) mask = (base >= n) ? 0ull : (all >> (trows - (n - base)));
+        if constexpr (PQ) {
+            const uint32_t w = base / 32u;
+            uint64_t any = 0ull;
+#pragma unroll
+            for (int b = 0; b < BQ; ++b) {
+                uint64_t m = 0ull;
+                if ((uint32_t)b < p.nq) {
+                    // (constant address space: nothing writes the table during the launch, so the uniform address is
+                    // enough for scalar loads; the shared bitset's plain loads are vector loads behind the row stores)
+                    const kc32* kp = (const kc32*)(p.keep + (size_t)p.slot[b] * p.keep_stride);
+                    const uint32_t w0 = (w < nwords) ? kp[w] : 0u;
+                    const uint32_t w1 = (w + 1u < nwords) ? kp[w + 1u] : 0u;
+                    m = mask & ((((uint64_t)w1 << 32) | (uint64_t)w0) >> (base & 31u));
+                }
+                const uint32_t mlo = __builtin_amdgcn_readfirstlane((uint32_t)m);
+                const uint32_t mhi = __builtin_amdgcn_readfirstlane((uint32_t)(m >> 32));
+                qmask[b] = ((uint64_t)mhi << 32) | mlo;
+                any |= qmask[b];
+            }
+            return any;
+        }
         if (p.keep) {
             const uint32_t w = base / 32u;
             const uint32_t w0 = (w < nwords) ? p.keep[w] : 0u;
@@ -333,14 +364,16 @@ TaskTiers plan_tiers(uint32_t n_pad, uint32_t n_cu, bool uniform64) {
 }
 static uint32_t tier_slot_log2(const TaskTiers& t) { return t.nA ? 6u : (t.nB ? 5u : 4u); }
 
-template <int NCH, int BQ, int RI>
+template <int NCH, int BQ, int RI, bool PQ>
 static hipError_t launch_gemv(const ScanArgs& a, uint32_t q0, uint32_t nq, uint32_t work_slot, hipStream_t st) {
     constexpr int PIPE = (BQ <= 2) ? CQS_SCAN_PIPE : 0;
     ScanParams p;
     p.rows = a.rows; p.n = a.n; p.n_pad = a.n_pad; p.dim = a.dim;
     p.q = a.q + (size_t)q0 * a.dim;
     p.scores = a.scores + (size_t)q0 * a.n_pad;
-    p.keep = a.keep; p.mode = a.mode; p.thr = a.threshold;
+    p.keep = PQ ? a.keep_tab : a.keep; p.mode = a.mode; p.thr = a.threshold;
+    p.keep_stride = PQ ? a.keep_stride : 0u;
+    for (uint32_t i = 0; i < kMaxGemvQ; ++i) p.slot[i] = (PQ && i < nq) ? a.keep_slot[q0 + i] : (uint8_t)0;
     p.nq = nq;
     p.work = a.work + work_slot;
     p.tiers = a.tiers;
@@ -378,7 +411,7 @@ static hipError_t launch_gemv(const ScanArgs& a, uint32_t q0, uint32_t nq, uint3
 #endif
 #define CQS_LAUNCH(NTV, FULLV, OCCV) \
     do {                                                                                                     \
-        auto kern = scan_gemv_kernel<NCH, BQ, RI, NTV, FULLV, PIPE, OCCV>;                                   \
+        auto kern = scan_gemv_kernel<NCH, BQ, RI, NTV, FULLV, PIPE, OCCV, PQ>;                               \
         if (occ_lds > 64u * 1024u) {                                                                         \
             static DynLdsOnce once;   /* per instantiation: the attribute is set once per device, not per launch */ \
             hipError_t e = once.ensure((const void*)kern, occ_lds);                                          \
@@ -394,7 +427,7 @@ static hipError_t launch_gemv(const ScanArgs& a, uint32_t q0, uint32_t nq, uint3
     return hipGetLastError();
 }
 
-template <int NCH>
+template <int NCH, bool PQ>
 static hipError_t launch_gemv_groups(const ScanArgs& a, hipStream_t st) {
     uint32_t done = 0, slot = 0;
     while (done < a.b) {
@@ -404,15 +437,15 @@ static hipError_t launch_gemv_groups(const ScanArgs& a, hipStream_t st) {
         // register budget ~ 4*NCH*(BQ + RI) + BQ*RI VGPRs: wide rows take fewer queries per pass
         if constexpr (NCH <= 4) {
             // 5..7 queries ride the 8-query pass (0.50 ms at 1M x 768; 4 + 1..3 would be two or three passes)
-            if (left >= 5) { g = left < 8u ? left : 8u; e = launch_gemv<NCH, 8, 2>(a, done, g, slot, st); }
-            else if (left >= 4) { g = 4; e = launch_gemv<NCH, 4, 4>(a, done, g, slot, st); }
-            else if (left >= 2) { g = 2; e = launch_gemv<NCH, 2, 4>(a, done, g, slot, st); }
-            else { g = 1; e = launch_gemv<NCH, 1, CQS_SCAN_RI1>(a, done, g, slot, st); }
+            if (left >= 5) { g = left < 8u ? left : 8u; e = launch_gemv<NCH, 8, 2, PQ>(a, done, g, slot, st); }
+            else if (left >= 4) { g = 4; e = launch_gemv<NCH, 4, 4, PQ>(a, done, g, slot, st); }
+            else if (left >= 2) { g = 2; e = launch_gemv<NCH, 2, 4, PQ>(a, done, g, slot, st); }
+            else { g = 1; e = launch_gemv<NCH, 1, CQS_SCAN_RI1, PQ>(a, done, g, slot, st); }
         } else if constexpr (NCH <= 8) {
-            if (left >= 2) { g = 2; e = launch_gemv<NCH, 2, 2>(a, done, g, slot, st); }
-            else { g = 1; e = launch_gemv<NCH, 1, 2>(a, done, g, slot, st); }
+            if (left >= 2) { g = 2; e = launch_gemv<NCH, 2, 2, PQ>(a, done, g, slot, st); }
+            else { g = 1; e = launch_gemv<NCH, 1, 2, PQ>(a, done, g, slot, st); }
         } else {
-            g = 1; e = launch_gemv<NCH, 1, 1>(a, done, g, slot, st);
+            g = 1; e = launch_gemv<NCH, 1, 1, PQ>(a, done, g, slot, st);
         }
         if (e != hipSuccess) return e;
         done += g;
@@ -429,6 +462,7 @@ hipError_t launch_scan(const ScanArgs& a, hipStream_t st) {
     if (a.b == 0 || a.n == 0) return hipSuccess;
     if (a.gate && (a.b > 64u || (!a.gemv_only && use_mfma(a.b, a.dim)))) return hipErrorInvalidValue;   // gemv passes only
     if (!a.gemv_only && use_mfma(a.b, a.dim)) {
+        if (a.keep_tab) return hipErrorInvalidValue;   // (per-query bitsets: gemv passes only)
         uint32_t slot = 0;
         for (uint32_t q0 = 0; q0 < a.b; q0 += 256u) {
             const uint32_t nq = (a.b - q0) < 256u ? (a.b - q0) : 256u;
@@ -443,23 +477,33 @@ hipError_t launch_scan(const ScanArgs& a, hipStream_t st) {
         return hipSuccess;
     }
     const uint32_t nch = (a.dim + 255u) / 256u;
+    if (a.keep_tab) {   // one bitset per query: the PQ instantiations (gemv passes only; the matrix-core kernel has none)
+        if (a.keep || !a.keep_slot || a.keep_stride < (a.n + 31u) / 32u) return hipErrorInvalidValue;
+        switch (nch) {
+#define CQS_PQ_CASE(N) case N: return launch_gemv_groups<N, true>(a, st);
+            CQS_PQ_CASE(1) CQS_PQ_CASE(2) CQS_PQ_CASE(3) CQS_PQ_CASE(4) CQS_PQ_CASE(5) CQS_PQ_CASE(6) CQS_PQ_CASE(7) CQS_PQ_CASE(8)
+            CQS_PQ_CASE(9) CQS_PQ_CASE(10) CQS_PQ_CASE(11) CQS_PQ_CASE(12) CQS_PQ_CASE(13) CQS_PQ_CASE(14) CQS_PQ_CASE(15) CQS_PQ_CASE(16)
+#undef CQS_PQ_CASE
+            default: return hipErrorInvalidValue;
+        }
+    }
     switch (nch) {
-        case 1: return launch_gemv_groups<1>(a, st);
-        case 2: return launch_gemv_groups<2>(a, st);
-        case 3: return launch_gemv_groups<3>(a, st);
-        case 4: return launch_gemv_groups<4>(a, st);
-        case 5: return launch_gemv_groups<5>(a, st);
-        case 6: return launch_gemv_groups<6>(a, st);
-        case 7: return launch_gemv_groups<7>(a, st);
-        case 8: return launch_gemv_groups<8>(a, st);
-        case 9: return launch_gemv_groups<9>(a, st);
-        case 10: return launch_gemv_groups<10>(a, st);
-        case 11: return launch_gemv_groups<11>(a, st);
-        case 12: return launch_gemv_groups<12>(a, st);
-        case 13: return launch_gemv_groups<13>(a, st);
-        case 14: return launch_gemv_groups<14>(a, st);
-        case 15: return launch_gemv_groups<15>(a, st);
-        case 16: return launch_gemv_groups<16>(a, st);
+        case 1: return launch_gemv_groups<1, false>(a, st);
+        case 2: return launch_gemv_groups<2, false>(a, st);
+        case 3: return launch_gemv_groups<3, false>(a, st);
+        case 4: return launch_gemv_groups<4, false>(a, st);
+        case 5: return launch_gemv_groups<5, false>(a, st);
+        case 6: return launch_gemv_groups<6, false>(a, st);
+        case 7: return launch_gemv_groups<7, false>(a, st);
+        case 8: return launch_gemv_groups<8, false>(a, st);
+        case 9: return launch_gemv_groups<9, false>(a, st);
+        case 10: return launch_gemv_groups<10, false>(a, st);
+        case 11: return launch_gemv_groups<11, false>(a, st);
+        case 12: return launch_gemv_groups<12, false>(a, st);
+        case 13: return launch_gemv_groups<13, false>(a, st);
+        case 14: return launch_gemv_groups<14, false>(a, st);
+        case 15: return launch_gemv_groups<15, false>(a, st);
+        case 16: return launch_gemv_groups<16, false>(a, st);
         default: return hipErrorInvalidValue;
     }
 }

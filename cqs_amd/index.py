@@ -362,6 +362,29 @@ class HipIndex(VectorIndex):
             raise HipError(rc, self.last_error())
         return rows[:, :k], scores[:, :k], counts
 
+    def search_batch_filtered(self, queries: np.ndarray, k: int, keep_bitsets: np.ndarray,
+                              mode: int = _lib.MODE_RAW, threshold: float = 0.0):
+        """Block of queries with a keep-bitset each (`keep_bitsets` u32 [b, words], words >= ceil(len/32)) through
+        `cqs_hip_index_search_filtered`: per query the answer of `search_batch(q, k, keep_bitset=its row)`.
+        Returns (rows u64 [b,k], scores f32 [b,k], counts u32 [b])."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        b, qd = q.shape
+        kb = np.ascontiguousarray(keep_bitsets, dtype=np.uint32)
+        if kb.ndim != 2 or kb.shape[0] != b:
+            raise ValueError("keep_bitsets must be [b, words]")
+        if kb.shape[1] < (len(self) + 31) // 32:
+            raise ValueError("keep_bitsets too short")
+        rows = np.zeros((b, max(k, 1)), dtype=np.uint64)
+        scores = np.zeros((b, max(k, 1)), dtype=np.float32)
+        counts = np.zeros((b,), dtype=np.uint32)
+        rc = self._lib.cqs_hip_index_search_filtered(self._h, _ptr(q), b, qd, k, _ptr(kb), kb.shape[1], mode, threshold,
+                                                     _ptr(rows), _ptr(scores), _ptr(counts))
+        if rc != _lib.OK:
+            raise HipError(rc, self.last_error())
+        return rows[:, :k], scores[:, :k], counts
+
     def search(self, query: np.ndarray, k: int) -> List[IndexResult]:
         """`VectorIndex::search` (src/index.rs:146): sorted by score desc; never raises for device trouble."""
         if self.is_empty() or k == 0:
@@ -408,6 +431,38 @@ class HipIndex(VectorIndex):
         c = int(counts[0])
         return [IndexResult(self._id(int(rows[0, i])), float(scores[0, i])) for i in range(c)]
 
+    def search_many_with_filters(self, queries: np.ndarray, k: int,
+                                 filters: Sequence[Callable[[str], bool]]) -> List[List[IndexResult]]:
+        """`search_with_filter` for a block of queries with a predicate each, in one call (the bitsets are built from
+        `id_map` as `search_with_filter` builds its one).  A query of the wrong dimension or with a non-finite component
+        gets []."""
+        q = np.asarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        if len(filters) != q.shape[0]:
+            raise ValueError("one filter per query")
+        if self.is_empty() or k == 0 or q.shape[0] == 0:
+            return [[] for _ in filters]
+        if q.shape[1] != self.dim():
+            log.warning("Query dimension mismatch expected_dim=%d actual_dim=%d", self.dim(), q.shape[1])
+            return [[] for _ in filters]
+        n = len(self)
+        base = int(self._lib.cqs_hip_index_row_base(self._h))
+        ids = [self._id(base + i) for i in range(n)]
+        bits = np.zeros((q.shape[0], (n + 31) // 32), dtype=np.uint32)
+        for j, flt in enumerate(filters):
+            keep = np.fromiter((bool(flt(cid)) for cid in ids), dtype=bool, count=n)
+            packed = np.packbits(keep, bitorder="little")
+            bits[j].view(np.uint8)[:len(packed)] = packed
+        k = min(k, self.max_k())
+        try:
+            rows, scores, counts = self.search_batch_filtered(q, k, bits)
+        except HipError as e:
+            log.error("HIP filtered search failed: %s", e)
+            return [[] for _ in filters]
+        return [[IndexResult(self._id(int(rows[j, i])), float(scores[j, i])) for i in range(int(counts[j]))]
+                for j in range(q.shape[0])]
+
     def neighbors_rows(self, target_row: int, limit: int):
         """`cqs_hip_index_neighbors`: (rows u64, scores f32) of the stored row's nearest neighbours, itself excluded."""
         rows = np.zeros((_lib.NEIGHBORS_MAX,), dtype=np.uint64)
@@ -450,6 +505,12 @@ class HipIndex(VectorIndex):
         """(passes, queries) the handle's combining queue has run since it was made (`cqs_hip_index_combine_stats`)."""
         p, q = C.c_uint64(), C.c_uint64()
         self._lib.cqs_hip_index_combine_stats(self._h, C.byref(p), C.byref(q))
+        return int(p.value), int(q.value)
+
+    def combine_filter_stats(self) -> Tuple[int, int]:
+        """(passes, queries) of the combining queue's blocks of callers with a bitset (`cqs_hip_index_combine_filter_stats`)."""
+        p, q = C.c_uint64(), C.c_uint64()
+        self._lib.cqs_hip_index_combine_filter_stats(self._h, C.byref(p), C.byref(q))
         return int(p.value), int(q.value)
 
     def set_bf16_scan(self, enable: bool) -> None:

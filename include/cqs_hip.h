@@ -169,15 +169,22 @@ size_t cqs_hip_index_last_error(const cqs_hip_index* idx, char* buf, size_t cap)
  *
  * Concurrent callers (the daemon calls `search` from one thread per client on a shared
  * Arc<dyn VectorIndex>, src/cli/watch/daemon.rs:273; CAGRA serialises them behind
- * Mutex<GpuState>, src/cagra.rs:263): calls with b == 1 and no bitset that meet on one
- * handle are COMBINED - a caller that finds the device busy parks its query, and whoever
- * takes the device next scans every parked query with the same (k, mode, threshold) in one
- * pass over the corpus (up to 8 queries share the HBM stream; more run as consecutive
- * passes inside the same hold of the device).  Each caller receives exactly the bytes a
- * lone call would have produced.  A lone caller pays two uncontended mutex operations.
- * A handle made by cqs_hip_index_create_sharded / _load_sharded combines the same way
- * (round 5): the block goes to every shard at once, one gather, one host merge per query.
- * Calls with a bitset or b > 1 run one after the other as before.
+ * Mutex<GpuState>, src/cagra.rs:263): calls with b == 1 that meet on one handle are
+ * COMBINED - a caller that finds the device busy parks its query, and whoever takes the
+ * device next scans every parked query with the same (k, mode, threshold) in one pass over
+ * the corpus (up to 8 queries share the HBM stream; more run as consecutive passes inside
+ * the same hold of the device).  Each caller receives exactly the bytes a lone call would
+ * have produced.  A lone caller pays two uncontended mutex operations.
+ * Callers with a keep_bitset (what `search_with_filter` and the hybrid search send,
+ * src/search/query.rs:860-888,1113-1132) are combined too, on a single-device handle: they
+ * form blocks of their own - never mixed with unfiltered callers - in which every query
+ * keeps its own bitset: a pass reads the rows that ANY of its queries keeps and scores each
+ * query over the rows IT keeps (see cqs_hip_index_search_filtered).
+ * CQS_HIP_COMBINE_FILTERED=0 (read at create) keeps them one after the other, as before.
+ * A handle made by cqs_hip_index_create_sharded / _load_sharded combines its unfiltered
+ * callers the same way (round 5): the block goes to every shard at once, one gather, one
+ * host merge per query; its callers with a bitset run one after the other.
+ * Calls with b > 1 run one after the other as before.
  * CQS_HIP_COMBINE_BITS=relaxed (read at create; default: exact) is an opt-in throughput mode: a block of >= 9 callers may
  * run on the matrix cores - 32 queries per corpus sweep instead of 8 (16 callers: 25 k q/s against 14 k) - and its answers
  * are then within the parity tolerance of the lone call's (scores <= 2e-6 apart on unit vectors, same ids outside
@@ -228,10 +235,30 @@ void cqs_hip_unpack_keys(const uint64_t* keys, size_t count, uint64_t* rows, flo
 size_t cqs_hip_merge_keys(const uint64_t* lists, const uint32_t* counts, size_t n_lists, size_t stride,
                           size_t k, uint64_t* out_keys);
 
+/* ---- search: host buffers, one keep-bitset per query ------------------------
+ * `search_with_filter` for a block of `b` queries with a filter EACH: query i is filtered by
+ * keep_bitsets + i * keep_stride_words (host; keep_stride_words >= ceil(len/32); bit layout
+ * as keep_bitset above).  Per query the result is exactly the bytes of
+ *   cqs_hip_index_search(idx, queries + i*dim, 1, dim, k, that bitset, mode, threshold, ...)
+ * with every rule of that call: an all-pass bitset is the unfiltered search, a bitset that
+ * keeps nothing gives count 0, the result length is capped at the kept rows, a non-finite
+ * query gives count 0, a dimension mismatch gives counts 0 and CQS_HIP_OK, k > max_k is
+ * CQS_HIP_ERR_INVALID.  out_rows / out_scores [b * k], out_counts [b].
+ * The queries run in blocks of up to 32 as passes of up to 8 that share the HBM stream: a
+ * pass reads a row when any of its queries keeps it.  With the bf16 / int8 shadow on, the
+ * blocks go through it like unfiltered ones.  A row-sharded handle answers the queries one
+ * by one through its filtered search (correct, not combined). */
+int32_t cqs_hip_index_search_filtered(cqs_hip_index* idx, const float* queries, uint32_t b, uint32_t query_dim,
+                                      uint32_t k, const uint32_t* keep_bitsets, uint64_t keep_stride_words,
+                                      uint32_t mode, float threshold,
+                                      uint64_t* out_rows, float* out_scores, uint32_t* out_counts);
+
 /* Combining-queue counters of a handle since it was made: passes the queue ran and the
- * queries they carried (queries / passes = mean callers per pass).  Either pointer may be
- * NULL.  Diagnostic; not part of the VectorIndex trait. */
+ * queries they carried (queries / passes = mean callers per pass), unfiltered callers only.
+ * Either pointer may be NULL.  Diagnostic; not part of the VectorIndex trait. */
 void cqs_hip_index_combine_stats(const cqs_hip_index* idx, uint64_t* passes, uint64_t* queries);
+/* The same two counters for the blocks of callers with a keep_bitset. */
+void cqs_hip_index_combine_filter_stats(const cqs_hip_index* idx, uint64_t* passes, uint64_t* queries);
 
 /* ---- bf16 shadow scan --------------------------------------------------------
  * Build (enable != 0) or free (enable == 0) a bf16 copy of the corpus that searches scan first.

@@ -95,6 +95,22 @@ extern "C" {
         out_scores: *mut f32,
         out_counts: *mut u32,
     ) -> i32;
+    // a block of queries with a keep-bitset each: per query the bytes of the call above with b = 1
+    fn cqs_hip_index_search_filtered(
+        idx: *mut CqsHipIndex,
+        queries: *const f32,
+        b: u32,
+        query_dim: u32,
+        k: u32,
+        keep_bitsets: *const u32,
+        keep_stride_words: u64,
+        mode: u32,
+        threshold: f32,
+        out_rows: *mut u64,
+        out_scores: *mut f32,
+        out_counts: *mut u32,
+    ) -> i32;
+    fn cqs_hip_index_combine_filter_stats(idx: *const CqsHipIndex, passes: *mut u64, queries: *mut u64);
 }
 
 /// Exact brute-force GPU index (HBM-resident `[n, dim]` f32 + top-k on device).
@@ -381,6 +397,65 @@ impl HipIndex {
         String::from_utf8_lossy(&buf[..n]).into_owned()
     }
 
+    /// (passes, queries) of the combined blocks of filtered callers since the index was opened (diagnostic).
+    pub fn combine_filter_stats(&self) -> (u64, u64) {
+        let (mut p, mut q) = (0u64, 0u64);
+        unsafe { cqs_hip_index_combine_filter_stats(self.handle, &mut p, &mut q) };
+        (p, q)
+    }
+
+    /// `search_with_filter` for several queries with a predicate each, in ONE call: the queries share passes over the
+    /// corpus, every one under its own bitset (`cqs_hip_index_search_filtered`), and each gets what its own
+    /// `search_with_filter` call returns.  A query of the wrong dimension gets an empty result.
+    pub fn search_many_with_filter(&self, queries: &[&Embedding], k: usize, filters: &[&dyn Fn(&str) -> bool]) -> Vec<Vec<IndexResult>> {
+        let b = queries.len();
+        if b == 0 || b != filters.len() || self.id_map.is_empty() || k == 0 || queries.iter().any(|q| q.len() != self.dim) {
+            return vec![Vec::new(); b];
+        }
+        let k = k.min(unsafe { cqs_hip_index_max_k(self.handle) } as usize);
+        let words = self.id_map.len().div_ceil(32);
+        let mut bitsets = vec![0u32; b * words];
+        for (j, filter) in filters.iter().enumerate() {
+            for (i, id) in self.id_map.iter().enumerate() {
+                if filter(id) {
+                    bitsets[j * words + i / 32] |= 1u32 << (i % 32);
+                }
+            }
+        }
+        let mut flat = Vec::with_capacity(b * self.dim);
+        for q in queries {
+            flat.extend_from_slice(q.as_slice());
+        }
+        let (mut rows, mut scores, mut counts) = (vec![0u64; b * k], vec![0f32; b * k], vec![0u32; b]);
+        let rc = unsafe {
+            cqs_hip_index_search_filtered(self.handle, flat.as_ptr(), b as u32, self.dim as u32, k as u32, bitsets.as_ptr(),
+                                          words as u64, CQS_HIP_MODE_RAW, 0.0, rows.as_mut_ptr(), scores.as_mut_ptr(),
+                                          counts.as_mut_ptr())
+        };
+        if rc != CQS_HIP_OK {
+            if unsafe { cqs_hip_index_poisoned(self.handle) } != 0 {
+                self.poisoned.store(true, Ordering::Release);
+            }
+            tracing::error!(error = %self.last_error(), rc, "HIP filtered block search failed");
+            return vec![Vec::new(); b];
+        }
+        (0..b)
+            .map(|j| {
+                (0..counts[j] as usize)
+                    .filter_map(|i| {
+                        self.id_map.get(rows[j * k + i] as usize).map(|id| IndexResult {
+                            id: id.to_string(),
+                            score: match self.metric {
+                                DistanceMetric::Cosine => scores[j * k + i].min(1.0),
+                                DistanceMetric::DotProduct => scores[j * k + i],
+                            },
+                        })
+                    })
+                    .collect()
+            })
+            .collect()
+    }
+
     fn search_impl(&self, query: &Embedding, k: usize, bitset: Option<&[u32]>) -> Vec<IndexResult> {
         let k = k.min(unsafe { cqs_hip_index_max_k(self.handle) } as usize);
         let mut rows = vec![0u64; k];
@@ -425,7 +500,8 @@ impl HipIndex {
 
 impl VectorIndex for HipIndex {
     /// Called concurrently from the daemon's client threads (src/cli/watch/daemon.rs:273) on one `Arc<dyn VectorIndex>`:
-    /// the library combines single-query, unfiltered calls that meet on the handle - single-device or sharded - into shared
+    /// the library combines single-query calls that meet on the handle - single-device or sharded; with a bitset
+    /// (`search_with_filter`): single-device, in blocks of their own, every query under its own bitset - into shared
     /// passes over the corpus (include/cqs_hip.h, "Concurrent callers"), each caller still getting the bytes its lone call
     /// would.  `CQS_HIP_COMBINE_BITS=relaxed` in the daemon's environment (read when the index is opened) trades that
     /// bit-reproducibility for throughput past 8 callers (blocks of >= 9 on the matrix cores; scores within 2e-6).
