@@ -760,6 +760,25 @@ static int32_t host_block(cqs_hip_index* x, const cqs_combine_req* const* qs, ui
     return CQS_HIP_OK;
 }
 
+// Kept rows of a host bitset over the handle's n rows (src/cagra.rs:747-775).
+static uint64_t count_kept(const cqs_hip_index* x, const uint32_t* keep_bitset) {
+    const uint64_t words = (x->n + 31) / 32;
+    uint64_t included = 0;
+    for (uint64_t w = 0; w < words; ++w) {
+        uint32_t v = keep_bitset[w];
+        if (w == words - 1 && (x->n % 32)) v &= (1u << (x->n % 32)) - 1u;
+        included += (uint64_t)__builtin_popcount(v);
+    }
+    return included;
+}
+
+// A query with a non-finite component has an empty result (src/cagra.rs:464-470).
+static bool query_finite(const float* q, uint32_t dim) {
+    bool ok = true;
+    for (uint32_t d = 0; d < dim; ++d) ok &= std::isfinite(q[d]);
+    return ok;
+}
+
 // The host-buffer search proper: `b` queries with one (k, mode, threshold, bitset), scanned in blocks the scratch
 // budget allows.  Caller holds mu, has checked the arguments and zeroed the counts.  `gemv_only`: every block goes
 // through the HBM-streaming passes of <= 8 queries, whose scores do not depend on how many queries share a pass (same
@@ -778,17 +797,11 @@ static int32_t search_host_locked(cqs_hip_index* x, const cqs_combine_req* qs, u
     const uint32_t* d_keep = nullptr;
     uint32_t k_eff = k;
     if (keep_bitset) {
-        const uint64_t words = (x->n + 31) / 32;
-        uint64_t included = 0;
-        for (uint64_t w = 0; w < words; ++w) {
-            uint32_t v = keep_bitset[w];
-            if (w == words - 1 && (x->n % 32)) v &= (1u << (x->n % 32)) - 1u;
-            included += (uint64_t)__builtin_popcount(v);
-        }
+        const uint64_t included = count_kept(x, keep_bitset);
         if (included == 0) return CQS_HIP_OK;                   // src/cagra.rs:765-767
         if (included < x->n) {                                  // all-pass == unfiltered, :760-762
             if (included < k_eff) k_eff = (uint32_t)included;   // :775
-            int32_t rck = stage_keep(x, keep_bitset, words);
+            int32_t rck = stage_keep(x, keep_bitset, (x->n + 31) / 32);
             if (rck != CQS_HIP_OK) return rck;
             d_keep = x->d_keep;
         }
@@ -805,8 +818,7 @@ static int32_t search_host_locked(cqs_hip_index* x, const cqs_combine_req* qs, u
         for (uint32_t i = 0; i < nb; ++i) {
             const float* src = qs[done + i].q;
             float* dst = x->h_q + (size_t)i * x->dim;
-            bool ok = true;
-            for (uint32_t d = 0; d < x->dim; ++d) ok &= std::isfinite(src[d]);
+            const bool ok = query_finite(src, x->dim);
             if (ok) memcpy(dst, src, (size_t)x->dim * sizeof(float));
             else memset(dst, 0, (size_t)x->dim * sizeof(float));
             staged.push_back(ok ? &qs[done + i] : nullptr);
@@ -821,18 +833,6 @@ static int32_t search_host_locked(cqs_hip_index* x, const cqs_combine_req* qs, u
         done += nb;
     }
     return CQS_HIP_OK;
-}
-
-// Kept rows of a host bitset over the handle's n rows (src/cagra.rs:747-775).
-static uint64_t count_kept(const cqs_hip_index* x, const uint32_t* keep_bitset) {
-    const uint64_t words = (x->n + 31) / 32;
-    uint64_t included = 0;
-    for (uint64_t w = 0; w < words; ++w) {
-        uint32_t v = keep_bitset[w];
-        if (w == words - 1 && (x->n % 32)) v &= (1u << (x->n % 32)) - 1u;
-        included += (uint64_t)__builtin_popcount(v);
-    }
-    return included;
 }
 
 // `b` queries with one (k, mode, threshold) and a bitset EACH (qs[i].keep), every one answered with the bytes of
@@ -872,9 +872,7 @@ static int32_t search_filtered_locked(cqs_hip_index* x, const cqs_combine_req* q
         if (rc != CQS_HIP_OK) return rc;
         for (; done < b && staged.size() < kCombineCap; ++done) {
             const cqs_combine_req& r = qs[done];
-            bool ok = true;
-            for (uint32_t d = 0; d < x->dim; ++d) ok &= std::isfinite(r.q[d]);
-            if (!ok || count_kept(x, r.keep) == 0) continue;          // src/cagra.rs:464-470, :765-767
+            if (!query_finite(r.q, x->dim) || count_kept(x, r.keep) == 0) continue;          // src/cagra.rs:464-470, :765-767
             memcpy(x->h_q + staged.size() * x->dim, r.q, (size_t)x->dim * sizeof(float));
             memcpy(x->h_keep_tab + staged.size() * x->keep_tab_stride, r.keep, words * sizeof(uint32_t));
             staged.push_back(&r);
@@ -1039,9 +1037,7 @@ int32_t cqs_hip_index_search(cqs_hip_index* x, const float* queries, uint32_t b,
         if (x->sh ? cqs_sharded::poisoned(x) != 0 : x->poisoned.load(std::memory_order_acquire))
             return CQS_HIP_ERR_POISONED;                                               // src/cagra.rs:486-490
         out_counts[0] = 0;
-        bool finite = true;
-        for (uint32_t d = 0; d < query_dim; ++d) finite &= std::isfinite(queries[d]);
-        if (!finite) return CQS_HIP_OK;                                                // src/cagra.rs:464-470
+        if (!query_finite(queries, query_dim)) return CQS_HIP_OK;                     // src/cagra.rs:464-470
         cqs_combine_req r{queries, k, mode, threshold, out_rows, out_scores, out_counts};
         r.keep = keep_bitset;
         return combine_search(x, r);
@@ -1202,9 +1198,10 @@ void cqs_hip_debug_index_fail_next(cqs_hip_index* x) CQS_ABI_TRY {
 // `n_queries` host rows, round and round) - what the reference's daemon does with one thread per client
 // (src/cli/watch/daemon.rs:273), without a Python interpreter lock between the callers.  out_rows / out_scores /
 // out_counts [n_queries, k] / [n_queries] receive each query's last answer.  Returns wall seconds, < 0 on a failed call.
-double cqs_hip_debug_client_storm(cqs_hip_index* x, const float* queries, uint32_t n_queries, uint32_t dim, uint32_t k,
-                                  uint32_t n_threads, uint32_t per_thread, uint64_t* out_rows, float* out_scores,
-                                  uint32_t* out_counts) CQS_ABI_TRY {
+// keep_bitsets (nullable): the call for query qi passes keep_bitsets + qi * keep_stride_words.
+static double client_storm(cqs_hip_index* x, const float* queries, uint32_t n_queries, uint32_t dim, uint32_t k,
+                           const uint32_t* keep_bitsets, uint64_t keep_stride_words, uint32_t n_threads, uint32_t per_thread,
+                           uint64_t* out_rows, float* out_scores, uint32_t* out_counts) {
     if (!x || !queries || !n_queries || !n_threads || !out_rows || !out_scores || !out_counts) return -1.0;
     std::atomic<int32_t> bad{0};
     std::atomic<uint32_t> ready{0};
@@ -1217,38 +1214,8 @@ double cqs_hip_debug_client_storm(cqs_hip_index* x, const float* queries, uint32
             while (!go.load(std::memory_order_acquire)) std::this_thread::yield();
             uint32_t qi = t % n_queries;
             for (uint32_t i = 0; i < per_thread; ++i) {
-                const int32_t rc = cqs_hip_index_search(x, queries + (size_t)qi * dim, 1, dim, k, nullptr, CQS_HIP_MODE_RAW, 0.f,
-                                                        out_rows + (size_t)qi * k, out_scores + (size_t)qi * k, out_counts + qi);
-                if (rc != CQS_HIP_OK) { bad.store(rc); break; }
-                qi = (qi + n_threads) % n_queries;
-            }
-        });
-    while (ready.load() < n_threads) std::this_thread::yield();
-    const auto t0 = std::chrono::steady_clock::now();
-    go.store(true, std::memory_order_release);
-    for (std::thread& t : th) t.join();
-    const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return bad.load() ? -1.0 : el;
-} CQS_ABI_CATCH_VAL(-1.0)
-
-// The same storm with one bitset per query row: thread t's call for query qi passes keep_bitsets + qi * keep_stride_words.
-double cqs_hip_debug_client_storm_filtered(cqs_hip_index* x, const float* queries, uint32_t n_queries, uint32_t dim, uint32_t k,
-                                           const uint32_t* keep_bitsets, uint64_t keep_stride_words, uint32_t n_threads,
-                                           uint32_t per_thread, uint64_t* out_rows, float* out_scores,
-                                           uint32_t* out_counts) CQS_ABI_TRY {
-    if (!x || !queries || !n_queries || !n_threads || !keep_bitsets || !out_rows || !out_scores || !out_counts) return -1.0;
-    std::atomic<int32_t> bad{0};
-    std::atomic<uint32_t> ready{0};
-    std::atomic<bool> go{false};
-    std::vector<std::thread> th;
-    th.reserve(n_threads);
-    for (uint32_t t = 0; t < n_threads; ++t)
-        th.emplace_back([&, t]() {
-            ready.fetch_add(1);
-            while (!go.load(std::memory_order_acquire)) std::this_thread::yield();
-            uint32_t qi = t % n_queries;
-            for (uint32_t i = 0; i < per_thread; ++i) {
-                const int32_t rc = cqs_hip_index_search(x, queries + (size_t)qi * dim, 1, dim, k, keep_bitsets + (size_t)qi * keep_stride_words,
+                const int32_t rc = cqs_hip_index_search(x, queries + (size_t)qi * dim, 1, dim, k,
+                                                        keep_bitsets ? keep_bitsets + (size_t)qi * keep_stride_words : nullptr,
                                                         CQS_HIP_MODE_RAW, 0.f, out_rows + (size_t)qi * k, out_scores + (size_t)qi * k,
                                                         out_counts + qi);
                 if (rc != CQS_HIP_OK) { bad.store(rc); break; }
@@ -1261,6 +1228,22 @@ double cqs_hip_debug_client_storm_filtered(cqs_hip_index* x, const float* querie
     for (std::thread& t : th) t.join();
     const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
     return bad.load() ? -1.0 : el;
+}
+
+double cqs_hip_debug_client_storm(cqs_hip_index* x, const float* queries, uint32_t n_queries, uint32_t dim, uint32_t k,
+                                  uint32_t n_threads, uint32_t per_thread, uint64_t* out_rows, float* out_scores,
+                                  uint32_t* out_counts) CQS_ABI_TRY {
+    return client_storm(x, queries, n_queries, dim, k, nullptr, 0, n_threads, per_thread, out_rows, out_scores, out_counts);
+} CQS_ABI_CATCH_VAL(-1.0)
+
+// The same storm with one bitset per query row.
+double cqs_hip_debug_client_storm_filtered(cqs_hip_index* x, const float* queries, uint32_t n_queries, uint32_t dim, uint32_t k,
+                                           const uint32_t* keep_bitsets, uint64_t keep_stride_words, uint32_t n_threads,
+                                           uint32_t per_thread, uint64_t* out_rows, float* out_scores,
+                                           uint32_t* out_counts) CQS_ABI_TRY {
+    if (!keep_bitsets) return -1.0;
+    return client_storm(x, queries, n_queries, dim, k, keep_bitsets, keep_stride_words, n_threads, per_thread, out_rows,
+                        out_scores, out_counts);
 } CQS_ABI_CATCH_VAL(-1.0)
 
 }  // extern "C"

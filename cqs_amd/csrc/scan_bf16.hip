@@ -17,18 +17,14 @@
 #include "scan_i8.h"
 #include "launch_util.h"
 #include "rank_sort.h"
-#include "scan_device.h"
+#include "scan_gemv_device.h"
 #include "select_device.h"
 
 namespace cqs {
 
 static_assert(kShadowKMax == kMaxK, "shadow k' policy and the select agree on max k");
 
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef unsigned u4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(4))) uint32_t kc32;
 
 __device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }          // component 2i
 __device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 0xFFFF0000u); }  // component 2i + 1
@@ -162,8 +158,7 @@ __global__ __launch_bounds__(256) void scan_bf16_kernel(const Bf16ScanParams p) 
     const uint32_t total_waves = gridDim.x * wpb;
     const uint32_t wave_id = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * wpb + (threadIdx.x >> 6)));
     const bool use_queue = n_tasks > total_waves;
-    uint32_t opaque_zero;   // (see scan_gemv_kernel: keeps the dequeue a plain returning atomic)
-    asm volatile("v_mov_b32 %0, 0" : "=v"(opaque_zero));
+    const uint32_t zero = opaque_zero();   // (keeps the dequeue a plain returning atomic)
 
     const char* const rows_b = (const char*)p.rows;
     const uint32_t row_bytes = dim * 2u;
@@ -284,7 +279,7 @@ __global__ __launch_bounds__(256) void scan_bf16_kernel(const Bf16ScanParams p) 
         const uint32_t base = p.tiers.locate(cur, trows);
         const uint64_t mask = task_mask(base, trows);
         uint32_t ticket = 0;
-        if (use_queue && lane == 0) ticket = atomicAdd(p.work + opaque_zero, 1u);
+        if (use_queue && lane == 0) ticket = atomicAdd(p.work + zero, 1u);
         float sc[BQ];
 #pragma unroll
         for (int b = 0; b < BQ; ++b) sc[b] = -INFINITY;
@@ -311,31 +306,18 @@ template <int NCH, int BQ, int RI, bool PQ>
 static hipError_t launch_bf16(const ScanArgs& a, const uint16_t* shadow, const float* bq, uint32_t q0, uint32_t nq,
                               uint32_t work_slot, hipStream_t st) {
     Bf16ScanParams p;
-    p.rows = shadow; p.n = a.n; p.n_pad = a.n_pad; p.dim = a.dim;
-    p.q = a.q + (size_t)q0 * a.dim;
-    p.scores = a.scores + (size_t)q0 * a.n_pad;
-    p.keep = PQ ? a.keep_tab : a.keep; p.mode = a.mode; p.thr = a.threshold;
-    p.keep_stride = PQ ? a.keep_stride : 0u;
-    for (uint32_t i = 0; i < kMaxGemvQ; ++i) p.slot[i] = (PQ && i < nq) ? a.keep_slot[q0 + i] : (uint8_t)0;
-    p.nq = nq;
+    fill_gemv_pass(p, a, q0, nq, PQ);
+    p.rows = shadow;
     p.work = a.work + work_slot;
-    p.tiers = a.tiers;
-    p.n_tasks = a.tiers.total();
-    p.gmax = a.gmax + (size_t)q0 * p.n_tasks;
-    p.gaux = a.gaux ? a.gaux + (size_t)q0 * p.n_tasks : nullptr;
     p.bq = bq + q0;
     const bool one_shot = p.n_tasks <= a.n_cu * 4u * CQS_BF16_ONE_SHOT;
     const uint32_t wpb = 4u;
     const uint32_t blocks = one_shot ? (p.n_tasks + wpb - 1u) / wpb : a.n_cu * CQS_BF16_BLOCKS_PER_CU;
     const dim3 grid(blocks), block(64u * wpb);
     const bool full = (a.dim == (uint32_t)NCH * 512u);
-    if (a.nontemporal) {
-        if (full) hipLaunchKernelGGL((scan_bf16_kernel<NCH, BQ, RI, true, true, PQ>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((scan_bf16_kernel<NCH, BQ, RI, true, false, PQ>), grid, block, 0, st, p);
-    } else {
-        if (full) hipLaunchKernelGGL((scan_bf16_kernel<NCH, BQ, RI, false, true, PQ>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((scan_bf16_kernel<NCH, BQ, RI, false, false, PQ>), grid, block, 0, st, p);
-    }
+    for_nt_full(a.nontemporal, full, [&](auto nt_c, auto full_c) {
+        hipLaunchKernelGGL((scan_bf16_kernel<NCH, BQ, RI, decltype(nt_c)::value, decltype(full_c)::value, PQ>), grid, block, 0, st, p);
+    });
     return hipGetLastError();
 }
 
@@ -365,7 +347,7 @@ static hipError_t launch_bf16_groups(const ScanArgs& a, const uint16_t* shadow, 
 hipError_t launch_scan_bf16(const ScanArgs& a, const uint16_t* shadow, const float* bq, hipStream_t st) {
     if (a.b == 0 || a.n == 0) return hipSuccess;
     if (a.b > kShadowMaxQ || a.dim % 8u != 0u || a.dim > kShadowMaxDim) return hipErrorInvalidValue;
-    if (a.keep_tab && (a.keep || !a.keep_slot || a.keep_stride < (a.n + 31u) / 32u)) return hipErrorInvalidValue;
+    if (a.keep_tab && !keep_tab_ok(a)) return hipErrorInvalidValue;
     switch ((a.dim + 511u) / 512u) {
         case 1: return a.keep_tab ? launch_bf16_groups<1, true>(a, shadow, bq, st) : launch_bf16_groups<1, false>(a, shadow, bq, st);
         case 2: return a.keep_tab ? launch_bf16_groups<2, true>(a, shadow, bq, st) : launch_bf16_groups<2, false>(a, shadow, bq, st);

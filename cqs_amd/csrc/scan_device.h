@@ -1,10 +1,17 @@
-// scan_device.h — device helpers shared by the f32 scan (scan_kernels.hip) and the bf16 shadow scan (scan_bf16.hip):
-// the ordered score keys and the transposed butterfly.  Internal to libcqs_hip.so.
+// scan_device.h — device helpers shared by the scan kernels (the f32 scan scan_kernels.hip, the shadow scans scan_bf16.hip
+// and scan_i8.hip) and the select (select_device.h): the vector typedefs, the ordered score keys and the transposed
+// butterfly.  What only the three HBM-streaming scans' launchers and dequeue share is in scan_gemv_device.h.
+// Internal to libcqs_hip.so.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 namespace cqs {
+
+typedef float f4 __attribute__((ext_vector_type(4)));
+typedef float f2 __attribute__((ext_vector_type(2)));
+typedef unsigned u4 __attribute__((ext_vector_type(4)));
+typedef __attribute__((address_space(4))) uint32_t kc32;   // constant address space: uniform addresses load through the scalar cache
 
 // ---- ordered keys ----------------------------------------------------------
 // f32 -> u32 preserving IEEE total order (what Rust's f32::total_cmp sorts by).

@@ -9,14 +9,9 @@
 // Wave = 64 lanes.  gfx950 only.
 #include "scan_i8.h"
 #include "launch_util.h"
-#include "scan_device.h"
+#include "scan_gemv_device.h"
 
 namespace cqs {
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(4))) uint32_t kc32;
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef unsigned u4 __attribute__((ext_vector_type(4)));
 
 // byte i of w as a signed code, converted (exact)
 template <int I>
@@ -308,28 +303,15 @@ template <int NCH, int BQ, int RI, bool PQ>
 static hipError_t launch_i8(const ScanArgs& a, const int8_t* codes, const float* scales, const float* bq, uint32_t q0,
                             uint32_t nq, hipStream_t st) {
     I8ScanParams p;
-    p.rows = codes; p.scales = scales; p.n = a.n; p.n_pad = a.n_pad; p.dim = a.dim;
-    p.q = a.q + (size_t)q0 * a.dim;
-    p.scores = a.scores + (size_t)q0 * a.n_pad;
-    p.keep = PQ ? a.keep_tab : a.keep; p.mode = a.mode; p.thr = a.threshold;
-    p.keep_stride = PQ ? a.keep_stride : 0u;
-    for (uint32_t i = 0; i < kMaxGemvQ; ++i) p.slot[i] = (PQ && i < nq) ? a.keep_slot[q0 + i] : (uint8_t)0;
-    p.nq = nq;
-    p.tiers = a.tiers;
-    p.n_tasks = a.tiers.total();
-    p.gmax = a.gmax + (size_t)q0 * p.n_tasks;
-    p.gaux = a.gaux ? a.gaux + (size_t)q0 * p.n_tasks : nullptr;
+    fill_gemv_pass(p, a, q0, nq, PQ);
+    p.rows = codes; p.scales = scales;
     p.bq = bq + q0;
     const uint32_t wpb = 4u;
     const dim3 grid((p.n_tasks + wpb - 1u) / wpb), block(64u * wpb);
     const bool full = (a.dim == (uint32_t)NCH * 1024u);
-    if (a.nontemporal) {
-        if (full) hipLaunchKernelGGL((scan_i8_kernel<NCH, BQ, RI, true, true, PQ>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((scan_i8_kernel<NCH, BQ, RI, true, false, PQ>), grid, block, 0, st, p);
-    } else {
-        if (full) hipLaunchKernelGGL((scan_i8_kernel<NCH, BQ, RI, false, true, PQ>), grid, block, 0, st, p);
-        else hipLaunchKernelGGL((scan_i8_kernel<NCH, BQ, RI, false, false, PQ>), grid, block, 0, st, p);
-    }
+    for_nt_full(a.nontemporal, full, [&](auto nt_c, auto full_c) {
+        hipLaunchKernelGGL((scan_i8_kernel<NCH, BQ, RI, decltype(nt_c)::value, decltype(full_c)::value, PQ>), grid, block, 0, st, p);
+    });
     return hipGetLastError();
 }
 
@@ -352,7 +334,7 @@ static hipError_t launch_i8_groups(const ScanArgs& a, const int8_t* codes, const
 hipError_t launch_scan_i8(const ScanArgs& a, const int8_t* codes, const float* scales, const float* bq, hipStream_t st) {
     if (a.b == 0 || a.n == 0) return hipSuccess;
     if (a.b > kShadowMaxQ || !i8_dim_ok(a.dim)) return hipErrorInvalidValue;
-    if (a.keep_tab && (a.keep || !a.keep_slot || a.keep_stride < (a.n + 31u) / 32u)) return hipErrorInvalidValue;
+    if (a.keep_tab && !keep_tab_ok(a)) return hipErrorInvalidValue;
     switch ((a.dim + 1023u) / 1024u) {
         case 1: return a.keep_tab ? launch_i8_groups<1, true>(a, codes, scales, bq, st) : launch_i8_groups<1, false>(a, codes, scales, bq, st);
         case 2: return a.keep_tab ? launch_i8_groups<2, true>(a, codes, scales, bq, st) : launch_i8_groups<2, false>(a, codes, scales, bq, st);

@@ -89,6 +89,11 @@ inline bool uniform_groups(uint32_t b, uint32_t dim) { return use_mfma(b, dim); 
 
 bool scan_dim_supported(uint32_t dim);
 
+// ScanArgs::keep_tab is usable by a gemv launch: no shared bitset beside it, a slot per query, rows that cover the corpus.
+inline bool keep_tab_ok(const ScanArgs& a) {
+    return !a.keep && a.keep_slot && a.keep_stride >= (a.n + 31u) / 32u;
+}
+
 #if defined(__HIPCC__)
 // The f32 fallback gate of the device-API shadow search (index.hip, cqs_hip_index_search_device): true when gate[0, b)
 // are all 1.  Invariants, kept by every kernel that takes a gate:

@@ -21,15 +21,10 @@
 // Wave = 64 lanes.  gfx950 only.
 #include "scan_kernels.h"
 #include "launch_util.h"
-#include "scan_device.h"
+#include "scan_gemv_device.h"
 #include "select_device.h"
 
 namespace cqs {
-
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef float f2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(1))) uint32_t gu32;
-typedef __attribute__((address_space(4))) uint32_t kc32;
 
 
 // ---- scan ------------------------------------------------------------------
@@ -103,12 +98,7 @@ __global__ __launch_bounds__(256, OCC) void scan_gemv_kernel(const ScanParams p)
     // shared queue, whose tickets count from #waves.  (One queue word sustains only ~88 dequeues/us: a
     // start-up burst from every wave would cost 10-25 us.)
     const bool use_queue = n_tasks > total_waves;
-    // A zero the compiler cannot see through.  With a provably uniform address hipcc rewrites the
-    // dequeue into a wave-aggregated atomic followed at once by s_waitcnt vmcnt(0) + readfirstlane,
-    // draining every row load in flight.  A "divergent" address keeps the plain returning atomic,
-    // whose ticket is only waited for where it is used.
-    uint32_t opaque_zero;
-    asm volatile("v_mov_b32 %0, 0" : "=v"(opaque_zero));
+    const uint32_t zero = opaque_zero();   // (keeps the dequeue a plain returning atomic)
     if (p.dbg && lane == 0 && wave_id < kDbgWaves) p.dbg[16u + 2u * wave_id] = __builtin_amdgcn_s_memrealtime();
 
     // issue the RI*NCH row loads of batch j of the task at `base` back to back (all in flight together).
@@ -275,14 +265,14 @@ __global__ __launch_bounds__(256, OCC) void scan_gemv_kernel(const ScanParams p)
                 load_rows(base, 2 * s + 1, xb);
                 // the dequeue goes out behind row loads already in flight: vmcnt retires in issue
                 // order, so an atomic issued ahead of them would stall the first reduction
-                if (s == 0 && use_queue && lane == 0) ticket = atomicAdd(p.work + opaque_zero, 1u);
+                if (s == 0 && use_queue && lane == 0) ticket = atomicAdd(p.work + zero, 1u);
                 reduce_rows(2 * s, xa, sc);
                 if (s + 1 < steps) load_rows(base, 2 * s + 2, xa);
                 reduce_rows(2 * s + 1, xb, sc);
             }
             epilogue(cur, base, trows, mask, sc);
         } else {
-            if (use_queue && lane == 0) ticket = atomicAdd(p.work + opaque_zero, 1u);
+            if (use_queue && lane == 0) ticket = atomicAdd(p.work + zero, 1u);
             sparse_task(cur, base, trows, mask);
         }
         cur = claimed(ticket);
@@ -368,18 +358,9 @@ template <int NCH, int BQ, int RI, bool PQ>
 static hipError_t launch_gemv(const ScanArgs& a, uint32_t q0, uint32_t nq, uint32_t work_slot, hipStream_t st) {
     constexpr int PIPE = (BQ <= 2) ? CQS_SCAN_PIPE : 0;
     ScanParams p;
-    p.rows = a.rows; p.n = a.n; p.n_pad = a.n_pad; p.dim = a.dim;
-    p.q = a.q + (size_t)q0 * a.dim;
-    p.scores = a.scores + (size_t)q0 * a.n_pad;
-    p.keep = PQ ? a.keep_tab : a.keep; p.mode = a.mode; p.thr = a.threshold;
-    p.keep_stride = PQ ? a.keep_stride : 0u;
-    for (uint32_t i = 0; i < kMaxGemvQ; ++i) p.slot[i] = (PQ && i < nq) ? a.keep_slot[q0 + i] : (uint8_t)0;
-    p.nq = nq;
+    fill_gemv_pass(p, a, q0, nq, PQ);
+    p.rows = a.rows;
     p.work = a.work + work_slot;
-    p.tiers = a.tiers;
-    p.n_tasks = a.tiers.total();
-    p.gmax = a.gmax + (size_t)q0 * p.n_tasks;
-    p.gaux = a.gaux ? a.gaux + (size_t)q0 * p.n_tasks : nullptr;
     p.dbg = (unsigned long long*)a.dbg;
     p.gate = a.gate;
     p.gate_n = a.b;
@@ -409,22 +390,22 @@ static hipError_t launch_gemv(const ScanArgs& a, uint32_t q0, uint32_t nq, uint3
 #else
     const bool nt = a.nontemporal;
 #endif
-#define CQS_LAUNCH(NTV, FULLV, OCCV) \
-    do {                                                                                                     \
-        auto kern = scan_gemv_kernel<NCH, BQ, RI, NTV, FULLV, PIPE, OCCV, PQ>;                               \
-        if (occ_lds > 64u * 1024u) {                                                                         \
-            static DynLdsOnce once;   /* per instantiation: the attribute is set once per device, not per launch */ \
-            hipError_t e = once.ensure((const void*)kern, occ_lds);                                          \
-            if (e != hipSuccess) return e;                                                                   \
-        }                                                                                                    \
-        hipLaunchKernelGGL(kern, grid, block, occ_lds, st, p);                                               \
-    } while (0)
+    auto launch = [&](auto nt_c, auto full_c, auto occ_c) -> hipError_t {
+        auto kern = scan_gemv_kernel<NCH, BQ, RI, decltype(nt_c)::value, decltype(full_c)::value, PIPE, decltype(occ_c)::value, PQ>;
+        if (occ_lds > 64u * 1024u) {
+            static DynLdsOnce once;   // per instantiation: the attribute is set once per device, not per launch
+            hipError_t e = once.ensure((const void*)kern, occ_lds);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL(kern, grid, block, occ_lds, st, p);
+        return hipGetLastError();
+    };
     // small corpora never stream past the caches: their OCC = 2 variant is built without nt loads only
-    if (small && PIPE == 1) { if (full) CQS_LAUNCH(false, true, 2); else CQS_LAUNCH(false, false, 2); }
-    else if (nt) { if (full) CQS_LAUNCH(true, true, 1); else CQS_LAUNCH(true, false, 1); }
-    else { if (full) CQS_LAUNCH(false, true, 1); else CQS_LAUNCH(false, false, 1); }
-#undef CQS_LAUNCH
-    return hipGetLastError();
+    if (small && PIPE == 1) {
+        const std::integral_constant<int, 2> occ2;
+        return full ? launch(std::false_type{}, std::true_type{}, occ2) : launch(std::false_type{}, std::false_type{}, occ2);
+    }
+    return for_nt_full(nt, full, [&](auto nt_c, auto full_c) { return launch(nt_c, full_c, std::integral_constant<int, 1>{}); });
 }
 
 template <int NCH, bool PQ>
@@ -478,7 +459,7 @@ hipError_t launch_scan(const ScanArgs& a, hipStream_t st) {
     }
     const uint32_t nch = (a.dim + 255u) / 256u;
     if (a.keep_tab) {   // one bitset per query: the PQ instantiations (gemv passes only; the matrix-core kernel has none)
-        if (a.keep || !a.keep_slot || a.keep_stride < (a.n + 31u) / 32u) return hipErrorInvalidValue;
+        if (!keep_tab_ok(a)) return hipErrorInvalidValue;
         switch (nch) {
 #define CQS_PQ_CASE(N) case N: return launch_gemv_groups<N, true>(a, st);
             CQS_PQ_CASE(1) CQS_PQ_CASE(2) CQS_PQ_CASE(3) CQS_PQ_CASE(4) CQS_PQ_CASE(5) CQS_PQ_CASE(6) CQS_PQ_CASE(7) CQS_PQ_CASE(8)
