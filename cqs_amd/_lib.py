@@ -26,6 +26,7 @@ MODE_RAW = 0
 MODE_PIPELINE = 1
 MAX_K = 1024
 NEIGHBORS_MAX = 100
+MMR_MAX = 1024
 
 _c_idx = C.c_void_p
 _pp = C.POINTER
@@ -73,6 +74,9 @@ SIGNATURES = [
     ("cqs_hip_index_bf16_stats", None, [_c_idx, _pp(C.c_uint64), _pp(C.c_uint64), _pp(C.c_uint64)]),
     ("cqs_hip_index_i8_stats", None, [_c_idx, _pp(C.c_uint64), _pp(C.c_uint64), _pp(C.c_uint64)]),
     ("cqs_hip_index_neighbors", C.c_int32, [_c_idx, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, _pp(C.c_uint32)]),
+    ("cqs_hip_index_pairwise", C.c_int32, [_c_idx, C.c_void_p, C.c_uint32, C.c_void_p]),
+    ("cqs_hip_index_mmr", C.c_int32,
+     [_c_idx, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, _pp(C.c_uint32)]),
     ("cqs_hip_unpack_keys", None, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     ("cqs_hip_merge_keys", C.c_size_t,
      [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p]),

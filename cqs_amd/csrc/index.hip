@@ -585,6 +585,7 @@ void cqs_hip_index_destroy(cqs_hip_index* x) CQS_ABI_TRY {
     hipSetDevice(x->device);
     (void)quiesce(x);  // src/cagra.rs:289-302 (incl. searches enqueued on caller streams)
     free_scratch(x);
+    cqs_mmr::free_scratch(x);
     shadow_free(x);
     hipFree(x->d_keep);
     free_keep_tab(x);

@@ -16,6 +16,7 @@
 
 namespace cqs_sharded { struct ShardSet; }
 namespace cqs_idx { struct Shadow; }
+namespace cqs_mmr { struct Scratch; }
 
 // One single-query host search: its query, parameters and output buffers (the caller's own).  The combining queue of
 // cqs_hip_index_search parks these on their callers' stacks; the host search runs blocks of them (index.hip).
@@ -113,6 +114,9 @@ struct cqs_hip_index {
     cqs_idx::Shadow* shadow = nullptr;
     std::atomic<uint64_t> stat_certified{0}, stat_fallbacks{0};
     std::atomic<uint64_t> stat_i8_certified{0}, stat_i8_fallbacks{0};   // those of them that the int8 copy served
+
+    // Scratch of cqs_hip_index_pairwise / cqs_hip_index_mmr (mmr.hip; null until the first such call on this handle).
+    cqs_mmr::Scratch* mmr = nullptr;
 };
 
 namespace cqs_idx {
@@ -188,8 +192,26 @@ int32_t read_blob_into(int fd, uint64_t checksum, uint32_t dim, const std::vecto
 
 }  // namespace cqs_idx
 
+// Pairwise similarities and the MMR re-rank of a candidate pool (mmr.hip).  Caller holds the owner's mutex.
+namespace cqs_mmr {
+void free_scratch(cqs_hip_index* x);   // (sets the owner's device)
+// G = X X^T over the m rows src[h_idx[i]] (h_idx null: rows 0 .. m-1 of src), then either the D2H of G (out_gram [m, m]) or
+// the greedy loop and the D2H of its `limit` picks (out_gram null; 0 < limit < m, lambda in [0, 1)).  `src` lies on
+// owner->device, the work runs on `st`; scratch and errors belong to `owner`.  Returns with the outputs written.
+int32_t run(cqs_hip_index* owner, hipStream_t st, const float* src, const uint32_t* h_idx, const float* h_scores, uint32_t m,
+            uint32_t limit, float lambda, float* out_gram, uint32_t* out_picks);
+// A shard's part of a sharded pool: its mc candidates' rows (local indices h_idx) gathered on c->stream into the dense
+// [mc, dim] block *out_block of c's own scratch.  Errors are left on c.
+int32_t gather_rows(cqs_hip_index* c, const uint32_t* h_idx, uint32_t mc, const float** out_block);
+// The parent's [m, dim] staging block on its first device.
+int32_t staging(cqs_hip_index* parent, uint32_t m, float** out_block);
+}  // namespace cqs_mmr
+
 // Row-sharded parent handles (sharded.hip); each takes the parent handle and does its own locking.
 namespace cqs_sharded {
+int32_t pairwise(cqs_hip_index* parent, const uint64_t* cand_rows, uint32_t m, float* out);
+int32_t mmr(cqs_hip_index* parent, const uint64_t* cand_rows, const float* cand_scores, uint32_t m, uint32_t limit,
+            float lambda, uint32_t* out_picks, uint32_t* out_count);
 void destroy(cqs_hip_index* parent);
 int32_t search(cqs_hip_index* parent, const float* queries, uint32_t b, uint32_t query_dim, uint32_t k,
                const uint32_t* keep_bitset, uint32_t mode, float threshold, uint64_t* out_rows, float* out_scores,

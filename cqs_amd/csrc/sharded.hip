@@ -25,6 +25,7 @@
 #include "abi_guard.h"
 #include "roctx.h"
 #include "index_internal.h"
+#include "mmr_host.h"
 
 using namespace cqs_idx;
 
@@ -318,6 +319,7 @@ void destroy(cqs_hip_index* p) {
         if (ss->ev[s]) { (void)hipSetDevice(ss->shard[s]->device); (void)hipEventDestroy(ss->ev[s]); }
     if (ss->h_q) (void)hipHostFree(ss->h_q);
     if (ss->h_counts) (void)hipHostFree(ss->h_counts);
+    cqs_mmr::free_scratch(p);
     for (cqs_hip_index* c : ss->shard) cqs_hip_index_destroy(c);
     delete ss;
     p->sh = nullptr;
@@ -492,6 +494,127 @@ int32_t neighbors(cqs_hip_index* p, uint64_t target_row, uint32_t limit, uint64_
         ++outc;
     }
     *out_count = outc;
+    return CQS_HIP_OK;
+}
+
+// A candidate pool of a sharded handle, brought together on the first shard's device: every shard gathers ITS candidates'
+// rows into a dense block on its own stream, the blocks are copied device to device, back to back in shard order, into
+// one [m, dim] staging block, and slot[i] names candidate i's row there (one copy per shard; a staging block in candidate
+// order would take one copy per run of candidates of one shard, ~m of them on a score-ordered pool).  The two kernels of
+// mmr.hip then read the staging block through `slot` exactly as they read a single-device handle's rows through its
+// candidates' rows: an entry of G depends on its two rows alone, so the bytes are the single-device handle's.  The
+// caller holds the parent mutex; the first shard's mutex is taken into `first` (the kernels run on its stream) and is
+// released here on a failure, by the caller's scope otherwise.
+static int32_t stage_pool(cqs_hip_index* p, const uint64_t* cand_rows, uint32_t m, float** d_stage, std::vector<uint32_t>& slot,
+                          std::unique_lock<std::mutex>& first) {
+    ShardSet* ss = p->sh;
+    const size_t G = ss->shard.size();
+    std::vector<std::vector<uint32_t>> local(G);
+    std::vector<uint32_t> owner(m), pos(m);
+    for (uint32_t i = 0; i < m; ++i) {
+        const uint64_t r = cand_rows[i] - p->row_base;
+        size_t o = 0;
+        for (size_t s = 0; s < G; ++s)
+            if (ss->shard[s]->n && r >= ss->lo[s] && r < ss->lo[s] + ss->shard[s]->n) o = s;
+        owner[i] = (uint32_t)o;
+        pos[i] = (uint32_t)local[o].size();
+        local[o].push_back((uint32_t)(r - ss->lo[o]));
+    }
+    std::vector<uint32_t> off(G + 1, 0);
+    for (size_t s = 0; s < G; ++s) off[s + 1] = off[s] + (uint32_t)local[s].size();
+    slot.resize(m);
+    for (uint32_t i = 0; i < m; ++i) slot[i] = off[owner[i]] + pos[i];
+    cqs_hip_index* c0 = ss->shard[0];
+    P_TRY(p, hipSetDevice(c0->device));
+    int32_t rc = cqs_mmr::staging(p, m, d_stage);
+    if (rc != CQS_HIP_OK) return rc;
+    first = std::unique_lock<std::mutex>(c0->mu);
+    if (c0->poisoned.load(std::memory_order_acquire)) { first.unlock(); return child_fail(p, 0, CQS_HIP_ERR_POISONED); }
+    P_TRY(p, order_after_last(c0, c0->stream));
+    // A shard's mutex is held while its gather is enqueued and dropped at the end of its turn, with the copy out of its
+    // block still only queued on c0->stream: children are reached under the parent mutex alone (held by the caller until
+    // cqs_mmr::run has synchronised c0->stream), so nobody can touch that block before the copy has run.  The gather
+    // reads d_rows and writes the shard's own MMR block, never the search scratch, so shards other than the first are not
+    // ordered behind their last search (order_after_last); the first is, because the kernels run on its stream.
+    for (size_t s = 0; s < G; ++s) {
+        if (local[s].empty()) continue;
+        cqs_hip_index* c = ss->shard[s];
+        std::unique_lock<std::mutex> g;
+        if (s != 0) {
+            g = std::unique_lock<std::mutex>(c->mu);
+            // (child_fail takes c->mu itself: release it first)
+            if (c->poisoned.load(std::memory_order_acquire)) { g.unlock(); first.unlock(); return child_fail(p, s, CQS_HIP_ERR_POISONED); }
+        }
+        const uint32_t mc = (uint32_t)local[s].size();
+        const float* blk = nullptr;
+        hipError_t e = hipSetDevice(c->device);
+        if (e == hipSuccess) {
+            if ((rc = cqs_mmr::gather_rows(c, local[s].data(), mc, &blk)) != CQS_HIP_OK) {
+                if (g.owns_lock()) g.unlock();
+                first.unlock();
+                return child_fail(p, s, rc);
+            }
+            if (s != 0) {
+                e = hipEventRecord(ss->ev[s], c->stream);
+                if (e == hipSuccess) e = hipSetDevice(c0->device);
+                if (e == hipSuccess) e = hipStreamWaitEvent(c0->stream, ss->ev[s], 0);
+            }
+        }
+        if (e == hipSuccess)
+            e = hipMemcpyAsync(*d_stage + (size_t)off[s] * p->dim, blk, (size_t)mc * p->dim * sizeof(float), hipMemcpyDefault, c0->stream);
+        if (e != hipSuccess) {
+            first.unlock();
+            return pfail(p, CQS_HIP_ERR_DEVICE, std::string("mmr: gathering the pool: ") + hipGetErrorString(e));
+        }
+    }
+    const hipError_t e = hipSetDevice(c0->device);
+    if (e != hipSuccess) { first.unlock(); return pfail(p, CQS_HIP_ERR_DEVICE, std::string("hipSetDevice: ") + hipGetErrorString(e)); }
+    return CQS_HIP_OK;
+}
+
+int32_t pairwise(cqs_hip_index* p, const uint64_t* cand_rows, uint32_t m, float* out) {
+    std::lock_guard<std::mutex> g(p->mu);
+    if (poisoned(p)) return CQS_HIP_ERR_POISONED;
+    const char* why = "";
+    const cqs_mmr::Plan plan = cqs_mmr::check_rows(cand_rows, m, p->row_base, len(p), &why);
+    if (plan == cqs_mmr::Plan::Invalid) return pfail(p, CQS_HIP_ERR_INVALID, why);
+    if (plan == cqs_mmr::Plan::Empty) return CQS_HIP_OK;
+    if (!out) return pfail(p, CQS_HIP_ERR_INVALID, "pairwise: null output buffer");
+    float* d_stage = nullptr;
+    std::vector<uint32_t> slot;
+    std::unique_lock<std::mutex> first;
+    int32_t rc = stage_pool(p, cand_rows, m, &d_stage, slot, first);
+    if (rc != CQS_HIP_OK) return rc;
+    cqs_hip_index* c0 = p->sh->shard[0];
+    if ((rc = cqs_mmr::run(p, c0->stream, d_stage, slot.data(), nullptr, m, 0, 0.f, out, nullptr)) != CQS_HIP_OK) return rc;
+    P_TRY(p, record_done(c0, c0->stream));
+    return CQS_HIP_OK;
+}
+
+int32_t mmr(cqs_hip_index* p, const uint64_t* cand_rows, const float* cand_scores, uint32_t m, uint32_t limit, float lambda,
+            uint32_t* out_picks, uint32_t* out_count) {
+    std::lock_guard<std::mutex> g(p->mu);
+    *out_count = 0;
+    if (poisoned(p)) return CQS_HIP_ERR_POISONED;
+    const char* why = "";
+    const cqs_mmr::Plan plan = cqs_mmr::plan_mmr(cand_rows, cand_scores, m, p->row_base, len(p), &limit, &lambda, &why);
+    if (plan == cqs_mmr::Plan::Invalid) return pfail(p, CQS_HIP_ERR_INVALID, why);
+    if (plan == cqs_mmr::Plan::Empty) return CQS_HIP_OK;
+    if (!out_picks) return pfail(p, CQS_HIP_ERR_INVALID, "mmr: null output buffer");
+    if (plan == cqs_mmr::Plan::Identity) {
+        for (uint32_t i = 0; i < limit; ++i) out_picks[i] = i;
+        *out_count = limit;
+        return CQS_HIP_OK;
+    }
+    float* d_stage = nullptr;
+    std::vector<uint32_t> slot;
+    std::unique_lock<std::mutex> first;
+    int32_t rc = stage_pool(p, cand_rows, m, &d_stage, slot, first);
+    if (rc != CQS_HIP_OK) return rc;
+    cqs_hip_index* c0 = p->sh->shard[0];
+    if ((rc = cqs_mmr::run(p, c0->stream, d_stage, slot.data(), cand_scores, m, limit, lambda, nullptr, out_picks)) != CQS_HIP_OK) return rc;
+    P_TRY(p, record_done(c0, c0->stream));
+    *out_count = limit;
     return CQS_HIP_OK;
 }
 

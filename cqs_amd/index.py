@@ -463,6 +463,12 @@ class HipIndex(VectorIndex):
         return [[IndexResult(self._id(int(rows[j, i])), float(scores[j, i])) for i in range(int(counts[j]))]
                 for j in range(q.shape[0])]
 
+    def _rows_by_id(self):
+        """chunk id -> local row of an `id_map` index, built on first use and rebuilt after `extend`."""
+        if not hasattr(self, "_row_of") or len(self._row_of) != len(self.id_map):
+            self._row_of = {cid: i for i, cid in enumerate(self.id_map)}
+        return self._row_of
+
     def neighbors_rows(self, target_row: int, limit: int):
         """`cqs_hip_index_neighbors`: (rows u64, scores f32) of the stored row's nearest neighbours, itself excluded."""
         rows = np.zeros((_lib.NEIGHBORS_MAX,), dtype=np.uint64)
@@ -483,13 +489,73 @@ class HipIndex(VectorIndex):
             if not (base <= row < base + len(self)):
                 raise KeyError(target_id)
         else:
-            if not hasattr(self, "_row_of") or len(self._row_of) != len(self.id_map):
-                self._row_of = {cid: i for i, cid in enumerate(self.id_map)}
-            if target_id not in self._row_of:
+            row_of = self._rows_by_id()
+            if target_id not in row_of:
                 raise KeyError(target_id)
-            row = base + self._row_of[target_id]
+            row = base + row_of[target_id]
         rows, scores = self.neighbors_rows(row, limit)
         return [IndexResult(self._id(int(r)), float(s)) for r, s in zip(rows, scores)]
+
+    # ---- cosine MMR over the resident rows (src/search/mmr.rs:59-126) ------------
+    def pairwise_rows(self, rows) -> np.ndarray:
+        """`cqs_hip_index_pairwise`: the [m, m] f32 dots of the stored rows `rows` (global row ids)."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+        m = r.shape[0]
+        out = np.zeros((m, m), dtype=np.float32)
+        rc = self._lib.cqs_hip_index_pairwise(self._h, _ptr(r), m, _ptr(out))
+        if rc != _lib.OK:
+            raise HipError(rc, self.last_error())
+        return out
+
+    def mmr_rows(self, rows, scores, limit: int, lam: float) -> np.ndarray:
+        """`cqs_hip_index_mmr`: `mmr_rerank` over the candidates (global row ids `rows`, relevance `scores`) with the
+        stored rows' dot as the similarity.  Returns the picked indices into the candidate list, in pick order."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+        s = np.ascontiguousarray(scores, dtype=np.float32).reshape(-1)
+        if s.shape[0] != r.shape[0]:
+            raise ValueError("one score per candidate row")
+        m = r.shape[0]
+        limit = max(0, min(int(limit), 2**32 - 1))
+        picks = np.zeros((max(1, min(limit, m)),), dtype=np.uint32)
+        c = C.c_uint32()
+        rc = self._lib.cqs_hip_index_mmr(self._h, _ptr(r), _ptr(s), m, limit, float(lam), _ptr(picks), C.byref(c))
+        if rc != _lib.OK:
+            raise HipError(rc, self.last_error())
+        return picks[:c.value]
+
+    def mmr_rerank(self, results: List[IndexResult], limit: int, lam: float) -> List[IndexResult]:
+        """`mmr_rerank` (src/search/mmr.rs:59-126) over a result list of this index, cosine of the stored rows as the
+        similarity: the picked results in pick order and nothing after them - the caller truncates to `limit` exactly as
+        `finalize_results` does (src/search/query.rs:685-705).  Raises `KeyError` for an id this index does not hold;
+        never raises for device trouble (logs and returns the first `limit` inputs, the reference's order without MMR)."""
+        base = int(self._lib.cqs_hip_index_row_base(self._h))
+        rows = np.zeros((len(results),), dtype=np.uint64)
+        if self.id_map is None:
+            for i, r in enumerate(results):
+                try:
+                    row = int(r.id)
+                except ValueError:
+                    raise KeyError(r.id)
+                if not (base <= row < base + len(self)):
+                    raise KeyError(r.id)
+                rows[i] = row
+        else:
+            row_of = self._rows_by_id()
+            for i, r in enumerate(results):
+                if r.id not in row_of:
+                    raise KeyError(r.id)
+                rows[i] = base + row_of[r.id]
+        limit = max(0, int(limit))
+        try:
+            picks = self.mmr_rows(rows, [r.score for r in results], limit, lam)
+        except HipError as e:
+            log.error("HIP MMR re-rank failed, keeping the relevance order: %s", e)
+            return list(results[:limit])
+        return [results[int(i)] for i in picks]
+
+    def search_mmr(self, query: np.ndarray, pool_k: int, limit: int, lam: float) -> List[IndexResult]:
+        """`search` for a pool of `pool_k`, then `mmr_rerank` of it down to `limit`."""
+        return self.mmr_rerank(self.search(query, pool_k), limit, lam)
 
     # ---- device-resident path (bench, sharded search) ---------------------------
     def search_device(self, d_queries: int, b: int, k: int, d_out_keys: int, d_out_counts: int,

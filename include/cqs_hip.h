@@ -225,6 +225,39 @@ int32_t cqs_hip_index_search_device(cqs_hip_index* idx, const float* d_queries, 
 int32_t cqs_hip_index_neighbors(cqs_hip_index* idx, uint64_t target_row, uint32_t limit, uint64_t* out_rows,
                                 float* out_scores, uint32_t* out_count);
 
+/* ---- cosine MMR re-rank of a candidate pool ------------------------------------
+ * The reference diversifies its top-K pool with `mmr_rerank` (src/search/mmr.rs:59-126) over a surface-feature
+ * similarity, because it drops the embeddings after scoring: "embedding-MMR is a follow-up" (mmr.rs:30-37,
+ * src/search/query.rs:540-542).  Behind this handle every candidate's row is still in HBM, so both calls run on the
+ * device and only the answer crosses the bus.
+ * cand_rows  [m] GLOBAL row ids as cqs_hip_index_search emits them (row_base + local), host.  A row outside the index
+ *            -> CQS_HIP_ERR_INVALID; m > CQS_HIP_MMR_MAX -> CQS_HIP_ERR_INVALID.  A row may appear more than once: its
+ *            entries are then fully similar (equal to the row's own diagonal entry, bit for bit).
+ * pairwise:  out [m * m] f32, host: out[i*m + j] = the f32 dot of stored rows cand_rows[i] and cand_rows[j] - the
+ *            cosine on a COSINE index.  out[i*m + j] and out[j*m + i] are the same bits; an entry depends on its two
+ *            rows only (not on m, the other candidates or the handle's sharding).  m == 0 writes nothing.
+ * mmr:       `mmr_rerank` with similarity(i, j) = that dot; cand_scores [m] f32 are the relevance scores, in the
+ *            caller's (relevance-descending) order.  Line by line:
+ *              lambda is clamped to [0, 1] (mmr.rs:60); limit = min(limit, m) (:62);
+ *              limit == 0 or m == 0 -> *out_count = 0, CQS_HIP_OK (:64-66);
+ *              lambda >= 1 or m <= limit -> picks 0 .. limit-1, no device work (:67-69);
+ *              per step and unselected i: max_sim = the fold of f32 `max` over the selected from 0.0 (:83-90) - negative
+ *              similarities count as 0, the first step's max_sim is 0; mmr = lambda * score - (1 - lambda) * max_sim
+ *              in f32, the two products and the difference each rounded (:92; no fused multiply-add);
+ *              the winner is the greatest mmr under the f32 total order, the lowest index among equals (:107-111).
+ *            out_picks [>= min(limit, m)] u32 receives indices INTO THE CANDIDATE LIST in pick order, *out_count their
+ *            number (= min(limit, m)).
+ *            Stated departure: a non-finite lambda or candidate score -> CQS_HIP_ERR_INVALID (the reference's env parser
+ *            refuses the former, mmr.rs:166-178; no search of this library emits the latter).  Arguments are checked
+ *            before the early answers above.
+ * Neither call poisons the handle on CQS_HIP_ERR_INVALID.  Scratch (the [m, m] Gram matrix: 4 MB at 1024) is made on
+ * the first call, sized for the largest m seen, freed at destroy; a handle that never calls these pays nothing.
+ * A row-sharded handle gathers the pool's rows on its first shard's device and runs the same kernels: same bytes. */
+#define CQS_HIP_MMR_MAX 1024u            /* pool size limit, = CQS_HIP_MAX_K */
+int32_t cqs_hip_index_pairwise(cqs_hip_index* idx, const uint64_t* cand_rows, uint32_t m, float* out);
+int32_t cqs_hip_index_mmr(cqs_hip_index* idx, const uint64_t* cand_rows, const float* cand_scores, uint32_t m,
+                          uint32_t limit, float lambda, uint32_t* out_picks, uint32_t* out_count);
+
 /* Host helpers for packed candidate keys (see above). */
 void cqs_hip_unpack_keys(const uint64_t* keys, size_t count, uint64_t* rows, float* scores);
 /* Final host-side k-way merge of per-shard candidate lists for one query

@@ -66,6 +66,10 @@ extern "C" {
                                   n_devices: u32, row_base: u64, out: *mut *mut CqsHipIndex) -> i32;
     fn cqs_hip_index_neighbors(idx: *mut CqsHipIndex, target_row: u64, limit: u32, out_rows: *mut u64,
                                out_scores: *mut f32, out_count: *mut u32) -> i32;
+    // cosine MMR over the resident rows (src/search/mmr.rs:59-126 with the stored rows' dot as `similarity`)
+    fn cqs_hip_index_pairwise(idx: *mut CqsHipIndex, cand_rows: *const u64, m: u32, out: *mut f32) -> i32;
+    fn cqs_hip_index_mmr(idx: *mut CqsHipIndex, cand_rows: *const u64, cand_scores: *const f32, m: u32, limit: u32,
+                         lambda: f32, out_picks: *mut u32, out_count: *mut u32) -> i32;
     fn cqs_hip_index_metric(idx: *const CqsHipIndex) -> u32;
     fn cqs_hip_index_extend(idx: *mut CqsHipIndex, rows: *const f32, n_new: u64) -> i32;
     // persistence (the index.cagra + .meta analogue, src/cagra.rs:973-1157, 1174-1330): the blob is written /
@@ -123,6 +127,8 @@ pub struct HipIndex {
     /// Set when the C side reports a device failure; `is_poisoned()` makes the daemon
     /// rebuild the index (src/index.rs:203-205, src/cagra.rs:472-489).
     poisoned: AtomicBool,
+    /// chunk id -> row, built by the first `mmr_rerank` (a pool names up to 1024 ids per query) and dropped by `extend`.
+    row_of: std::sync::OnceLock<std::collections::HashMap<Box<str>, u64>>,
 }
 
 // SAFETY: the handle serialises device access behind its own mutex (include/cqs_hip.h,
@@ -244,6 +250,7 @@ impl HipIndex {
             dim,
             metric,
             poisoned: AtomicBool::new(false),
+            row_of: std::sync::OnceLock::new(),
         })
     }
 
@@ -283,6 +290,7 @@ impl HipIndex {
             return Err(self.last_error());
         }
         self.id_map.extend(ids.into_iter().map(String::into_boxed_str));
+        self.row_of = std::sync::OnceLock::new();
         Ok(())
     }
 
@@ -356,6 +364,7 @@ impl HipIndex {
             dim,
             metric,
             poisoned: AtomicBool::new(false),
+            row_of: std::sync::OnceLock::new(),
         };
         // the sidecar must describe THIS blob: its checksum is the one the library just verified against the rows
         let blob_metric = unsafe { cqs_hip_index_metric(idx.handle) };
@@ -389,6 +398,38 @@ impl HipIndex {
         Some((0..count as usize)
             .filter_map(|i| self.id_map.get(rows[i] as usize).map(|id| IndexResult { id: id.to_string(), score: scores[i] }))
             .collect())
+    }
+
+    /// `mmr_rerank` (src/search/mmr.rs:59-126) over `(chunk id, relevance)` candidates of this index, in the caller's
+    /// relevance-descending order, with the cosine of the stored embeddings as the similarity - the "embedding-MMR"
+    /// mmr.rs:30-37 leaves as a follow-up.  Returns the picked indices into `candidates`, in pick order, exactly what
+    /// `mmr_rerank` hands `finalize_results` (src/search/query.rs:674-703).  `None` = a candidate is not in this index,
+    /// the pool exceeds the library's limit (1024), or the device failed: the caller keeps the surface-feature MMR.
+    pub fn mmr_rerank(&self, candidates: &[(String, f32)], limit: usize, lambda: f32) -> Option<Vec<usize>> {
+        if candidates.len() > 1024 || !lambda.is_finite() {
+            return None;
+        }
+        // (first occurrence wins, as `position()` in find_neighbors)
+        let row_of = self.row_of.get_or_init(|| {
+            let mut m = std::collections::HashMap::with_capacity(self.id_map.len());
+            for (i, id) in self.id_map.iter().enumerate() {
+                m.entry(id.clone()).or_insert(i as u64);
+            }
+            m
+        });
+        let rows: Vec<u64> = candidates.iter().map(|(id, _)| row_of.get(id.as_str()).copied()).collect::<Option<_>>()?;
+        let scores: Vec<f32> = candidates.iter().map(|(_, s)| *s).collect();
+        let mut picks = vec![0u32; candidates.len().max(1)];
+        let mut count = 0u32;
+        let rc = unsafe {
+            cqs_hip_index_mmr(self.handle, rows.as_ptr(), scores.as_ptr(), rows.len() as u32,
+                              limit.min(u32::MAX as usize) as u32, lambda, picks.as_mut_ptr(), &mut count)
+        };
+        if rc != CQS_HIP_OK {
+            tracing::warn!(error = %self.last_error(), rc, "HIP MMR re-rank failed");
+            return None;
+        }
+        Some(picks[..count as usize].iter().map(|&i| i as usize).collect())
     }
 
     fn last_error(&self) -> String {
