@@ -1,4 +1,5 @@
-// index_internal.h — the index handle and the host helpers shared by index.hip and sharded.hip.
+// index_internal.h — the index handle and the host helpers shared by the index's translation units (index.hip,
+// index_persist.hip, index_combine.hip, index_shadow.hip, mmr.hip, sharded.hip).
 // Internal to libcqs_hip.so (the public boundary is include/cqs_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -19,7 +20,7 @@ namespace cqs_idx { struct Shadow; }
 namespace cqs_mmr { struct Scratch; }
 
 // One single-query host search: its query, parameters and output buffers (the caller's own).  The combining queue of
-// cqs_hip_index_search parks these on their callers' stacks; the host search runs blocks of them (index.hip).
+// cqs_hip_index_search (index_combine.hip) parks these on their callers' stacks; the host search runs blocks of them (index.hip).
 struct cqs_combine_req {
     const float* q;          // [dim] host, validated (finite)
     uint32_t k, mode;
@@ -89,7 +90,7 @@ struct cqs_hip_index {
     std::atomic<bool> poisoned{false};
     std::string last_error;
 
-    // Combining queue (index.hip, cqs_hip_index_search): concurrent single-query callers park here and ride ONE pass
+    // Combining queue (index_combine.hip, cqs_hip_index_search): concurrent single-query callers park here and ride ONE pass
     // over the corpus (up to kMaxGemvQ queries share the HBM stream in registers).  `cmu` orders the queue only; the
     // device work itself still runs under `mu`.  The reference serialises its callers behind Mutex<GpuState>
     // (src/cagra.rs:263) one search at a time; the daemon calls `search` from one thread per client
@@ -182,7 +183,14 @@ int32_t shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k,
 // The last host shadow pass's verdicts, pinned, valid after x->stream's wait (queues their copy when not mappable).
 hipError_t shadow_verdicts(cqs_hip_index* x, uint32_t nb, const uint32_t** h_cert);
 
-// persistence over one or more device segments in row order (index.hip)
+// The host-buffer searches proper (index.hip).  Caller holds mu, has checked the arguments and zeroed the counts.
+int32_t search_host_locked(cqs_hip_index* x, const cqs_combine_req* qs, uint32_t b, uint32_t k, const uint32_t* keep_bitset,
+                           uint32_t mode, float threshold, bool gemv_only);
+int32_t search_filtered_locked(cqs_hip_index* x, const cqs_combine_req* qs, uint32_t b, uint32_t k, uint32_t mode, float threshold);
+// Park one single-query request on the combining queue and return its answer (index_combine.hip).
+int32_t combine_search(cqs_hip_index* x, cqs_combine_req& r);
+
+// persistence over one or more device segments in row order (index_persist.hip)
 struct Segment { int device; float* d_rows; uint64_t rows; hipStream_t stream; };
 int32_t save_segments(cqs_hip_index* err_owner, const std::vector<Segment>& segs, uint32_t dim, uint32_t metric,
                       const char* path, uint64_t* out_checksum);
@@ -216,7 +224,7 @@ void destroy(cqs_hip_index* parent);
 int32_t search(cqs_hip_index* parent, const float* queries, uint32_t b, uint32_t query_dim, uint32_t k,
                const uint32_t* keep_bitset, uint32_t mode, float threshold, uint64_t* out_rows, float* out_scores,
                uint32_t* out_counts);
-// One sealed block of the combining queue (index.hip): nb single-query callers with the same (k, mode, threshold), every
+// One sealed block of the combining queue (index_combine.hip): nb single-query callers with the same (k, mode, threshold), every
 // query finite and of the parent's dimension; takes the parent mutex for the block.  gemv passes only, so each caller gets
 // the bits its lone call gets.
 int32_t search_combined(cqs_hip_index* parent, cqs_combine_req* const* batch, uint32_t nb);
@@ -226,7 +234,6 @@ int32_t extend(cqs_hip_index* parent, const float* rows, uint64_t n_new);
 int32_t save(cqs_hip_index* parent, const char* path, uint64_t* out_checksum);
 uint64_t len(const cqs_hip_index* parent);
 int32_t poisoned(const cqs_hip_index* parent);
-size_t last_error(const cqs_hip_index* parent, char* buf, size_t cap);
 void set_timing(cqs_hip_index* parent, int32_t enable);
 int32_t scan_time(cqs_hip_index* parent, uint32_t* launches, double* total_ms);
 }  // namespace cqs_sharded

@@ -26,8 +26,10 @@
 #include "roctx.h"
 #include "index_internal.h"
 #include "mmr_host.h"
+#include "search_host.h"
 
 using namespace cqs_idx;
+using cqs_search::popcount_bits;
 
 namespace {
 
@@ -60,14 +62,6 @@ RcclApi* rccl_api() {
         api.GetErrorString = (decltype(api.GetErrorString))dlsym(h, "ncclGetErrorString");
     });
     return &api;
-}
-
-uint64_t popcount_bits(const uint32_t* words, uint64_t first_bit, uint64_t nbits) {   // first_bit % 32 == 0
-    const uint32_t* w = words + first_bit / 32;
-    uint64_t c = 0;
-    for (uint64_t i = 0; i < nbits / 32; ++i) c += (uint64_t)__builtin_popcount(w[i]);
-    if (nbits % 32) c += (uint64_t)__builtin_popcount(w[nbits / 32] & ((1u << (nbits % 32)) - 1u));
-    return c;
 }
 
 }  // namespace
@@ -339,14 +333,6 @@ int32_t poisoned(const cqs_hip_index* p) {
     return 0;
 }
 
-size_t last_error(const cqs_hip_index* p, char* buf, size_t cap) {
-    std::lock_guard<std::mutex> g(p->mu);
-    const size_t m = p->last_error.size() < cap - 1 ? p->last_error.size() : cap - 1;
-    memcpy(buf, p->last_error.data(), m);
-    buf[m] = 0;
-    return m;
-}
-
 void set_timing(cqs_hip_index* p, int32_t enable) {
     for (cqs_hip_index* c : p->sh->shard) cqs_hip_index_set_timing(c, enable);
 }
@@ -365,49 +351,35 @@ int32_t scan_time(cqs_hip_index* p, uint32_t* launches, double* total_ms) {
     return CQS_HIP_OK;
 }
 
+static uint32_t query_block(const cqs_hip_index* p) {   // the largest block every shard's scratch budget allows
+    uint32_t blk = 1024;
+    for (const cqs_hip_index* c : p->sh->shard) blk = std::min(blk, max_query_block(c));
+    return blk;
+}
+
 int32_t search(cqs_hip_index* p, const float* queries, uint32_t b, uint32_t query_dim, uint32_t k,
                const uint32_t* keep_bitset, uint32_t mode, float threshold, uint64_t* out_rows, float* out_scores,
                uint32_t* out_counts) {
     std::lock_guard<std::mutex> g(p->mu);
     if (poisoned(p)) return CQS_HIP_ERR_POISONED;
-    if (b == 0) return CQS_HIP_OK;
-    if (!queries || !out_counts) return pfail(p, CQS_HIP_ERR_INVALID, "search: null buffer");
-    for (uint32_t i = 0; i < b; ++i) out_counts[i] = 0;
-    const uint64_t n = len(p);
-    if (n == 0 || k == 0) return CQS_HIP_OK;                       // src/cagra.rs:445-447
-    if (query_dim != p->dim) {                                      // src/cagra.rs:449-456
-        p->last_error = "search: query dimension mismatch (empty result)";
-        return CQS_HIP_OK;
-    }
-    if (k > cqs::kMaxK) return pfail(p, CQS_HIP_ERR_INVALID, "search: k > max_k");
-    if (mode > CQS_HIP_MODE_PIPELINE) return pfail(p, CQS_HIP_ERR_INVALID, "search: bad mode");
-    if (!out_rows || !out_scores) return pfail(p, CQS_HIP_ERR_INVALID, "search: null output buffer");
+    const char* why = "";
+    const cqs_search::Plan plan = cqs_search::plan_search({queries, b, query_dim, k, mode, out_rows, out_scores, out_counts}, len(p), p->dim,
+                                                          cqs::kMaxK, &why);
+    if (plan == cqs_search::Plan::Invalid) return pfail(p, CQS_HIP_ERR_INVALID, why);
+    if (plan == cqs_search::Plan::Empty && why[0]) p->last_error = why;   // (the dimension mismatch: an answer with a message)
+    if (plan != cqs_search::Plan::Run) return CQS_HIP_OK;
     uint32_t k_eff = k;
-    const uint32_t* keep = nullptr;
-    if (keep_bitset) {                                              // src/cagra.rs:747-775, on the GLOBAL bitset
-        const uint64_t included = popcount_bits(keep_bitset, 0, n);
-        if (included == 0) return CQS_HIP_OK;
-        if (included < n) {
-            if (included < k_eff) k_eff = (uint32_t)included;
-            keep = keep_bitset;
-        }
-    }
-    uint32_t blk = 1024;
-    for (const cqs_hip_index* c : p->sh->shard) blk = std::min(blk, max_query_block(c));
+    const cqs_search::Keep kept = cqs_search::plan_keep(keep_bitset, len(p), &k_eff);   // src/cagra.rs:747-775, on the GLOBAL bitset
+    if (kept == cqs_search::Keep::Empty) return CQS_HIP_OK;
+    const uint32_t* keep = kept == cqs_search::Keep::Filtered ? keep_bitset : nullptr;
+    const uint32_t blk = query_block(p);
     std::vector<uint8_t> bad(b, 0);
     for (uint32_t done = 0; done < b;) {
         const uint32_t nb = std::min(b - done, blk);
         int32_t rc = ensure_hq(p, (size_t)nb * p->dim);
         if (rc != CQS_HIP_OK) return rc;
-        for (uint32_t i = 0; i < nb; ++i) {
-            const float* src = queries + (size_t)(done + i) * p->dim;
-            float* dst = p->sh->h_q + (size_t)i * p->dim;
-            bool ok = true;
-            for (uint32_t d = 0; d < p->dim; ++d) ok &= std::isfinite(src[d]);
-            bad[done + i] = !ok;
-            if (ok) memcpy(dst, src, (size_t)p->dim * sizeof(float));
-            else memset(dst, 0, (size_t)p->dim * sizeof(float));
-        }
+        for (uint32_t i = 0; i < nb; ++i)
+            bad[done + i] = !cqs_search::stage_query(p->sh->h_q + (size_t)i * p->dim, queries + (size_t)(done + i) * p->dim, p->dim);
         rc = search_block(p, nb, k_eff, keep, mode, threshold, bad.data() + done, out_rows + (size_t)done * k,
                           out_scores + (size_t)done * k, out_counts + done, k);
         if (rc != CQS_HIP_OK) return rc;
@@ -416,7 +388,7 @@ int32_t search(cqs_hip_index* p, const float* queries, uint32_t b, uint32_t quer
     return CQS_HIP_OK;
 }
 
-// The combining queue's block on a sharded parent (index.hip, combine_lead): the callers' queries become ONE block
+// The combining queue's block on a sharded parent (index_combine.hip, combine_lead): the callers' queries become ONE block
 // through every shard (gemv passes only: a shard's scores do not depend on how many queries share its pass), one
 // gather, one host merge per query; answers go back to each caller's own buffers.
 int32_t search_combined(cqs_hip_index* p, cqs_combine_req* const* batch, uint32_t nb) {
@@ -427,8 +399,7 @@ int32_t search_combined(cqs_hip_index* p, cqs_combine_req* const* batch, uint32_
     const uint32_t k = batch[0]->k;
     for (uint32_t i = 0; i < nb; ++i) *batch[i]->out_count = 0;
     if (len(p) == 0) return CQS_HIP_OK;                              // src/cagra.rs:445-447
-    uint32_t blk = 1024;
-    for (const cqs_hip_index* c : p->sh->shard) blk = std::min(blk, max_query_block(c));
+    const uint32_t blk = query_block(p);
     static thread_local std::vector<uint64_t> rows;
     static thread_local std::vector<float> scores;
     static thread_local std::vector<uint32_t> counts;
@@ -464,10 +435,8 @@ int32_t neighbors(cqs_hip_index* p, uint64_t target_row, uint32_t limit, uint64_
     const uint64_t n = len(p);
     if (target_row < p->row_base || target_row - p->row_base >= n)
         return pfail(p, CQS_HIP_ERR_INVALID, "neighbors: target row not in this index");
-    if (limit < 1u) limit = 1u;
-    if (limit > CQS_HIP_NEIGHBORS_MAX) limit = CQS_HIP_NEIGHBORS_MAX;
-    if (n <= 1) return CQS_HIP_OK;
-    const uint32_t k = (uint64_t)limit + 1u < n ? limit + 1u : (uint32_t)n;
+    const uint32_t k = cqs_search::neighbors_k(&limit, n);
+    if (k == 0) return CQS_HIP_OK;
     ShardSet* ss = p->sh;
     int32_t rc = ensure_hq(p, p->dim);
     if (rc != CQS_HIP_OK) return rc;
@@ -486,14 +455,7 @@ int32_t neighbors(cqs_hip_index* p, uint64_t target_row, uint32_t limit, uint64_
     const uint8_t bad = 0;
     rc = search_block(p, 1, k, nullptr, CQS_HIP_MODE_RAW, 0.f, &bad, rows.data(), scores.data(), &cnt, k);
     if (rc != CQS_HIP_OK) return rc;
-    uint32_t outc = 0;
-    for (uint32_t i = 0; i < cnt && outc < limit; ++i) {
-        if (rows[i] == target_row) continue;                       // neighbors.rs:116-118
-        out_rows[outc] = rows[i];
-        out_scores[outc] = scores[i];
-        ++outc;
-    }
-    *out_count = outc;
+    *out_count = cqs_search::drop_self(rows.data(), scores.data(), cnt, target_row, limit, out_rows, out_scores);
     return CQS_HIP_OK;
 }
 
