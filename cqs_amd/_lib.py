@@ -48,6 +48,7 @@ SIGNATURES = [
     ("cqs_hip_index_shard_info", C.c_int32,
      [_c_idx, C.c_uint32, _pp(C.c_int32), _pp(C.c_uint64), _pp(C.c_uint64), _pp(C.c_int32)]),
     ("cqs_hip_index_extend", C.c_int32, [_c_idx, C.c_void_p, C.c_uint64]),
+    ("cqs_hip_index_remove", C.c_int32, [_c_idx, C.c_void_p, C.c_uint64, _pp(C.c_uint64)]),
     ("cqs_hip_index_destroy", None, [_c_idx]),
     ("cqs_hip_index_save", C.c_int32, [_c_idx, C.c_char_p, _pp(C.c_uint64)]),
     ("cqs_hip_index_load", C.c_int32, [C.c_char_p, C.c_uint32, C.c_uint64, C.c_int32, C.c_uint64, _pp(_c_idx)]),
@@ -141,8 +142,9 @@ SIGNATURES = [
     ("cqs_hip_sparse_index_last_error", C.c_size_t, [_c_idx, C.c_char_p, C.c_size_t]),
 ]
 
-# Test hooks the library exports beside the header's symbols (embedder.hip; not part of include/cqs_hip.h).
+# Test hooks the library exports beside the header's symbols (embedder.hip, index_remove.hip; not part of include/cqs_hip.h).
 DEBUG_SIGNATURES = [
+    ("cqs_hip_debug_index_remove_budget", None, [_c_idx, C.c_uint64]),
     ("cqs_hip_debug_embedder_query_state", C.c_int32,
      [_c_idx, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _pp(C.c_int32)]),
 ]

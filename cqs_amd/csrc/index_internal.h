@@ -1,5 +1,5 @@
 // index_internal.h — the index handle and the host helpers shared by the index's translation units (index.hip,
-// index_persist.hip, index_combine.hip, index_shadow.hip, mmr.hip, sharded.hip).
+// index_persist.hip, index_combine.hip, index_shadow.hip, index_remove.hip, mmr.hip, sharded.hip).
 // Internal to libcqs_hip.so (the public boundary is include/cqs_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -109,7 +109,8 @@ struct cqs_hip_index {
     std::chrono::steady_clock::time_point last_pass_end{};   // guarded by cmu (epoch until the first pass: nobody waits)
     std::atomic<uint64_t> stat_passes{0}, stat_queries{0};   // combined passes run / queries they carried (unfiltered callers)
     std::atomic<uint64_t> stat_fpasses{0}, stat_fqueries{0}; // the same for the blocks of callers with a bitset
-    std::atomic<int32_t> inject_fail{0};  // test hook (cqs_hip_debug_index_fail_next): the next host search fails as a device error
+    std::atomic<int32_t> inject_fail{0};  // test hook (cqs_hip_debug_index_fail_next): the next host search (or remove) fails as a device error
+    uint64_t remove_budget_rows = 0;      // test hook (cqs_hip_debug_index_remove_budget): rows per pass of remove; 0 = the bounce buffer's byte budget
 
     // bf16 shadow (index_shadow.hip; null = off).  Its certified / fallback counts outlive it: they live on the handle.
     cqs_idx::Shadow* shadow = nullptr;
@@ -175,6 +176,9 @@ void read_combine_env(cqs_hip_index* x);
 int32_t shadow_auto(cqs_hip_index* x);
 int32_t shadow_extend(cqs_hip_index* x, uint64_t n_old);
 void shadow_free(cqs_hip_index* x);
+// The shadow's per-row buffers, which remove compacts beside d_rows (index_remove.hip); null: that copy is off.
+struct ShadowBuffers { uint16_t* bf16; int8_t* i8; float* i8_scale; };
+ShadowBuffers shadow_buffers(const cqs_hip_index* x);
 bool shadow_takes(const cqs_hip_index* x, uint32_t b, uint32_t k, bool gemv_only);
 bool shadow_uses_i8(const cqs_hip_index* x, uint32_t b, uint32_t k);   // of a block shadow_takes: the int8 copy serves it
 int32_t shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k, const uint32_t* d_keep, uint32_t mode,

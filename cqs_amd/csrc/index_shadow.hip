@@ -83,6 +83,11 @@ void shadow_free(cqs_hip_index* x) {
     x->shadow = nullptr;
 }
 
+ShadowBuffers shadow_buffers(const cqs_hip_index* x) {
+    const Shadow* s = x->shadow;
+    return s ? ShadowBuffers{s->d_bf16, s->d_i8, s->d_i8_scale} : ShadowBuffers{nullptr, nullptr, nullptr};
+}
+
 // Convert rows [row0, x->n) into the shadow and fold them into R.  Caller holds mu, the stream is idle.  *outlier: a finite
 // row has a component of magnitude >= 2^64 (the shadow cannot certify against it).
 static int32_t shadow_convert(cqs_hip_index* x, uint64_t row0, bool* outlier) {

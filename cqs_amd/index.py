@@ -226,6 +226,44 @@ class HipIndex(VectorIndex):
         if ids is not None:
             self.id_map.extend(ids)
 
+    def remove_rows(self, rows) -> int:
+        """`cqs_hip_index_remove`: the stored rows `rows` (global row ids, any order, duplicates count once) leave the
+        index in place; the survivors keep their order and are renumbered densely.  Returns the number removed.  Raises
+        HipError (INVALID: an id the index does not hold, a borrowed or sharded handle); `id_map` is not touched here."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+        removed = C.c_uint64()
+        rc = self._lib.cqs_hip_index_remove(self._h, _ptr(r), r.shape[0], C.byref(removed))
+        if rc != _lib.OK:
+            raise HipError(rc, self.last_error())
+        return int(removed.value)
+
+    def remove(self, ids: Iterable[str]) -> int:
+        """Delete chunks by id (the watch loop's deletions, the tiered backend's "clean orphaned vectors",
+        src/tiered.rs:13-17).  Ids the index does not hold are ignored: the watch loop also deletes chunks that were
+        never indexed (zero vectors skipped by `prepare_index_data`).  Returns the number removed; on HipError `id_map`
+        is left as it was."""
+        base = int(self._lib.cqs_hip_index_row_base(self._h))
+        local = set()
+        if self.id_map is None:
+            n = len(self)
+            for cid in ids:
+                try:
+                    row = int(cid)
+                except ValueError:
+                    continue
+                if base <= row < base + n:
+                    local.add(row - base)
+        else:
+            row_of = self._rows_by_id()
+            local = {row_of[cid] for cid in ids if cid in row_of}
+        if not local:
+            return 0
+        removed = self.remove_rows([base + i for i in sorted(local)])
+        if self.id_map is not None:
+            self.id_map[:] = [cid for i, cid in enumerate(self.id_map) if i not in local]
+            self.__dict__.pop("_row_of", None)
+        return removed
+
     # ---- persistence: blob + CagraMeta-style sidecar (src/cagra.rs:973-1157, 1174-1330) -----------
     META_MAGIC = "cqs-hip-flat-meta"
     META_VERSION = 1

@@ -16,7 +16,7 @@
  * one device scratch: `cqs_hip_index_search_device` returns with its kernels still in
  * flight, and the handle orders the NEXT search (any entry point, any stream) behind
  * them with an event, so calls on different streams serialise on the device instead of
- * racing; extend / save / destroy wait for the last enqueued search first.  Device failures never
+ * racing; extend / remove / save / destroy wait for the last enqueued search first.  Device failures never
  * abort: they return a negative status, set the handle's poisoned flag
  * (src/index.rs:203-205, src/cagra.rs:472-489) and leave a message for
  * cqs_hip_index_last_error.
@@ -118,6 +118,18 @@ int32_t cqs_hip_index_shard_info(const cqs_hip_index* idx, uint32_t shard, int32
  * tiered backend's extend() exposes (src/tiered.rs:1-43).  Not valid on a
  * borrowing index. */
 int32_t cqs_hip_index_extend(cqs_hip_index* idx, const float* rows, uint64_t n_new);
+/* Remove rows from an owning index in place — the other half of the tiered backend's purpose, "to clean orphaned
+ * vectors and absorb deltas" without a rebuild (src/tiered.rs:13-17).  `rows` are `m` global row ids (row_base
+ * included, as cqs_hip_index_neighbors takes them), in any order; a duplicate counts once.  *out_removed (may be NULL)
+ * = the distinct rows removed.  Afterwards len has dropped by that many, the surviving rows keep their relative order
+ * and are renumbered densely from row_base, and the index is indistinguishable from one created from the surviving
+ * rows: searches return the same bytes, save writes the same blob.  Nothing is reallocated.  The bf16 / int8 shadow
+ * copies are compacted with the rows and keep their bounds (still valid, at worst looser) and their counts.  Removing
+ * every row leaves an empty index that extend can refill.  m == 0 changes nothing.  CQS_HIP_ERR_INVALID, with the
+ * index untouched and the reason in last_error: an id outside [row_base, row_base + len), NULL rows with m > 0, a
+ * borrowing index (the rows are the caller's), a row-sharded handle.  Waits for the searches in flight, as extend does;
+ * a device failure half-way leaves the rows half-moved and poisons the handle. */
+int32_t cqs_hip_index_remove(cqs_hip_index* idx, const uint64_t* rows, uint64_t m, uint64_t* out_removed);
 /* Synchronises the index's streams, then frees everything (src/cagra.rs:289-302). */
 void cqs_hip_index_destroy(cqs_hip_index* idx);
 

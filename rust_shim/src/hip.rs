@@ -72,6 +72,7 @@ extern "C" {
                          lambda: f32, out_picks: *mut u32, out_count: *mut u32) -> i32;
     fn cqs_hip_index_metric(idx: *const CqsHipIndex) -> u32;
     fn cqs_hip_index_extend(idx: *mut CqsHipIndex, rows: *const f32, n_new: u64) -> i32;
+    fn cqs_hip_index_remove(idx: *mut CqsHipIndex, rows: *const u64, m: u64, out_removed: *mut u64) -> i32;
     // persistence (the index.cagra + .meta analogue, src/cagra.rs:973-1157, 1174-1330): the blob is written /
     // validated by the library, the CagraMeta-style sidecar (magic, version, dim, chunk_count, id_map,
     // checksum, metric) by `HipIndex::save` / `HipIndex::load` below via serde_json like src/cagra.rs:1128-1147
@@ -127,7 +128,7 @@ pub struct HipIndex {
     /// Set when the C side reports a device failure; `is_poisoned()` makes the daemon
     /// rebuild the index (src/index.rs:203-205, src/cagra.rs:472-489).
     poisoned: AtomicBool,
-    /// chunk id -> row, built by the first `mmr_rerank` (a pool names up to 1024 ids per query) and dropped by `extend`.
+    /// chunk id -> row, built by the first `mmr_rerank` (a pool names up to 1024 ids per query) and dropped by `extend` / `remove`.
     row_of: std::sync::OnceLock<std::collections::HashMap<Box<str>, u64>>,
 }
 
@@ -292,6 +293,37 @@ impl HipIndex {
         self.id_map.extend(ids.into_iter().map(String::into_boxed_str));
         self.row_of = std::sync::OnceLock::new();
         Ok(())
+    }
+
+    /// Delete chunks in place (the tiered backend's other purpose, "to clean orphaned vectors", src/tiered.rs:13-17):
+    /// the library compacts the resident rows, `id_map` loses the same positions in the same order.  Ids the index
+    /// does not hold are ignored (the watch loop also deletes chunks that were never indexed).  Returns the number
+    /// removed; on an error `id_map` stays as it was.
+    pub fn remove(&mut self, ids: &[&str]) -> Result<usize, String> {
+        let wanted: std::collections::HashSet<&str> = ids.iter().copied().collect();
+        let rows: Vec<u64> =
+            self.id_map.iter().enumerate().filter(|(_, id)| wanted.contains(&***id)).map(|(i, _)| i as u64).collect();
+        if rows.is_empty() {
+            return Ok(0);
+        }
+        let mut removed: u64 = 0;
+        // (handles made here have row_base 0: global row ids are `id_map` positions)
+        let rc = unsafe { cqs_hip_index_remove(self.handle, rows.as_ptr(), rows.len() as u64, &mut removed) };
+        if rc != CQS_HIP_OK {
+            return Err(self.last_error());
+        }
+        let mut gone = rows.into_iter().peekable();
+        let mut i: u64 = 0;
+        self.id_map.retain(|_| {
+            let drop = gone.peek() == Some(&i);
+            if drop {
+                gone.next();
+            }
+            i += 1;
+            !drop
+        });
+        self.row_of = std::sync::OnceLock::new();
+        Ok(removed as usize)
     }
 
     /// `CagraIndex::save` (src/cagra.rs:1086-1157): the library streams the rows HBM -> `<path>.tmp` -> fsync -> `.bak`
