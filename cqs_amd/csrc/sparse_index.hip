@@ -37,22 +37,10 @@
 #include "abi_guard.h"
 #include "persist_util.h"
 #include "scan_kernels.h"
+#include "sparse_internal.h"
 
 namespace cqs {
 
-constexpr uint32_t kSparsePad = 1024;          // n_pad granule (a multiple of every wave range)
-constexpr uint32_t kUnscored = 0xFFFFFFFFu;    // LDS marker: `scores.entry(chunk)` does not exist yet (a NaN bit pattern: weights that
-                                               // carry it are refused at build / search, a sum that lands on it is stored as 0x7FC00000)
-constexpr uint32_t kMaxTerms = 1u << 16;        // per query
-constexpr uint32_t kSparseMaxBatch = 64;       // queries per cqs_hip_sparse_index_search_batch call
-
-struct SparseTerm {            // one query term, resolved on the host
-    unsigned long long start;  // first posting of the token's list
-    unsigned long long dir;    // first entry of the list's range directory (kNoDir: none - the wave bisects the list)
-    uint32_t len;              // postings in the list
-    float w;                   // query weight
-};
-constexpr unsigned long long kNoDir = ~0ull;
 constexpr size_t kQoffBytes = ((kSparseMaxBatch + 1) * 4 + 15) / 16 * 16;   // the offsets' share of the query block (terms follow, 16-byte aligned)
 
 __device__ __forceinline__ uint32_t lower_bound_chunk(const uint2* __restrict__ p, uint32_t a, uint32_t b, uint32_t c) {
@@ -243,82 +231,9 @@ using cqs::sparse_accumulate_kernel;
 using cqs::sparse_wave_lds_words;
 using cqs::SparseTerm;
 
-// One single-query search waiting for a shared pair of launches (the combining queue of cqs_hip_sparse_index_search).
-// Lives on its caller's stack; the pointers are the caller's own buffers.
-struct cqs_sparse_req {
-    const uint32_t* q_tokens;
-    const float* q_weights;
-    uint32_t n_terms, k;
-    uint64_t* out_chunks;
-    float* out_scores;
-    uint32_t* out_count;
-    int32_t rc = 0;
-    bool done = false;
-};
-
-struct cqs_hip_sparse_index {
-    std::mutex mu;
-    // combining queue (as the dense index's, index.hip): concurrent unfiltered single-query calls share launches
-    std::mutex cmu;
-    std::condition_variable ccv;
-    std::deque<cqs_sparse_req*> pending;
-    bool leader = false;
-    bool combine = true;                     // CQS_HIP_COMBINE=0 turns it off (read at create)
-    uint32_t combine_wait_us = 100;          // CQS_HIP_COMBINE_WAIT_US
-    std::chrono::steady_clock::time_point last_pass_end{};   // guarded by cmu
-    uint32_t expect = 1;                     // like-parameter callers recent passes saw
-    std::atomic<uint64_t> stat_passes{0}, stat_queries{0};
-    std::string last_error;
-    std::atomic<bool> poisoned{false};
-    int device = 0;
-    uint64_t n = 0, n_postings = 0;
-    uint32_t n_pad = 0, rw = 64, sh = 6, n_cu = 256;
-    bool ranked = false;
-    bool group16 = false;                    // maxima per 16 chunks instead of 64 (indexes up to 262 144 chunks)
-    std::vector<uint32_t> tok;               // sorted distinct token ids
-    std::vector<uint64_t> off;               // [tok.size() + 1]
-    std::vector<uint32_t> chunk_of_rank;     // host copy (empty: identity)
-    hipStream_t stream = nullptr;
-    uint2* d_post = nullptr;
-    uint32_t* d_chunk_of_rank = nullptr;
-    float* d_scores = nullptr;
-    float* d_gmax = nullptr;
-    uint32_t* d_work = nullptr;
-    uint32_t* d_keep = nullptr;
-    SparseTerm* d_terms = nullptr;
-    uint32_t* d_qoff = nullptr;              // [kSparseMaxBatch + 1] first term of every query of a batch
-    uint32_t* h_qoff = nullptr;              // pinned
-    uint32_t b_cap = 0;                      // queries the score / maxima / key scratch holds
-    uint32_t terms_cap = 0;
-    SparseTerm* h_terms = nullptr;           // pinned
-    uint32_t* d_dir = nullptr;               // range directories, list after list: n_pad / rw + 1 entries each
-    std::vector<uint64_t> dir_off;           // [tok.size()]: a list's first entry in d_dir, kNoDir = none
-    uint64_t dir_entries = 0;
-    uint32_t* h_keep = nullptr;              // pinned, ceil(n / 32) words
-    uint64_t* d_out_keys = nullptr;
-    uint32_t* d_out_count = nullptr;
-    uint64_t* h_out_keys = nullptr;          // pinned + device-visible, kMaxK + 1 words (the last one: the count): the select writes here
-    uint64_t* h_out_keys_dev = nullptr;      // its device address (null: not mappable -> device buffer + two copies)
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    unsigned long long* d_dbg = nullptr;     // CQS_HIP_DEBUG_STAMPS=1: select_finish phase stamps of the last search (printed to stderr)
-    float last_ms = 0.f;
-    std::atomic<bool> want_timing{false};    // set by the first last_search that asks for the time: searches are timed from then on
-    uint64_t last_touched = 0;
-};
-
 namespace {
 
-int32_t sfail(cqs_hip_sparse_index* s, int32_t code, const std::string& what, hipError_t he = hipSuccess) {
-    s->last_error = what;
-    if (he != hipSuccess) s->last_error += std::string(": ") + hipGetErrorString(he);
-    if (code == CQS_HIP_ERR_DEVICE) s->poisoned = true;
-    return code;
-}
-#define S_TRY(s, expr)                                                                   \
-    do {                                                                                 \
-        const hipError_t he_ = (expr);                                                   \
-        if (he_ != hipSuccess) return sfail((s), he_ == hipErrorOutOfMemory ? CQS_HIP_ERR_NOMEM : CQS_HIP_ERR_DEVICE, #expr, he_); \
-    } while (0)
+using cqs_sparse::sfail;
 
 void release(cqs_hip_sparse_index* s) {
     if (!s) return;
@@ -381,35 +296,16 @@ int32_t finish_create(cqs_hip_sparse_index* s, const std::vector<uint2>& post, i
     if (he != hipSuccess) return dfail(he);
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) s->n_cu = (uint32_t)prop.multiProcessorCount;
-    // chunks per wave: enough waves to keep ~16 per CU in flight, 64 ... 1024 chunks each
-    s->rw = 1024;
-    while (s->rw > 64u && s->n_pad / s->rw < s->n_cu * 16u) s->rw >>= 1;
-    s->sh = 0;
-    while ((1u << s->sh) < s->rw) ++s->sh;
-    // Range directories: dir[r] = how many postings of the list sit below position r * rw, r = 0 .. n_pad / rw - what a wave
-    // needs to find its slice of the list with two adjacent loads.  Longest lists first, within a budget of entries equal
-    // to the postings' own bytes (2 P entries x 4 B = P x 8 B; never less than 64 MB.  Round 4's floor was 256 MB: a 100k-chunk
-    // index with a 30k-token vocabulary paid 192 MB of directories - and the same again as a host staging vector - for
-    // 80 MB of postings): at 1M chunks rw = 128, so a list's directory is 7 813 + 1 entries and the ~25 k longest
-    // lists of a 96 M-posting index get one; lists left without (shorter than kDirMinLen, or past the budget) are bisected.
+    // n_pad, the waves' ranges, the select's group size and which lists get a range directory: sparse_geometry.h (shared
+    // with the in-place updates)
+    const cqs::SparseGeometry geo = cqs::sparse_geometry(n, s->n_cu);
+    s->n_pad = geo.n_pad;
+    s->rw = geo.rw;
+    s->sh = geo.sh;
+    s->group16 = geo.group16;
     {
-        constexpr uint64_t kDirMinLen = 32;
         const uint64_t R1 = (uint64_t)(s->n_pad / s->rw) + 1;
-        const uint64_t budget = std::max<uint64_t>(16ull << 20, 2ull * P);
-        s->dir_off.assign(s->tok.size(), kNoDir);
-        std::vector<uint32_t> order;
-        for (size_t t = 0; t < s->tok.size(); ++t)
-            if (s->off[t + 1] - s->off[t] >= kDirMinLen) order.push_back((uint32_t)t);
-        std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
-            const uint64_t lx = s->off[x + 1] - s->off[x], ly = s->off[y + 1] - s->off[y];
-            return lx != ly ? lx > ly : x < y;
-        });
-        uint64_t used = 0;
-        for (uint32_t t : order) {
-            if (used + R1 > budget || s->off[t + 1] - s->off[t] > 0xFFFFFFFFull) break;
-            s->dir_off[t] = used;
-            used += R1;
-        }
+        const uint64_t used = cqs::sparse_plan_directories(s->off, geo, &s->dir_off);
         s->dir_entries = used;
         std::vector<uint32_t> dirs((size_t)used);
         for (size_t t = 0; t < s->tok.size(); ++t) {
@@ -435,9 +331,6 @@ int32_t finish_create(cqs_hip_sparse_index* s, const std::vector<uint2>& post, i
         if ((he = hipMalloc((void**)&s->d_chunk_of_rank, std::max<size_t>((size_t)n, 1) * 4)) != hipSuccess) return dfail(he);
         if (n && (he = hipMemcpy(s->d_chunk_of_rank, s->chunk_of_rank.data(), (size_t)n * 4, hipMemcpyHostToDevice)) != hipSuccess) return dfail(he);
     }
-    // measured (select at k = 500): 20k chunks 40 -> 24 us, 100k 29 -> 23, 1M 29 -> 45: 16-chunk groups while their maxima fit
-    // one pass of the select's workgroup (1024 threads x 16 registers)
-    s->group16 = s->n_pad / 16u <= 16384u;
     if ((he = hipMalloc((void**)&s->d_work, cqs::kWorkWords * 4)) != hipSuccess) return dfail(he);
     if ((he = hipMemset(s->d_work, 0, cqs::kWorkWords * 4)) != hipSuccess) return dfail(he);
     if ((he = hipMalloc((void**)&s->d_keep, (size_t)(s->n_pad / 32u) * 4)) != hipSuccess) return dfail(he);
@@ -464,8 +357,7 @@ cqs_hip_sparse_index* begin_create(uint64_t n, const uint32_t* id_rank, int32_t 
     CreateGuard guard{s};
     s->device = device;
     s->n = n;
-    s->n_pad = (uint32_t)((n + kSparsePad - 1) / kSparsePad * kSparsePad);
-    if (s->n_pad == 0) s->n_pad = kSparsePad;
+    s->n_pad = cqs::sparse_geometry(n, s->n_cu).n_pad;
     if (id_rank) {                                         // chunk_of_rank[r] = the chunk whose id is the r-th smallest
         s->chunk_of_rank.assign((size_t)n, 0xFFFFFFFFu);
         for (uint64_t i = 0; i < n; ++i) {
@@ -714,8 +606,7 @@ int32_t cqs_hip_sparse_index_load(const char* path, uint64_t expected_chunks, ui
     s->device = device;
     s->n = h.chunks;
     s->n_postings = h.postings;
-    s->n_pad = (uint32_t)((h.chunks + kSparsePad - 1) / kSparsePad * kSparsePad);
-    if (s->n_pad == 0) s->n_pad = kSparsePad;
+    s->n_pad = cqs::sparse_geometry(h.chunks, s->n_cu).n_pad;
     s->ranked = h.ranked != 0;
     std::vector<uint64_t> tokbuf(pad8(b_tok) / 8), rankbuf(pad8(b_rank) / 8);
     s->off.resize((size_t)h.tokens + 1);

@@ -162,6 +162,81 @@ class HipSpladeIndex:
             logging.getLogger("cqs.hip").warning("sparse index persist failed: %s", e)
         return idx, True
 
+    # ---- in-place updates (cqs_hip_sparse_index_remove / _extend) ------------
+    def _raise(self, rc: int, what: str):
+        buf = C.create_string_buffer(512)
+        self._lib.cqs_hip_sparse_index_last_error(self._h, buf, 512)
+        self.last_error = buf.value.decode("utf-8", "replace")
+        raise HipError(rc, self.last_error or what)
+
+    def remove_chunks(self, indices) -> int:
+        """`cqs_hip_sparse_index_remove`: the chunks `indices` (what `search_raw` returns; any order, a duplicate counts
+        once) leave the index in place; the survivors keep their order and are renumbered densely.  Returns the number
+        removed.  Raises HipError (INVALID: an index >= len); `id_map` is not touched here."""
+        c = np.ascontiguousarray(indices, dtype=np.uint64).reshape(-1)
+        removed = C.c_uint64()
+        rc = self._lib.cqs_hip_sparse_index_remove(self._h, _ptr(c), c.shape[0], C.byref(removed))
+        if rc != _lib.OK:
+            self._raise(rc, "cqs_hip_sparse_index_remove failed")
+        return int(removed.value)
+
+    def remove(self, ids) -> int:
+        """Delete chunks by id, beside `HipIndex.remove` on the dense leg.  Ids the index does not hold are ignored.
+        Returns the number removed; on HipError `id_map` is left as it was."""
+        n = len(self)
+        local = set()
+        if self.id_map is None:
+            for cid in ids:
+                try:
+                    c = int(cid)
+                except ValueError:
+                    continue
+                if 0 <= c < n:
+                    local.add(c)
+        else:
+            want = set(ids)
+            local = {i for i, cid in enumerate(self.id_map) if cid in want}
+        if not local:
+            return 0
+        removed = self.remove_chunks(sorted(local))
+        if self.id_map is not None:
+            self.id_map[:] = [cid for i, cid in enumerate(self.id_map) if i not in local]
+        return removed
+
+    def extend(self, chunks: Sequence[Tuple[str, SparseVector]]) -> None:
+        """Incremental add of `(chunk_id, sparse_vector)` pairs, beside `HipIndex.extend` on the dense leg: the index
+        afterwards is the one `build` makes of the old pairs followed by these."""
+        off, tok, w = forward_csr([v for _cid, v in chunks])
+        self.extend_csr(None if self.id_map is None else [cid for cid, _v in chunks], off, tok, w)
+
+    def extend_csr(self, ids: Optional[List[str]], doc_off: np.ndarray, tokens: np.ndarray, weights: np.ndarray,
+                   new_rank: Optional[np.ndarray] = None) -> None:
+        """`cqs_hip_sparse_index_extend` from flat arrays.  `ids` must match the index's id flavour (None or a list).
+        With ids and no `new_rank`, the new chunks' final ranks follow `id_ranks` over the old and the new ids: byte
+        order, equal ids in chunk order (an id equal to an existing one ranks behind it).  `id_map` grows only after the
+        library has succeeded."""
+        doc_off = np.ascontiguousarray(doc_off, dtype=np.uint64)
+        tokens = np.ascontiguousarray(tokens, dtype=np.uint32)
+        weights = np.ascontiguousarray(weights, dtype=np.float32)
+        n_new = doc_off.size - 1
+        if n_new < 0 or tokens.size != weights.size or int(doc_off[-1]) != tokens.size:
+            raise ValueError("doc_off / tokens / weights disagree")
+        if (self.id_map is None) != (ids is None):
+            raise ValueError("ids must match the index's id flavour")
+        if ids is not None and len(ids) != n_new:
+            raise ValueError("ids length != chunks")
+        if new_rank is None and ids is not None:
+            new_rank = id_ranks(list(self.id_map) + list(ids))[len(self.id_map):]
+        if new_rank is not None:
+            new_rank = np.ascontiguousarray(new_rank, dtype=np.uint32)
+            if new_rank.size != n_new:
+                raise ValueError("new_rank length != chunks")
+        rc = self._lib.cqs_hip_sparse_index_extend(self._h, _ptr(doc_off), _ptr(tokens), _ptr(weights), n_new, _ptr(new_rank))
+        if rc != _lib.OK:
+            self._raise(rc, "cqs_hip_sparse_index_extend failed")
+        if ids is not None:
+            self.id_map.extend(ids)
+
     # ---- properties -----------------------------------------------------------
     def __len__(self) -> int:
         return int(self._lib.cqs_hip_sparse_index_len(self._h))

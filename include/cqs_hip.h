@@ -592,6 +592,22 @@ int32_t cqs_hip_sparse_index_search(cqs_hip_sparse_index* idx, const uint32_t* q
 int32_t cqs_hip_sparse_index_search_batch(cqs_hip_sparse_index* idx, const uint64_t* q_off, const uint32_t* q_tokens,
                                           const float* q_weights, uint32_t b, uint32_t k, const uint32_t* keep_bitset,
                                           uint64_t* out_chunks, float* out_scores, uint32_t* out_counts);
+/* In-place updates: the sparse leg follows cqs_hip_index_remove / cqs_hip_index_extend of the dense leg
+ * without a rebuild from every document's sparse vector.  After either call the handle is indistinguishable from one
+ * freshly created from the resulting documents with the resulting id order: same len / unique_tokens / postings, the
+ * same bytes from every search, the same file from save.  Both take the handle's mutex: a concurrent search sees the old
+ * index or the new one.  INVALID (see last_error) and NOMEM leave the index untouched; a device error poisons the handle.
+ *
+ * remove: chunks leave the index in place.  `chunks` are chunk indices (what search returns), any order, a duplicate
+ * counts once; an index >= len is INVALID.  The survivors keep their relative order, in chunk index and in rank, and are
+ * renumbered densely; a token whose every posting belonged to removed chunks leaves the token table. */
+int32_t cqs_hip_sparse_index_remove(cqs_hip_sparse_index* idx, const uint64_t* chunks, uint64_t m, uint64_t* out_removed);
+/* extend: n_new documents join the index as chunks len .. len + n_new - 1.  doc_off / tokens / weights as in create.
+ * new_rank[i] = the FINAL position of new chunk i in ascending id order of the grown index (distinct, < len + n_new);
+ * the existing chunks keep their relative order in the remaining positions.  NULL: the new chunks rank after every
+ * existing one, in the order given.  On a handle created without id_rank, new_rank must be NULL. */
+int32_t cqs_hip_sparse_index_extend(cqs_hip_sparse_index* idx, const uint64_t* doc_off, const uint32_t* tokens,
+                                    const float* weights, uint64_t n_new, const uint32_t* new_rank);
 /* Concurrent callers: unfiltered single-query cqs_hip_sparse_index_search calls on one handle are combined into shared
  * batches like the dense index's (CQS_HIP_COMBINE=0 / CQS_HIP_COMBINE_WAIT_US, read at create); every caller gets the bits
  * its own call would have produced.  Counters since the handle was made: batches run through the queue and the queries they

@@ -75,6 +75,15 @@ extern "C" {
         out_scores: *mut f32,
         out_counts: *mut u32,
     ) -> i32;
+    fn cqs_hip_sparse_index_remove(idx: *mut CqsHipSparseIndex, chunks: *const u64, m: u64, out_removed: *mut u64) -> i32;
+    fn cqs_hip_sparse_index_extend(
+        idx: *mut CqsHipSparseIndex,
+        doc_off: *const u64,
+        tokens: *const u32,
+        weights: *const f32,
+        n_new: u64,
+        new_rank: *const u32,
+    ) -> i32;
     fn cqs_hip_sparse_index_last_search(idx: *const CqsHipSparseIndex, accumulate_ms: *mut f32, touched_postings: *mut u64) -> i32;
     fn cqs_hip_sparse_index_poisoned(idx: *const CqsHipSparseIndex) -> i32;
     fn cqs_hip_sparse_index_last_error(idx: *const CqsHipSparseIndex, buf: *mut c_char, cap: usize) -> usize;
@@ -165,6 +174,73 @@ impl HipSpladeIndex {
             return None;
         }
         Some(Self { raw, id_map: id_map.to_vec() })
+    }
+
+    /// Delete chunks by id in place, beside `HipIndex::remove` on the dense leg (the watch loop's deletions; "clean
+    /// orphaned vectors", src/tiered.rs:13-17).  Ids the index does not hold are ignored.  Returns the number removed; on a
+    /// refused or failed call the id map is left as it was.
+    pub fn remove(&mut self, ids: &[&str]) -> usize {
+        let want: std::collections::HashSet<&str> = ids.iter().copied().collect();
+        let chunks: Vec<u64> = self.id_map.iter().enumerate().filter(|(_, id)| want.contains(&***id)).map(|(i, _)| i as u64).collect();
+        if chunks.is_empty() {
+            return 0;
+        }
+        let mut removed = 0u64;
+        let rc = unsafe { cqs_hip_sparse_index_remove(self.raw, chunks.as_ptr(), chunks.len() as u64, &mut removed) };
+        if rc != CQS_HIP_OK {
+            tracing::warn!(rc, error = %self.last_error(), "HIP SPLADE remove failed, index unchanged");
+            return 0;
+        }
+        let mut at = 0usize;
+        let mut i = 0usize;
+        self.id_map.retain(|_| {
+            let gone = at < chunks.len() && chunks[at] == i as u64;
+            if gone {
+                at += 1;
+            }
+            i += 1;
+            !gone
+        });
+        removed as usize
+    }
+
+    /// Incremental add in place ("absorb deltas", src/tiered.rs:13-17): afterwards the index is the one `build` makes of the
+    /// old rows followed by these.  The new chunks' final ranks follow the ordering `build` uses - byte order, equal ids in
+    /// chunk order, so an id equal to an existing one ranks behind it.  `false` = refused or failed: index and id map unchanged.
+    pub fn extend(&mut self, chunks: Vec<(String, SparseVector)>) -> bool {
+        let n_old = self.id_map.len();
+        let n_new = chunks.len();
+        let mut doc_off: Vec<u64> = Vec::with_capacity(n_new + 1);
+        doc_off.push(0);
+        let mut tokens: Vec<u32> = Vec::new();
+        let mut weights: Vec<f32> = Vec::new();
+        let mut new_ids: Vec<Box<str>> = Vec::with_capacity(n_new);
+        for (chunk_id, sparse) in chunks {
+            for &(token_id, weight) in &sparse {
+                tokens.push(token_id);
+                weights.push(weight);
+            }
+            doc_off.push(tokens.len() as u64);
+            new_ids.push(chunk_id.into_boxed_str());
+        }
+        let id_at = |i: u32| -> &str { if (i as usize) < n_old { &self.id_map[i as usize] } else { &new_ids[i as usize - n_old] } };
+        let mut order: Vec<u32> = (0..(n_old + n_new) as u32).collect();
+        order.sort_by(|&a, &b| id_at(a).cmp(id_at(b)).then(a.cmp(&b)));
+        let mut new_rank = vec![0u32; n_new];
+        for (r, &i) in order.iter().enumerate() {
+            if i as usize >= n_old {
+                new_rank[i as usize - n_old] = r as u32;
+            }
+        }
+        let rc = unsafe {
+            cqs_hip_sparse_index_extend(self.raw, doc_off.as_ptr(), tokens.as_ptr(), weights.as_ptr(), n_new as u64, new_rank.as_ptr())
+        };
+        if rc != CQS_HIP_OK {
+            tracing::warn!(rc, error = %self.last_error(), "HIP SPLADE extend failed, index unchanged");
+            return false;
+        }
+        self.id_map.extend(new_ids);
+        true
     }
 
     /// `SpladeIndex::save` (index.rs:346): the device-ready arrays under `path` (own format), tied to `generation`.
