@@ -69,6 +69,12 @@ SIGNATURES = [
     ("cqs_hip_index_search_filtered", C.c_int32,
      [_c_idx, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint64, C.c_uint32, C.c_float,
       C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("cqs_hip_index_set_tags", C.c_int32, [_c_idx, C.c_uint64, C.c_void_p, C.c_uint64]),
+    ("cqs_hip_index_tagged_rows", C.c_uint64, [_c_idx]),
+    ("cqs_hip_index_count_tagged", C.c_int32, [_c_idx, C.c_void_p, _pp(C.c_uint64)]),
+    ("cqs_hip_index_search_tagged", C.c_int32,
+     [_c_idx, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float,
+      C.c_void_p, C.c_void_p, C.c_void_p]),
     ("cqs_hip_index_combine_stats", None, [_c_idx, _pp(C.c_uint64), _pp(C.c_uint64)]),
     ("cqs_hip_index_combine_filter_stats", None, [_c_idx, _pp(C.c_uint64), _pp(C.c_uint64)]),
     ("cqs_hip_index_set_bf16_scan", C.c_int32, [_c_idx, C.c_int32]),
@@ -138,14 +144,20 @@ SIGNATURES = [
      [_c_idx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("cqs_hip_sparse_index_remove", C.c_int32, [_c_idx, C.c_void_p, C.c_uint64, _pp(C.c_uint64)]),
     ("cqs_hip_sparse_index_extend", C.c_int32, [_c_idx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    ("cqs_hip_sparse_index_set_tags", C.c_int32, [_c_idx, C.c_uint64, C.c_void_p, C.c_uint64]),
+    ("cqs_hip_sparse_index_tagged_chunks", C.c_uint64, [_c_idx]),
+    ("cqs_hip_sparse_index_search_tagged", C.c_int32,
+     [_c_idx, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, _pp(C.c_uint32)]),
     ("cqs_hip_sparse_index_combine_stats", None, [_c_idx, _pp(C.c_uint64), _pp(C.c_uint64)]),
     ("cqs_hip_sparse_index_last_search", C.c_int32, [_c_idx, _pp(C.c_float), _pp(C.c_uint64)]),
     ("cqs_hip_sparse_index_poisoned", C.c_int32, [_c_idx]),
     ("cqs_hip_sparse_index_last_error", C.c_size_t, [_c_idx, C.c_char_p, C.c_size_t]),
 ]
 
-# Test hooks the library exports beside the header's symbols (embedder.hip, index_remove.hip; not part of include/cqs_hip.h).
+# Test hooks the library exports beside the header's symbols (embedder.hip, index_remove.hip, index_tags.hip; not part of
+# include/cqs_hip.h).
 DEBUG_SIGNATURES = [
+    ("cqs_hip_debug_index_tag_keep", C.c_int32, [_c_idx, C.c_void_p, C.c_void_p]),
     ("cqs_hip_debug_index_remove_budget", None, [_c_idx, C.c_uint64]),
     ("cqs_hip_debug_embedder_query_state", C.c_int32,
      [_c_idx, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _pp(C.c_int32)]),

@@ -180,15 +180,20 @@ hipError_t quiesce(cqs_hip_index* x) {
 }
 
 // Copy a host keep-bitset (`words` u32) into the handle's device copy on its stream.  Caller holds mu.
+int32_t ensure_keep(cqs_hip_index* x, uint64_t words) {
+    if (words <= x->keep_words_cap) return CQS_HIP_OK;
+    HIP_TRY(x, quiesce(x));
+    hipFree(x->d_keep);
+    x->d_keep = nullptr;
+    x->keep_words_cap = 0;
+    HIP_TRY(x, hipMalloc(&x->d_keep, words * sizeof(uint32_t)));
+    x->keep_words_cap = words;
+    return CQS_HIP_OK;
+}
+
 int32_t stage_keep(cqs_hip_index* x, const uint32_t* host_words, uint64_t words) {
-    if (words > x->keep_words_cap) {
-        HIP_TRY(x, quiesce(x));
-        hipFree(x->d_keep);
-        x->d_keep = nullptr;
-        x->keep_words_cap = 0;
-        HIP_TRY(x, hipMalloc(&x->d_keep, words * sizeof(uint32_t)));
-        x->keep_words_cap = words;
-    }
+    const int32_t rc = ensure_keep(x, words);
+    if (rc != CQS_HIP_OK) return rc;
     HIP_TRY(x, hipMemcpyAsync(x->d_keep, host_words, words * sizeof(uint32_t), hipMemcpyHostToDevice, x->stream));
     return CQS_HIP_OK;
 }
@@ -366,6 +371,7 @@ int32_t cqs_hip_index_extend(cqs_hip_index* x, const float* rows, uint64_t n_new
         x->d_rows = nd;
         x->cap_rows = cap;
         if (x->d_keep_tab) (void)ensure_keep_tab(x);   // (a failure leaves no table: filtered calls run one by one)
+        if (x->d_tags) tags_regrow(x);                 // (a failure leaves no tags: search_tagged refuses until set_tags)
     }
     HIP_TRY(x, hipMemcpyAsync(x->d_rows + x->n * x->dim, rows, n_new * row_bytes, hipMemcpyHostToDevice, x->stream));
     HIP_TRY(x, hipStreamSynchronize(x->stream));
@@ -386,6 +392,7 @@ void cqs_hip_index_destroy(cqs_hip_index* x) CQS_ABI_TRY {
     free_scratch(x);
     cqs_mmr::free_scratch(x);
     shadow_free(x);
+    tags_free(x);
     hipFree(x->d_keep);
     free_keep_tab(x);
     hipFree(x->d_dbg);
@@ -551,7 +558,7 @@ static int32_t answer_block(cqs_hip_index* x, std::vector<const cqs_combine_req*
 }
 
 // The test hook (cqs_hip_debug_index_fail_next), consumed: an armed hook fails this one host search as a device error would.
-static int32_t injected_failure(cqs_hip_index* x) {
+int32_t injected_failure(cqs_hip_index* x) {
     if (x->inject_fail.exchange(0, std::memory_order_acq_rel) == 0) return CQS_HIP_OK;
     return fail(x, CQS_HIP_ERR_DEVICE, "search: injected device failure (test hook)");
 }
@@ -575,6 +582,14 @@ int32_t search_host_locked(cqs_hip_index* x, const cqs_combine_req* qs, uint32_t
         if ((rc = stage_keep(x, keep_bitset, (x->n + 31) / 32)) != CQS_HIP_OK) return rc;
         d_keep = x->d_keep;
     }
+    return search_blocks_locked(x, qs, b, k_eff, d_keep, mode, threshold, gemv_only);
+}
+
+// The block loop behind it, over a bitset that is already on the device (search_tagged builds its own there): the scratch
+// budget's blocks, staged and answered one after the other.
+int32_t search_blocks_locked(cqs_hip_index* x, const cqs_combine_req* qs, uint32_t b, uint32_t k_eff, const uint32_t* d_keep,
+                             uint32_t mode, float threshold, bool gemv_only) {
+    int32_t rc;
     const uint32_t blk = max_query_block(x);
     std::vector<const cqs_combine_req*> staged;
     for (uint32_t done = 0; done < b;) {
@@ -634,7 +649,7 @@ int32_t search_filtered_locked(cqs_hip_index* x, const cqs_combine_req* qs, uint
 }
 
 // plan_search under the handle's mutex: true = there is device work, else *rc is the call's answer.
-static bool search_planned(cqs_hip_index* x, const cqs_search::Args& a, int32_t* rc) {
+bool search_planned(cqs_hip_index* x, const cqs_search::Args& a, int32_t* rc) {
     const char* why = "";
     const cqs_search::Plan plan = cqs_search::plan_search(a, x->n, x->dim, kMaxK, &why);
     *rc = plan == cqs_search::Plan::Invalid ? fail(x, CQS_HIP_ERR_INVALID, why) : CQS_HIP_OK;
@@ -643,7 +658,7 @@ static bool search_planned(cqs_hip_index* x, const cqs_search::Args& a, int32_t*
 }
 
 // One request per query of a planned call: its own output rows and, filtered, its own bitset.
-static std::vector<cqs_combine_req> requests(const cqs_search::Args& a, float thr) {
+std::vector<cqs_combine_req> requests(const cqs_search::Args& a, float thr) {
     std::vector<cqs_combine_req> rq(a.b);
     for (uint32_t i = 0; i < a.b; ++i) {
         rq[i] = cqs_combine_req{a.queries + (size_t)i * a.query_dim, a.k, a.mode, thr, a.out_rows + (size_t)i * a.k,

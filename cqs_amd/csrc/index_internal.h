@@ -18,6 +18,7 @@
 namespace cqs_sharded { struct ShardSet; }
 namespace cqs_idx { struct Shadow; }
 namespace cqs_mmr { struct Scratch; }
+namespace cqs_search { struct Args; }
 
 // One single-query host search: its query, parameters and output buffers (the caller's own).  The combining queue of
 // cqs_hip_index_search (index_combine.hip) parks these on their callers' stacks; the host search runs blocks of them (index.hip).
@@ -119,6 +120,15 @@ struct cqs_hip_index {
 
     // Scratch of cqs_hip_index_pairwise / cqs_hip_index_mmr (mmr.hip; null until the first such call on this handle).
     cqs_mmr::Scratch* mmr = nullptr;
+
+    // Row tags (index_tags.hip; null until the first set_tags): one u32 per row beside the corpus, the
+    // library's own also on a borrowing handle.  Local rows [0, tagged) have a tag.  tags_cap >= cap_rows whenever d_tags
+    // is set (extend regrows it with the corpus, remove compacts it with the rows).
+    uint32_t* d_tags = nullptr;
+    uint64_t tags_cap = 0;
+    uint64_t tagged = 0;
+    uint32_t* d_tag_count = nullptr;      // the kept rows of the last tags_keep_kernel launch, one partial count per workgroup
+    uint32_t* h_tag_count = nullptr;      // (kTagMaxBlocks words), and the pinned block they are read back into
 };
 
 namespace cqs_idx {
@@ -166,6 +176,8 @@ hipError_t quiesce(cqs_hip_index* x);
 int32_t create_owned(const float* rows, uint64_t n, uint32_t dim, uint32_t metric, int32_t device, uint64_t row_base,
                      cqs_hip_index** out);
 int32_t stage_keep(cqs_hip_index* x, const uint32_t* host_words, uint64_t words);
+// d_keep holds at least `words` u32 (regrown after a quiesce).  Caller holds mu.
+int32_t ensure_keep(cqs_hip_index* x, uint64_t words);
 // The handle's bitset table sized for cap_rows (made or regrown here; false = none: not enough memory).  Caller holds mu.
 bool ensure_keep_tab(cqs_hip_index* x);
 void free_keep_tab(cqs_hip_index* x);
@@ -186,6 +198,22 @@ int32_t shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k,
                     const KeepTab* tab = nullptr);
 // The last host shadow pass's verdicts, pinned, valid after x->stream's wait (queues their copy when not mappable).
 hipError_t shadow_verdicts(cqs_hip_index* x, uint32_t nb, const uint32_t** h_cert);
+
+// plan_search (search_host.h) under the handle's mutex: true = there is device work, else *rc is the call's answer.
+bool search_planned(cqs_hip_index* x, const cqs_search::Args& a, int32_t* rc);
+// One request per query of a planned call: its own output rows and, filtered, its own bitset.
+std::vector<cqs_combine_req> requests(const cqs_search::Args& a, float thr);
+// The test hook (cqs_hip_debug_index_fail_next), consumed: an armed hook fails this one host search as a device error would.
+int32_t injected_failure(cqs_hip_index* x);
+// The block loop of the host search: `b` queries at k_eff over the rows d_keep keeps (device bitset of the whole index,
+// ceil(n/32) words; null: every row).  Caller holds mu, has set the device and ordered x->stream after the last search.
+int32_t search_blocks_locked(cqs_hip_index* x, const cqs_combine_req* qs, uint32_t b, uint32_t k_eff, const uint32_t* d_keep,
+                             uint32_t mode, float threshold, bool gemv_only);
+// Row tags (index_tags.hip).  Caller holds mu (or owns the handle).
+void tags_free(cqs_hip_index* x);
+// After extend regrew the corpus: the column regrown to cap_rows with its contents.  No memory for it: the tags are dropped
+// (tagged = 0, reason in last_error) and the index stays usable.  The stream is idle.
+void tags_regrow(cqs_hip_index* x);
 
 // The host-buffer searches proper (index.hip).  Caller holds mu, has checked the arguments and zeroed the counts.
 int32_t search_host_locked(cqs_hip_index* x, const cqs_combine_req* qs, uint32_t b, uint32_t k, const uint32_t* keep_bitset,

@@ -10,6 +10,7 @@
 #include "abi_guard.h"
 #include "index_internal.h"
 #include "remove_host.h"
+#include "tags_host.h"
 
 namespace cqs_idx {
 
@@ -116,8 +117,10 @@ int32_t remove_locked(cqs_hip_index* x, const std::vector<uint64_t>& removed, co
         const auto pb = sb.bf16 ? passes_for(x, runs, (uint64_t)dim * sizeof(uint16_t)) : std::vector<cqs_remove::Pass>();
         const auto p8 = sb.i8 ? passes_for(x, runs, dim) : std::vector<cqs_remove::Pass>();
         const auto ps = sb.i8 ? passes_for(x, runs, sizeof(float)) : std::vector<cqs_remove::Pass>();
-        const uint64_t bounce_bytes = std::max(std::max(largest_pass(pf) * dim * sizeof(float), largest_pass(pb) * dim * sizeof(uint16_t)),
-                                               std::max(largest_pass(p8) * dim, largest_pass(ps) * sizeof(float)));
+        const auto pt = x->d_tags ? passes_for(x, runs, sizeof(uint32_t)) : std::vector<cqs_remove::Pass>();
+        const uint64_t bounce_bytes = std::max(std::max(std::max(largest_pass(pf) * dim * sizeof(float), largest_pass(pb) * dim * sizeof(uint16_t)),
+                                                        std::max(largest_pass(p8) * dim, largest_pass(ps) * sizeof(float))),
+                                               largest_pass(pt) * sizeof(uint32_t));
         std::vector<uint2> h_runs(runs.size() + 1);   // (row ids fit 32 bits: create / extend keep n + row_base below 2^32)
         for (size_t i = 0; i < runs.size(); ++i) h_runs[i] = make_uint2((uint32_t)runs[i].src, (uint32_t)runs[i].dst);
         h_runs[runs.size()] = make_uint2((uint32_t)x->n, (uint32_t)n_new);
@@ -133,9 +136,13 @@ int32_t remove_locked(cqs_hip_index* x, const std::vector<uint64_t>& removed, co
         if (rc == CQS_HIP_OK && sb.bf16) rc = compact<unit16>(x, (unit16*)sb.bf16, dim / 8u, pb, dr, bounce.p);
         if (rc == CQS_HIP_OK && sb.i8) rc = compact<unit16>(x, (unit16*)sb.i8, dim / 16u, p8, dr, bounce.p);
         if (rc == CQS_HIP_OK && sb.i8) rc = compact<float>(x, sb.i8_scale, 1u, ps, dr, bounce.p);
+        // The tag column moves with the same runs, whole (rows past the tagged prefix hold nothing anybody reads; the column
+        // is as long as the corpus's allocation).
+        if (rc == CQS_HIP_OK && x->d_tags) rc = compact<uint32_t>(x, x->d_tags, 1u, pt, dr, bounce.p);
         if (rc != CQS_HIP_OK) { (void)hipStreamSynchronize(x->stream); return rc; }   // (h_runs and the buffers outlive the queue)
         HIP_TRY(x, hipStreamSynchronize(x->stream));
     }
+    x->tagged = cqs_tags::tagged_after_remove(removed.data(), removed.size(), x->tagged);
     x->n = n_new;   // cap_rows stays: nothing is reallocated, the keep-bitset table's stride stays valid
     return CQS_HIP_OK;
 }

@@ -447,9 +447,9 @@ int32_t cqs_hip_sparse_index_remove(cqs_hip_sparse_index* s, const uint64_t* chu
     const su::Plan p = su::plan_remove(chunks, m, s->n, s->chunk_of_rank, &plan, &why);
     if (p == su::Plan::Invalid) return sfail(s, CQS_HIP_ERR_INVALID, std::string("sparse remove: ") + why);
     if (p == su::Plan::Nothing) return CQS_HIP_OK;
-    const uint64_t removed = plan.removed.size();
-    const int32_t rc = remove_locked(s, plan);
-    if (rc == CQS_HIP_OK && out_removed) *out_removed = removed;
+    const int32_t rc = remove_locked(s, plan);   // (takes plan.chunk_of_rank; plan.removed stays)
+    if (rc == CQS_HIP_OK) cqs_sparse::tags_after_remove(s, plan.removed);
+    if (rc == CQS_HIP_OK && out_removed) *out_removed = plan.removed.size();
     return rc;
 } CQS_ABI_CATCH(s)
 
@@ -463,7 +463,9 @@ int32_t cqs_hip_sparse_index_extend(cqs_hip_sparse_index* s, const uint64_t* doc
     const su::Plan p = su::plan_extend(doc_off, tokens, weights, n_new, new_rank, s->n, s->ranked, s->chunk_of_rank, s->tok, s->off, &plan, &why);
     if (p == su::Plan::Invalid) return sfail(s, CQS_HIP_ERR_INVALID, std::string("sparse extend: ") + why);
     if (p == su::Plan::Nothing) return CQS_HIP_OK;
-    return extend_locked(s, plan);
+    const int32_t rc = extend_locked(s, plan);
+    if (rc == CQS_HIP_OK) cqs_sparse::tags_after_extend(s);
+    return rc;
 } CQS_ABI_CATCH(s)
 
 }  // extern "C"

@@ -92,6 +92,12 @@ struct cqs_hip_sparse_index {
     float last_ms = 0.f;
     std::atomic<bool> want_timing{false};    // set by the first last_search that asks for the time: searches are timed from then on
     uint64_t last_touched = 0;
+    // Chunk tags: one u32 per chunk INDEX (what keep_bitset is indexed by), chunks [0, h_tags.size()) have
+    // one.  The host copy is the master - remove renumbers it with the chunks, extend keeps it - and d_tags its device copy
+    // (null until the first set_tags; tags_cap entries, regrown from the host copy when the index outgrows it).
+    std::vector<uint32_t> h_tags;
+    uint32_t* d_tags = nullptr;
+    uint64_t tags_cap = 0;
 };
 
 namespace cqs_sparse {
@@ -102,6 +108,11 @@ inline int32_t sfail(cqs_hip_sparse_index* s, int32_t code, const std::string& w
     if (code == CQS_HIP_ERR_DEVICE) s->poisoned = true;
     return code;
 }
+
+// The tags follow an update that succeeded (sparse_index.hip).  Caller holds mu; the stream is idle.  Memory that fails
+// here drops the tags (reason in last_error), never the update.
+void tags_after_remove(cqs_hip_sparse_index* s, const std::vector<uint32_t>& removed);   // distinct chunk indices, ascending
+void tags_after_extend(cqs_hip_sparse_index* s);
 
 }  // namespace cqs_sparse
 

@@ -131,6 +131,31 @@ def _ptr(a: Optional[np.ndarray]):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def tag_filter(f0: Optional[Iterable[int]] = None, f1: Optional[Iterable[int]] = None,
+               f2: Optional[Iterable[int]] = None, f3: Optional[Iterable[int]] = None) -> np.ndarray:
+    """The `allow` argument of the tagged searches (include/cqs_hip.h, "row tags"): 32 u32 words = four 256-bit sets,
+    one per 8-bit field of a row's tag.  Each argument lists the allowed codes (0 .. 255) of its field; `None` leaves the
+    field unconstrained (all 256 bits set).  Bit v of field f's set is bit v % 32 of word 8 f + v // 32."""
+    allow = np.zeros(32, dtype=np.uint32)
+    for f, codes in enumerate((f0, f1, f2, f3)):
+        if codes is None:
+            allow[8 * f:8 * f + 8] = 0xFFFFFFFF
+            continue
+        for v in codes:
+            v = int(v)
+            if not 0 <= v <= 255:
+                raise ValueError(f"tag code {v} of field {f} is not in 0 .. 255")
+            allow[8 * f + v // 32] |= np.uint32(1 << (v % 32))
+    return allow
+
+
+def _allow_words(allow) -> np.ndarray:
+    a = np.ascontiguousarray(allow, dtype=np.uint32).reshape(-1)
+    if a.shape[0] != 32:
+        raise ValueError("allow must be 32 uint32 words (tag_filter)")
+    return a
+
+
 class HipIndex(VectorIndex):
     """Exact GPU index: `[n, dim]` f32 rows resident in HBM, brute-force scan + top-k.
 
@@ -422,6 +447,66 @@ class HipIndex(VectorIndex):
         if rc != _lib.OK:
             raise HipError(rc, self.last_error())
         return rows[:, :k], scores[:, :k], counts
+
+    # ---- row tags (include/cqs_hip.h "row tags") ----------------
+    def set_tags(self, tags, first: int = 0) -> None:
+        """`cqs_hip_index_set_tags`: one u32 tag per row for the rows `first` .. `first + len(tags) - 1` (global row ids).
+        The tagged rows stay a prefix: overwrite inside it and / or extend it.  Raises HipError (INVALID: a gap, a range
+        past the end, a sharded handle)."""
+        t = np.ascontiguousarray(tags, dtype=np.uint32).reshape(-1)
+        rc = self._lib.cqs_hip_index_set_tags(self._h, int(first), _ptr(t), t.shape[0])
+        if rc != _lib.OK:
+            raise HipError(rc, self.last_error())
+
+    def tagged_rows(self) -> int:
+        """The leading rows that have a tag (`cqs_hip_index_tagged_rows`)."""
+        return int(self._lib.cqs_hip_index_tagged_rows(self._h))
+
+    def count_tagged(self, allow) -> int:
+        """The rows the filter `allow` (`tag_filter`) keeps (`cqs_hip_index_count_tagged`): what cqs logs as `included`."""
+        kept = C.c_uint64()
+        rc = self._lib.cqs_hip_index_count_tagged(self._h, _ptr(_allow_words(allow)), C.byref(kept))
+        if rc != _lib.OK:
+            raise HipError(rc, self.last_error())
+        return int(kept.value)
+
+    def search_tagged_batch(self, queries: np.ndarray, k: int, allow, mode: int = _lib.MODE_RAW, threshold: float = 0.0):
+        """Block of queries through `cqs_hip_index_search_tagged`: the answer of `search_batch(queries, k, keep_bitset=the
+        host bitset of the same predicate)`, byte for byte, without the bitset.  `allow`: `tag_filter(...)`.
+        Returns (rows u64 [b,k], scores f32 [b,k], counts u32 [b])."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        b, qd = q.shape
+        a = _allow_words(allow)
+        rows = np.zeros((b, max(k, 1)), dtype=np.uint64)
+        scores = np.zeros((b, max(k, 1)), dtype=np.float32)
+        counts = np.zeros((b,), dtype=np.uint32)
+        rc = self._lib.cqs_hip_index_search_tagged(self._h, _ptr(q), b, qd, k, _ptr(a), mode, threshold,
+                                                   _ptr(rows), _ptr(scores), _ptr(counts))
+        if rc != _lib.OK:
+            raise HipError(rc, self.last_error())
+        return rows[:, :k], scores[:, :k], counts
+
+    def search_tagged(self, query: np.ndarray, k: int, allow) -> List[IndexResult]:
+        """`search_with_filter` for a predicate over the rows' tags: no loop over the ids, no bitset.  Like `search`, never
+        raises for device trouble (logs + []); that includes tags that do not cover the index."""
+        if self.is_empty() or k == 0:
+            return []
+        query = np.asarray(query, dtype=np.float32).reshape(-1)
+        if query.shape[0] != self.dim():
+            log.warning("Query dimension mismatch expected_dim=%d actual_dim=%d", self.dim(), query.shape[0])
+            return []
+        if not np.all(np.isfinite(query)):
+            return []
+        k = min(k, self.max_k())
+        try:
+            rows, scores, counts = self.search_tagged_batch(query, k, allow)
+        except HipError as e:
+            log.error("HIP tagged search failed: %s", e)
+            return []
+        c = int(counts[0])
+        return [IndexResult(self._id(int(rows[0, i])), float(scores[0, i])) for i in range(c)]
 
     def search(self, query: np.ndarray, k: int) -> List[IndexResult]:
         """`VectorIndex::search` (src/index.rs:146): sorted by score desc; never raises for device trouble."""

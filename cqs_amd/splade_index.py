@@ -14,7 +14,7 @@ from typing import Callable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from . import _lib
-from .index import HipError, IndexResult
+from .index import HipError, IndexResult, _allow_words
 
 SparseVector = Sequence[Tuple[int, float]]      # `pub type SparseVector = Vec<(u32, f32)>` (src/splade/mod.rs)
 
@@ -289,6 +289,43 @@ class HipSpladeIndex:
             self.last_error = buf.value.decode("utf-8", "replace")
             return out[:0], sc[:0], rc
         return out[:cnt.value], sc[:cnt.value], rc
+
+    # ---- chunk tags (include/cqs_hip.h "Chunk tags") -----------
+    def set_tags(self, tags, first: int = 0) -> None:
+        """`cqs_hip_sparse_index_set_tags`: one u32 tag per chunk index for the chunks `first` .. `first + len(tags) - 1`.
+        The tagged chunks stay a prefix.  Raises HipError (INVALID: a gap, a range past the end)."""
+        t = np.ascontiguousarray(tags, dtype=np.uint32).reshape(-1)
+        rc = self._lib.cqs_hip_sparse_index_set_tags(self._h, int(first), _ptr(t), t.shape[0])
+        if rc != _lib.OK:
+            self._raise(rc, "cqs_hip_sparse_index_set_tags failed")
+
+    def tagged_chunks(self) -> int:
+        return int(self._lib.cqs_hip_sparse_index_tagged_chunks(self._h))
+
+    def search_tagged_raw(self, q_tokens, q_weights, k: int, allow):
+        """`cqs_hip_sparse_index_search_tagged`: `search_raw` with keep = the tag predicate `allow` (`tag_filter`), no
+        bitset built or sent.  -> (chunk indices u64, scores f32, status)."""
+        qt = np.ascontiguousarray(q_tokens, dtype=np.uint32)
+        qw = np.ascontiguousarray(q_weights, dtype=np.float32)
+        if qt.size != qw.size:
+            raise ValueError("query tokens / weights disagree")
+        a = None if allow is None else _allow_words(allow)
+        out = np.zeros(max(k, 1), dtype=np.uint64)
+        sc = np.zeros(max(k, 1), dtype=np.float32)
+        cnt = C.c_uint32()
+        rc = self._lib.cqs_hip_sparse_index_search_tagged(self._h, _ptr(qt), _ptr(qw), qt.size, k, _ptr(a), _ptr(out), _ptr(sc),
+                                                         C.byref(cnt))
+        if rc != _lib.OK:
+            buf = C.create_string_buffer(512)
+            self._lib.cqs_hip_sparse_index_last_error(self._h, buf, 512)
+            self.last_error = buf.value.decode("utf-8", "replace")
+            return out[:0], sc[:0], rc
+        return out[:cnt.value], sc[:cnt.value], rc
+
+    def search_tagged(self, query: SparseVector, k: int, allow) -> List[IndexResult]:
+        """`search_with_filter` for a predicate over the chunks' tags."""
+        ch, sc, _rc = self.search_tagged_raw([t for t, _w in query], [w for _t, w in query], k, allow)
+        return [IndexResult(self._id(int(c)), float(s)) for c, s in zip(ch, sc)]
 
     def search_batch_raw(self, queries, k: int, keep: Optional[np.ndarray] = None):
         """`cqs_hip_sparse_index_search_batch`: queries = [(tokens, weights), ...] (at most 64).

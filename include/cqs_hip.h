@@ -298,6 +298,48 @@ int32_t cqs_hip_index_search_filtered(cqs_hip_index* idx, const float* queries, 
                                       uint32_t mode, float threshold,
                                       uint64_t* out_rows, float* out_scores, uint32_t* out_counts);
 
+/* ---- row tags: filtered search without a host bitset -------------
+ * The predicate the reference sends with every filtered and hybrid query - chunk type in an include set, not in an
+ * exclude set, language in a set; a chunk without metadata never passes (src/search/query.rs:860-900) - is a function of
+ * two small integers per chunk.  Kept beside the rows in device memory, they let the caller send the allowed sets
+ * (128 bytes) instead of evaluating a predicate n times and uploading n / 8 bytes: a kernel writes the keep-bitset the
+ * scans already read, and the host cost of a filtered search stops depending on n.
+ *
+ * Tag: one uint32_t per row, read as four 8-bit fields, field f = (tag >> 8 f) & 255.  The library gives the fields no
+ * meaning (the cqs shim: field 0 = chunk-type code, field 1 = language code, 255 = "no metadata", fields 2 and 3 spare).
+ * Filter: `allow`, 32 host uint32_t words = four 256-bit sets; bit v of field f's set is bit v % 32 of word 8 f + v / 32.
+ * A row is kept iff, for every field, the bit named by the row's field value is set.  A field the caller does not
+ * constrain has all 256 bits set; a filter of 32 all-ones words keeps every row.
+ *
+ * set_tags: tags [m] (host) for the rows first_row .. first_row + m - 1 (GLOBAL row ids).  The tagged rows are always a
+ * prefix [row_base, row_base + tagged_rows): a call may overwrite inside the prefix and / or extend it.  m == 0 changes
+ * nothing.  CQS_HIP_ERR_INVALID, the handle untouched and the reason in last_error: a gap (first_row > row_base +
+ * tagged_rows), a range past len, NULL tags with m > 0, a row-sharded handle (not built).  Takes the handle's mutex and
+ * waits for the searches in flight, as extend does.  The column (4 B per row) is the library's own also on a borrowing
+ * handle; it is made by the first call, sized like the corpus's allocation, and regrown with its contents when extend
+ * regrows the corpus (no memory for that: the tags are dropped, tagged_rows is 0 and last_error says so).
+ * extend leaves tagged_rows where it was: the new rows have no tag until set_tags covers them.  remove compacts the column
+ * with the rows; tagged_rows drops by the number of removed rows that lay below it.  save / load do not persist tags: the
+ * blob format is unchanged and a loaded handle has tagged_rows == 0.
+ * tagged_rows: the leading rows that have a tag (0 on a row-sharded handle). */
+int32_t  cqs_hip_index_set_tags(cqs_hip_index* idx, uint64_t first_row, const uint32_t* tags, uint64_t m);
+uint64_t cqs_hip_index_tagged_rows(const cqs_hip_index* idx);
+/* search_tagged: first the tag-specific checks, each CQS_HIP_ERR_INVALID without poisoning and with the reason in
+ * last_error: NULL allow; a row-sharded handle (not built); tagged_rows < len ("tags cover X of N rows").  After them the
+ * call returns, byte for byte, what cqs_hip_index_search returns for the same arguments with keep_bitset = the host
+ * bitset of the same predicate, every rule of that call included: a dimension mismatch gives counts 0 and CQS_HIP_OK, a
+ * non-finite query count 0, k > max_k is CQS_HIP_ERR_INVALID, an all-pass filter is the unfiltered search, a filter
+ * that keeps nothing gives counts 0, k is capped at the kept rows, and the bf16 / int8 shadow is used where that call
+ * would use it.  A filter of 32 all-ones words costs no device work and runs cqs_hip_index_search with a NULL bitset;
+ * any other runs one small kernel on the handle's stream and waits for its exact kept-row count before the scan.
+ * Concurrency: the call holds the handle's mutex throughout, like a filtered search with b > 1; tagged callers are NOT
+ * combined by the queue (all-pass ones are, being unfiltered searches).
+ * count_tagged: *out_kept = the rows `allow` keeps - the same kernel and count, no search (same checks). */
+int32_t  cqs_hip_index_count_tagged(cqs_hip_index* idx, const uint32_t* allow, uint64_t* out_kept);
+int32_t  cqs_hip_index_search_tagged(cqs_hip_index* idx, const float* queries, uint32_t b, uint32_t query_dim,
+                                     uint32_t k, const uint32_t* allow, uint32_t mode, float threshold,
+                                     uint64_t* out_rows, float* out_scores, uint32_t* out_counts);
+
 /* Combining-queue counters of a handle since it was made: passes the queue ran and the
  * queries they carried (queries / passes = mean callers per pass), unfiltered callers only.
  * Either pointer may be NULL.  Diagnostic; not part of the VectorIndex trait. */
@@ -608,6 +650,19 @@ int32_t cqs_hip_sparse_index_remove(cqs_hip_sparse_index* idx, const uint64_t* c
  * existing one, in the order given.  On a handle created without id_rank, new_rank must be NULL. */
 int32_t cqs_hip_sparse_index_extend(cqs_hip_sparse_index* idx, const uint64_t* doc_off, const uint32_t* tokens,
                                     const float* weights, uint64_t n_new, const uint32_t* new_rank);
+/* Chunk tags (tags, filter and rules as cqs_hip_index_set_tags / _search_tagged above): one uint32_t per
+ * chunk INDEX (what keep_bitset is indexed by, whatever the id order).  The tagged chunks are a prefix [0, tagged_chunks);
+ * set_tags overwrites inside it and / or extends it; a gap, a range past len and NULL tags with m > 0 are INVALID with
+ * the handle untouched.  extend leaves the prefix alone; remove renumbers the tags with the chunks and drops the prefix
+ * by the number of removed chunks below it; save / load do not persist tags.
+ * search_tagged: INVALID for a NULL allow or tagged_chunks < len; otherwise the bytes of cqs_hip_sparse_index_search with
+ * the host bitset of the same predicate (an all-ones filter: the keep_bitset == NULL call).  The bitset is written on the
+ * device in front of the scoring launch; the call has no extra wait.  The batch call has no tagged twin. */
+int32_t  cqs_hip_sparse_index_set_tags(cqs_hip_sparse_index* idx, uint64_t first_chunk, const uint32_t* tags, uint64_t m);
+uint64_t cqs_hip_sparse_index_tagged_chunks(const cqs_hip_sparse_index* idx);
+int32_t  cqs_hip_sparse_index_search_tagged(cqs_hip_sparse_index* idx, const uint32_t* q_tokens, const float* q_weights,
+                                            uint32_t n_terms, uint32_t k, const uint32_t* allow, uint64_t* out_chunks,
+                                            float* out_scores, uint32_t* out_count);
 /* Concurrent callers: unfiltered single-query cqs_hip_sparse_index_search calls on one handle are combined into shared
  * batches like the dense index's (CQS_HIP_COMBINE=0 / CQS_HIP_COMBINE_WAIT_US, read at create); every caller gets the bits
  * its own call would have produced.  Counters since the handle was made: batches run through the queue and the queries they

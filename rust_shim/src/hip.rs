@@ -23,6 +23,8 @@ use std::os::raw::c_char;
 use std::sync::atomic::{AtomicBool, Ordering};
 
 use crate::embedder::Embedding;
+use crate::hip_tags::TagCodes;
+use crate::parser::{ChunkType, Language};
 use crate::index::{BackendContext, DistanceMetric, IndexBackend, IndexResult, VectorIndex};
 use crate::store::{ClearHnswDirty, Store, StoreError};
 
@@ -116,6 +118,23 @@ extern "C" {
         out_counts: *mut u32,
     ) -> i32;
     fn cqs_hip_index_combine_filter_stats(idx: *const CqsHipIndex, passes: *mut u64, queries: *mut u64);
+    // row tags (include/cqs_hip.h, "row tags"): one u32 per row beside the corpus, filtered search without a host bitset
+    fn cqs_hip_index_set_tags(idx: *mut CqsHipIndex, first_row: u64, tags: *const u32, m: u64) -> i32;
+    fn cqs_hip_index_tagged_rows(idx: *const CqsHipIndex) -> u64;
+    fn cqs_hip_index_count_tagged(idx: *mut CqsHipIndex, allow: *const u32, out_kept: *mut u64) -> i32;
+    fn cqs_hip_index_search_tagged(
+        idx: *mut CqsHipIndex,
+        queries: *const f32,
+        b: u32,
+        query_dim: u32,
+        k: u32,
+        allow: *const u32,
+        mode: u32,
+        threshold: f32,
+        out_rows: *mut u64,
+        out_scores: *mut f32,
+        out_counts: *mut u32,
+    ) -> i32;
 }
 
 /// Exact brute-force GPU index (HBM-resident `[n, dim]` f32 + top-k on device).
@@ -130,6 +149,8 @@ pub struct HipIndex {
     poisoned: AtomicBool,
     /// chunk id -> row, built by the first `mmr_rerank` (a pool names up to 1024 ids per query) and dropped by `extend` / `remove`.
     row_of: std::sync::OnceLock<std::collections::HashMap<Box<str>, u64>>,
+    /// The codes behind the rows' tags (`set_chunk_meta`); `None`: no tags, `search_with_tags` builds the bitset.
+    tag_codes: Option<TagCodes>,
 }
 
 // SAFETY: the handle serialises device access behind its own mutex (include/cqs_hip.h,
@@ -252,6 +273,7 @@ impl HipIndex {
             metric,
             poisoned: AtomicBool::new(false),
             row_of: std::sync::OnceLock::new(),
+            tag_codes: None,
         })
     }
 
@@ -293,6 +315,92 @@ impl HipIndex {
         self.id_map.extend(ids.into_iter().map(String::into_boxed_str));
         self.row_of = std::sync::OnceLock::new();
         Ok(())
+    }
+
+    /// Tag every row with its (chunk type, language) codes from `Store::chunk_type_language_map` - call it once after the
+    /// index is opened (built, loaded or extended: tags are not persisted, and `extend` leaves the new rows without one).
+    /// From then on `search_with_tags` filters on the device.  Returns false, and leaves the index on the host-bitset
+    /// path, when a field would need more than 255 codes or the library refuses the tags.
+    pub fn set_chunk_meta(&mut self, meta: &std::collections::HashMap<String, (ChunkType, Language)>) -> bool {
+        self.tag_codes = None;
+        let Some(codes) = TagCodes::assign(meta) else {
+            tracing::info!("HIP index: more than 255 chunk types or languages, filtered searches keep the host bitset");
+            return false;
+        };
+        let tags: Vec<u32> = self.id_map.iter().map(|id| codes.tag_of(id, meta)).collect();
+        // (handles made here have row_base 0)
+        let rc = unsafe { cqs_hip_index_set_tags(self.handle, 0, tags.as_ptr(), tags.len() as u64) };
+        if rc != CQS_HIP_OK {
+            tracing::warn!(rc, error = %self.last_error(), "HIP index: set_tags refused, filtered searches keep the host bitset");
+            return false;
+        }
+        self.tag_codes = Some(codes);
+        true
+    }
+
+    /// `search_with_filter` for the predicate `search_hybrid_inner` builds (src/search/query.rs:860-877), without the
+    /// loop over every chunk id: the allowed sets go to the library, which writes the bitset on the device
+    /// (`cqs_hip_index_search_tagged`; same results as the bitset path, byte for byte).  Falls back to
+    /// `search_with_filter` with that predicate when the index has no tags (`set_chunk_meta` not called, or refused) or
+    /// they do not cover it (rows added since).  `meta` is only looked at on the fallback.
+    pub fn search_with_tags(
+        &self,
+        query: &Embedding,
+        k: usize,
+        include: Option<&[ChunkType]>,
+        exclude: Option<&[ChunkType]>,
+        languages: Option<&[Language]>,
+        meta: &std::collections::HashMap<String, (ChunkType, Language)>,
+    ) -> Vec<IndexResult> {
+        if self.id_map.is_empty() || k == 0 || query.len() != self.dim {
+            return Vec::new();
+        }
+        let covered = unsafe { cqs_hip_index_tagged_rows(self.handle) } as usize == self.id_map.len();
+        let Some(codes) = self.tag_codes.as_ref().filter(|_| covered) else {
+            let predicate = |id: &str| -> bool {
+                if include.is_none() && exclude.is_none() && languages.is_none() {
+                    return true;
+                }
+                meta.get(id).is_some_and(|(ct, lang)| {
+                    include.is_none_or(|t| t.contains(ct)) && exclude.is_none_or(|t| !t.contains(ct)) && languages.is_none_or(|l| l.contains(lang))
+                })
+            };
+            return self.search_with_filter(query, k, &predicate);
+        };
+        let allow = codes.allow(include, exclude, languages);
+        let k = k.min(unsafe { cqs_hip_index_max_k(self.handle) } as usize);
+        let mut rows = vec![0u64; k];
+        let mut scores = vec![0f32; k];
+        let mut count = 0u32;
+        let rc = unsafe {
+            cqs_hip_index_search_tagged(self.handle, query.as_slice().as_ptr(), 1, query.len() as u32, k as u32, allow.as_ptr(),
+                                        CQS_HIP_MODE_RAW, 0.0, rows.as_mut_ptr(), scores.as_mut_ptr(), &mut count)
+        };
+        if rc != CQS_HIP_OK {
+            if unsafe { cqs_hip_index_poisoned(self.handle) } != 0 {
+                self.poisoned.store(true, Ordering::Release);
+            }
+            tracing::error!(error = %self.last_error(), rc, "HIP tagged search failed");
+            return Vec::new();
+        }
+        (0..count as usize)
+            .filter_map(|i| {
+                self.id_map.get(rows[i] as usize).map(|id| IndexResult {
+                    id: id.to_string(),
+                    score: match self.metric {
+                        DistanceMetric::Cosine => scores[i].min(1.0),
+                        DistanceMetric::DotProduct => scores[i],
+                    },
+                })
+            })
+            .collect()
+    }
+
+    /// The rows a tag filter keeps (what the reference logs as `included`, src/cagra.rs:758); `None` without tags.
+    pub fn count_with_tags(&self, include: Option<&[ChunkType]>, exclude: Option<&[ChunkType]>, languages: Option<&[Language]>) -> Option<u64> {
+        let allow = self.tag_codes.as_ref()?.allow(include, exclude, languages);
+        let mut kept = 0u64;
+        (unsafe { cqs_hip_index_count_tagged(self.handle, allow.as_ptr(), &mut kept) } == CQS_HIP_OK).then_some(kept)
     }
 
     /// Delete chunks in place (the tiered backend's other purpose, "to clean orphaned vectors", src/tiered.rs:13-17):
@@ -397,6 +505,7 @@ impl HipIndex {
             metric,
             poisoned: AtomicBool::new(false),
             row_of: std::sync::OnceLock::new(),
+            tag_codes: None,
         };
         // the sidecar must describe THIS blob: its checksum is the one the library just verified against the rows
         let blob_metric = unsafe { cqs_hip_index_metric(idx.handle) };

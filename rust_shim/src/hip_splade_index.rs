@@ -12,7 +12,9 @@
 
 use std::os::raw::c_char;
 
+use crate::hip_tags::TagCodes;
 use crate::index::IndexResult;
+use crate::parser::{ChunkType, Language};
 use crate::splade::SparseVector;
 
 #[repr(C)]
@@ -84,6 +86,20 @@ extern "C" {
         n_new: u64,
         new_rank: *const u32,
     ) -> i32;
+    // chunk tags (include/cqs_hip.h, "Chunk tags"): filtered search without a host bitset
+    fn cqs_hip_sparse_index_set_tags(idx: *mut CqsHipSparseIndex, first_chunk: u64, tags: *const u32, m: u64) -> i32;
+    fn cqs_hip_sparse_index_tagged_chunks(idx: *const CqsHipSparseIndex) -> u64;
+    fn cqs_hip_sparse_index_search_tagged(
+        idx: *mut CqsHipSparseIndex,
+        q_tokens: *const u32,
+        q_weights: *const f32,
+        n_terms: u32,
+        k: u32,
+        allow: *const u32,
+        out_chunks: *mut u64,
+        out_scores: *mut f32,
+        out_count: *mut u32,
+    ) -> i32;
     fn cqs_hip_sparse_index_last_search(idx: *const CqsHipSparseIndex, accumulate_ms: *mut f32, touched_postings: *mut u64) -> i32;
     fn cqs_hip_sparse_index_poisoned(idx: *const CqsHipSparseIndex) -> i32;
     fn cqs_hip_sparse_index_last_error(idx: *const CqsHipSparseIndex, buf: *mut c_char, cap: usize) -> usize;
@@ -94,6 +110,8 @@ pub struct HipSpladeIndex {
     raw: *mut CqsHipSparseIndex,
     /// chunk id of every position of the build order - the library answers in positions.
     id_map: Vec<Box<str>>,
+    /// The codes behind the chunks' tags (`set_chunk_meta`); `None`: no tags, `search_with_tags` builds the bitset.
+    tag_codes: Option<TagCodes>,
 }
 
 // The handle serialises device work behind its own mutex (include/cqs_hip.h, threading note).
@@ -135,7 +153,7 @@ impl HipSpladeIndex {
             return None;
         }
         tracing::info!(chunks = n, postings = total, "HIP SPLADE index built");
-        Some(Self { raw, id_map })
+        Some(Self { raw, id_map, tag_codes: None })
     }
 
     /// From an index the CPU side already holds - e.g. right after `SpladeIndex::load` read `splade.index.bin` - without
@@ -173,7 +191,7 @@ impl HipSpladeIndex {
             tracing::warn!(rc, "HIP SPLADE index build from postings failed, keeping the in-memory index");
             return None;
         }
-        Some(Self { raw, id_map: id_map.to_vec() })
+        Some(Self { raw, id_map: id_map.to_vec(), tag_codes: None })
     }
 
     /// Delete chunks by id in place, beside `HipIndex::remove` on the dense leg (the watch loop's deletions; "clean
@@ -259,7 +277,7 @@ impl HipSpladeIndex {
         if rc != CQS_HIP_OK || raw.is_null() {
             return None;
         }
-        Some(Self { raw, id_map })
+        Some(Self { raw, id_map, tag_codes: None })
     }
 
     /// Largest `k` one call serves (the library's top-k capacity).  The reference asks the sparse leg for
@@ -295,6 +313,70 @@ impl HipSpladeIndex {
             Some(keep) => self.search_keep(query, k, Some(&keep)),
             None => self.search_keep(query, k, None),          // the predicate kept everything
         }
+    }
+
+    /// Tag every chunk with its (chunk type, language) codes from `Store::chunk_type_language_map`, beside
+    /// `HipIndex::set_chunk_meta` on the dense leg - once after the index is opened (tags are not persisted) and again
+    /// after `extend`.  Returns false, and leaves the index on the host-bitset path, when a field would need more than
+    /// 255 codes or the library refuses the tags.
+    pub fn set_chunk_meta(&mut self, meta: &std::collections::HashMap<String, (ChunkType, Language)>) -> bool {
+        self.tag_codes = None;
+        let Some(codes) = TagCodes::assign(meta) else { return false };
+        let tags: Vec<u32> = self.id_map.iter().map(|id| codes.tag_of(id, meta)).collect();
+        let rc = unsafe { cqs_hip_sparse_index_set_tags(self.raw, 0, tags.as_ptr(), tags.len() as u64) };
+        if rc != CQS_HIP_OK {
+            tracing::warn!(rc, error = %self.last_error(), "HIP SPLADE index: set_tags refused, filtered searches keep the host bitset");
+            return false;
+        }
+        self.tag_codes = Some(codes);
+        true
+    }
+
+    /// `search_with_filter` for the predicate `search_hybrid_inner` builds (src/search/query.rs:860-877) without a call
+    /// per chunk id: the allowed sets go to the library (`cqs_hip_sparse_index_search_tagged`; the bytes of the bitset
+    /// path).  Falls back to `search_with_filter` with that predicate when the index has no tags or they do not cover it.
+    pub fn search_with_tags(
+        &self,
+        query: &SparseVector,
+        k: usize,
+        include: Option<&[ChunkType]>,
+        exclude: Option<&[ChunkType]>,
+        languages: Option<&[Language]>,
+        meta: &std::collections::HashMap<String, (ChunkType, Language)>,
+    ) -> Vec<IndexResult> {
+        if query.is_empty() || self.id_map.is_empty() || k == 0 {
+            return Vec::new();
+        }
+        let covered = unsafe { cqs_hip_sparse_index_tagged_chunks(self.raw) } as usize == self.id_map.len();
+        let Some(codes) = self.tag_codes.as_ref().filter(|_| covered) else {
+            let predicate = |id: &str| -> bool {
+                if include.is_none() && exclude.is_none() && languages.is_none() {
+                    return true;
+                }
+                meta.get(id).is_some_and(|(ct, lang)| {
+                    include.is_none_or(|t| t.contains(ct)) && exclude.is_none_or(|t| !t.contains(ct)) && languages.is_none_or(|l| l.contains(lang))
+                })
+            };
+            return self.search_with_filter(query, k, &predicate);
+        };
+        let allow = codes.allow(include, exclude, languages);
+        let k = self.clamp_k(k);
+        let q_tokens: Vec<u32> = query.iter().map(|&(t, _)| t).collect();
+        let q_weights: Vec<f32> = query.iter().map(|&(_, w)| w).collect();
+        let mut chunks = vec![0u64; k];
+        let mut scores = vec![0f32; k];
+        let mut count = 0u32;
+        let rc = unsafe {
+            cqs_hip_sparse_index_search_tagged(self.raw, q_tokens.as_ptr(), q_weights.as_ptr(), q_tokens.len() as u32, k as u32,
+                                               allow.as_ptr(), chunks.as_mut_ptr(), scores.as_mut_ptr(), &mut count)
+        };
+        if rc != CQS_HIP_OK {
+            tracing::warn!(rc, error = %self.last_error(), "HIP SPLADE tagged search failed");
+            return Vec::new();
+        }
+        (0..count as usize)
+            .filter_map(|i| self.id_map.get(chunks[i] as usize).map(|id| IndexResult { id: id.to_string(), score: scores[i] }))
+            .collect()
     }
 
     /// The keep-bitset of a predicate over this index's chunk ids (bit i = chunk i kept); `None` when it keeps every
