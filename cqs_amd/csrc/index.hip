@@ -454,10 +454,15 @@ int32_t cqs_hip_index_search_device(cqs_hip_index* x, const float* d_queries, ui
     // gate words.  The f32 scan + select that follow return at entry when every query is certified, else recompute the whole
     // block, which is harmless (gemv-pass scores do not depend on which queries share a pass; a certified answer is the f32
     // one).  `done` is recorded after the gated select, so the cross-stream hand-off covers the shadow's scratch too.
+    // Where it applies the fallback is ONE gated launch instead (shadow_fallback: an exact brute-force top-k of the block).
     const uint32_t* gate = nullptr;
-    if (shadow_takes(x, b, k, /*gemv_only=*/false) &&
-        (rc = shadow_pass(x, d_queries, b, k, d_keep_bitset, mode, threshold, d_out_keys, d_out_counts, st, &gate)) != CQS_HIP_OK)
-        return rc;
+    if (shadow_takes(x, b, k, /*gemv_only=*/false)) {
+        if ((rc = shadow_pass(x, d_queries, b, k, d_keep_bitset, mode, threshold, d_out_keys, d_out_counts, st, &gate)) != CQS_HIP_OK)
+            return rc;
+        bool taken = false;
+        rc = shadow_fallback(x, d_queries, b, k, d_keep_bitset, mode, threshold, d_out_keys, d_out_counts, st, gate, &taken);
+        if (rc != CQS_HIP_OK || taken) return rc;
+    }
     return enqueue_search(x, d_queries, b, k, d_keep_bitset, mode, threshold, d_out_keys, d_out_counts, st, false, gate);
 } CQS_ABI_CATCH(x)
 

@@ -196,6 +196,10 @@ bool shadow_uses_i8(const cqs_hip_index* x, uint32_t b, uint32_t k);   // of a b
 int32_t shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k, const uint32_t* d_keep, uint32_t mode,
                     float thr, uint64_t* out_keys, uint32_t* out_counts, hipStream_t st, const uint32_t** device_gate,
                     const KeepTab* tab = nullptr);
+// The gated f32 fallback behind a device-API shadow_pass as one launch; *taken = false: not this block (the caller enqueues
+// the gated scan + select).
+int32_t shadow_fallback(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k, const uint32_t* d_keep, uint32_t mode,
+                        float thr, uint64_t* out_keys, uint32_t* out_counts, hipStream_t st, const uint32_t* gate, bool* taken);
 // The last host shadow pass's verdicts, pinned, valid after x->stream's wait (queues their copy when not mappable).
 hipError_t shadow_verdicts(cqs_hip_index* x, uint32_t nb, const uint32_t** h_cert);
 

@@ -7,6 +7,7 @@
 #include "abi_guard.h"
 #include "index_internal.h"
 #include "scan_bf16.h"
+#include "scan_fallback.h"
 #include "scan_i8.h"
 
 namespace cqs_idx {
@@ -43,6 +44,11 @@ struct Shadow {
                                           // searches: launch_shadow_bound / launch_i8_bound, ahead of the scan that reads it)
     uint32_t* d_tickets = nullptr;        // [kShadowMaxQ] arrival counts of the tail kernel's workgroups: zeroed here once,
                                           // put back to zero by every launch (launch_rescore_certify)
+    uint64_t* d_fb_lists = nullptr;       // [kMaxGemvQ, n_cu, kFallbackMaxK] the one-launch f32 fallback's hand-off scratch
+    uint32_t* d_fb_tickets = nullptr;     // [kMaxGemvQ] ... and its arrival counts: zeroed here once, put back to zero by every
+                                          // launch (scan_fallback.h)
+    bool fb_one_launch = true;            // CQS_HIP_FALLBACK_ONE_LAUNCH, read when the shadow is built: 0 = the device-API searches'
+                                          // f32 fallback is always the gated scan + select pair
     uint32_t* h_cert = nullptr;           // pinned [kShadowMaxQ]
     uint32_t* h_cert_dev = nullptr;       // its device-visible address (null: not mappable)
 };
@@ -78,7 +84,8 @@ void shadow_free(cqs_hip_index* x) {
     x->stat_i8_fallbacks.fetch_add(f, std::memory_order_relaxed);
     i8_free(s);
     hipFree(s->d_bf16); hipFree(s->d_stats); hipFree(s->d_ekeys);
-    hipFree(s->d_cert); hipFree(s->d_bq); hipFree(s->d_tickets); hipHostFree(s->h_cert);
+    hipFree(s->d_cert); hipFree(s->d_bq); hipFree(s->d_tickets); hipFree(s->d_fb_lists); hipFree(s->d_fb_tickets);
+    hipHostFree(s->h_cert);
     delete s;
     x->shadow = nullptr;
 }
@@ -216,6 +223,11 @@ static int32_t shadow_enable(cqs_hip_index* x, const char* what) {
     if ((e = hipMalloc(&s->d_bq, (size_t)cqs::kShadowMaxQ * sizeof(float))) != hipSuccess) return oom(e);
     if ((e = hipMalloc(&s->d_tickets, (size_t)cqs::kShadowMaxQ * sizeof(uint32_t))) != hipSuccess) return oom(e);
     if ((e = hipMemsetAsync(s->d_tickets, 0, (size_t)cqs::kShadowMaxQ * sizeof(uint32_t), x->stream)) != hipSuccess) return oom(e);
+    const char* fb_env = getenv("CQS_HIP_FALLBACK_ONE_LAUNCH");
+    s->fb_one_launch = !(fb_env && fb_env[0] == '0');
+    if ((e = hipMalloc(&s->d_fb_lists, cqs::f32_topk_fallback_words(x->n_cu) * sizeof(uint64_t))) != hipSuccess) return oom(e);
+    if ((e = hipMalloc(&s->d_fb_tickets, (size_t)cqs::kMaxGemvQ * sizeof(uint32_t))) != hipSuccess) return oom(e);
+    if ((e = hipMemsetAsync(s->d_fb_tickets, 0, (size_t)cqs::kMaxGemvQ * sizeof(uint32_t), x->stream)) != hipSuccess) return oom(e);
     if ((e = hipHostMalloc(&s->h_cert, (size_t)cqs::kShadowMaxQ * sizeof(uint32_t), hipHostMallocDefault)) != hipSuccess) return oom(e);
     if (hipHostGetDevicePointer((void**)&s->h_cert_dev, s->h_cert, 0) != hipSuccess) {
         (void)hipGetLastError();
@@ -287,7 +299,8 @@ int32_t shadow_auto(cqs_hip_index* x) {
         return CQS_HIP_OK;
     }
     const uint64_t cap = x->cap_rows ? x->cap_rows : 1;
-    const uint64_t need = cap * x->dim * sizeof(uint16_t) + (cqs::kMaxK + 2ull) * cqs::kShadowMaxQ * sizeof(uint64_t);
+    const uint64_t need = cap * x->dim * sizeof(uint16_t) + (cqs::kMaxK + 2ull) * cqs::kShadowMaxQ * sizeof(uint64_t) +
+                          cqs::f32_topk_fallback_words(x->n_cu) * sizeof(uint64_t);
     const uint64_t frac = (uint64_t)(kShadowFreeFrac * (double)total_b);
     const uint64_t reserve = frac > kShadowFreeMinBytes ? frac : kShadowFreeMinBytes;
     if (free_b < need || free_b - need < reserve) {
@@ -346,6 +359,25 @@ int32_t shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k,
                                                device_gate ? s->d_stats + kStatCounts : nullptr,
                                                device_gate && i8 ? s->d_stats + kStatI8Counts : nullptr, st));
     return rc;
+}
+
+// The f32 fallback of a device-API search behind shadow_pass on the same stream, gated by its verdicts.  One launch where
+// that form takes the block (scan_fallback.h: b <= 8, k <= kFallbackMaxK, no per-query table) and the handle's switch is on;
+// else *taken = false and the caller enqueues the gated scan + select pair.  Nothing is launched between the tail kernel and
+// this launch (gate_closed), and `done` is recorded after it: the next search, on any stream, is ordered after every user of
+// the hand-off scratch and its tickets.
+int32_t shadow_fallback(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k, const uint32_t* d_keep, uint32_t mode,
+                        float threshold, uint64_t* out_keys, uint32_t* out_counts, hipStream_t st, const uint32_t* gate,
+                        bool* taken) {
+    const Shadow* s = x->shadow;
+    *taken = false;
+    if (!s || !gate || !s->fb_one_launch) return CQS_HIP_OK;
+    const cqs::ScanArgs a = scan_args(x, d_q, nb, k, d_keep, mode, threshold, sizeof(float), false, nullptr, gate);
+    if (!cqs::f32_topk_fallback_takes(a)) return CQS_HIP_OK;
+    HIP_TRY(x, cqs::launch_f32_topk_fallback(a, (uint32_t)x->row_base, gate, s->d_fb_lists, s->d_fb_tickets, out_keys, out_counts, st));
+    HIP_TRY(x, record_done(x, st));
+    *taken = true;
+    return CQS_HIP_OK;
 }
 
 hipError_t shadow_verdicts(cqs_hip_index* x, uint32_t nb, const uint32_t** h_cert) {

@@ -15,6 +15,7 @@
 // Wave = 64 lanes.  gfx950 only.
 #include "scan_bf16.h"
 #include "scan_i8.h"
+#include "f32_score.h"
 #include "launch_util.h"
 #include "rank_sort.h"
 #include "scan_gemv_device.h"
@@ -447,33 +448,11 @@ __global__ __launch_bounds__(1024) void rescore_certify_kernel(const TailParams 
         const uint64_t key = akeys[i];
         const uint32_t grow = 0xFFFFFFFFu - (uint32_t)key;
         const float* rp = p.rows + (size_t)(grow - p.row_base) * dim;
+        // the exact score and scan_gemv_kernel's epilogue: f32_score.h, shared with the one-launch f32 fallback
         f4 x[NCH], qv[NCH];
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const uint32_t idx = (uint32_t)c * 256u + lane * 4u;
-            const bool in = idx < dim;
-            const uint32_t off = in ? idx : dim - 4u;
-            x[c] = *(const f4*)(rp + off);
-            const f4 v = *(const f4*)(qp + off);
-            qv[c] = in ? v : (f4)(0.f);
-        }
-        f2 acc2 = (f2)(0.f);
-#pragma unroll
-        for (int c = 0; c < NCH; ++c) {
-            const f2 xlo = __builtin_shufflevector(x[c], x[c], 0, 1);
-            const f2 xhi = __builtin_shufflevector(x[c], x[c], 2, 3);
-            acc2 = __builtin_elementwise_fma(xlo, __builtin_shufflevector(qv[c], qv[c], 0, 1), acc2);
-            acc2 = __builtin_elementwise_fma(xhi, __builtin_shufflevector(qv[c], qv[c], 2, 3), acc2);
-        }
-        float s = acc2.x + acc2.y;
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
-        // scan_gemv_kernel's epilogue: non-finite dropped; PIPELINE: clamp(0, 1) then `>= threshold`
-        bool keep = __builtin_fabsf(s) <= 3.4028234664e38f;
-        if (keep && p.mode == 1u) {
-            s = s < 0.f ? 0.f : (s > 1.f ? 1.f : s);
-            keep = s >= p.thr;
-        }
+        f32_fragments<NCH>(rp, qp, dim, lane, x, qv);
+        float s = f32_dot_chain<NCH>(x, qv);
+        const bool keep = f32_emit(s, p.mode, p.thr);
         if (lane == 0u)
             __hip_atomic_store(p.ekeys + (size_t)qi * p.kprime + i, keep ? pack_key(okey(s), grow) : 0ull, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);

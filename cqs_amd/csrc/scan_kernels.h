@@ -106,7 +106,12 @@ inline bool keep_tab_ok(const ScanArgs& a) {
 //    boundaries on one stream either side).  A gated scan runs on the persistent grid (launch_gemv) and does dequeue from
 //    them when its gate is open; the gated select that follows then re-zeroes them;
 //  - the launches between the shadow's tail kernel and the gated select include no memset (gemv blocks of <= 32 queries
-//    stay under kWorkWords launches); a memset added there must be gated too.
+//    stay under kWorkWords launches); a memset added there must be gated too;
+//  - the one-launch form of the fallback (scan_fallback.hip, f32_topk_fallback_kernel: the blocks scan_fallback.h takes)
+//    stands in the pair's place: the same words, the same decision, at entry in every wave before any other load or barrier;
+//    nothing is launched between the tail kernel and it; gate open or closed it never touches the work-queue heads, the
+//    score rows, gmax or gaux (it has no work queue and no score row), so the heads stay as the tail kernel zeroed them; its
+//    own tickets are zero between launches (the finisher of each query puts its ticket back).
 __device__ __forceinline__ bool gate_closed(const uint32_t* gate, uint32_t b) {
     uint32_t all = 1u;
     for (uint32_t i = 0; i < b; ++i) all &= gate[i];   // (uniform: scalar loads, no vector registers at entry)
