@@ -223,7 +223,7 @@ bool ensure_keep_tab(cqs_hip_index* x) {
 void read_combine_env(cqs_hip_index* x) {                                              // read once per handle
     if (const char* ce = getenv("CQS_HIP_COMBINE")) x->combine = ce[0] != '0';
     if (const char* cf = getenv("CQS_HIP_COMBINE_FILTERED")) x->combine_filtered = cf[0] != '0';
-    if (const char* cw = getenv("CQS_HIP_COMBINE_WAIT_US")) x->combine_wait_us = (uint32_t)atoi(cw);
+    x->cq.wait_us = cqs_combine::wait_us_from_env();
     if (const char* cb = getenv("CQS_HIP_COMBINE_BITS")) x->combine_relaxed = cb[0] == 'r';
 }
 

@@ -5,18 +5,19 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <deque>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/cqs_hip.h"
+#include "combine_queue.h"
 #include "scan_kernels.h"
 
 namespace cqs_sharded { struct ShardSet; }
-namespace cqs_idx { struct Shadow; }
+namespace cqs_idx {
+struct Shadow;
+constexpr uint32_t kCombineCap = 32;         // queries per combined block (4 passes of 8) = rows of the handle's bitset table
+}
 namespace cqs_mmr { struct Scratch; }
 namespace cqs_search { struct Args; }
 
@@ -91,23 +92,16 @@ struct cqs_hip_index {
     std::atomic<bool> poisoned{false};
     std::string last_error;
 
-    // Combining queue (index_combine.hip, cqs_hip_index_search): concurrent single-query callers park here and ride ONE pass
-    // over the corpus (up to kMaxGemvQ queries share the HBM stream in registers).  `cmu` orders the queue only; the
-    // device work itself still runs under `mu`.  The reference serialises its callers behind Mutex<GpuState>
+    // Combining queue (combine_queue.h; index_combine.hip, cqs_hip_index_search): concurrent single-query callers park here and
+    // ride ONE pass over the corpus (up to kMaxGemvQ queries share the HBM stream in registers).  cq.mu orders the queue only;
+    // the device work itself still runs under `mu`.  The reference serialises its callers behind Mutex<GpuState>
     // (src/cagra.rs:263) one search at a time; the daemon calls `search` from one thread per client
-    // (src/cli/watch/daemon.rs:273).
-    std::mutex cmu;
-    std::condition_variable ccv;
-    std::deque<cqs_combine_req*> pending;
-    std::atomic<uint32_t> n_pending{0};   // = pending.size(), readable without cmu (the leader's short wait for stragglers)
-    bool leader = false;                  // somebody is collecting / running a combined pass
-    uint32_t expect = 1;                  // callers the next pass should expect (what recent passes saw); guarded by cmu
+    // (src/cli/watch/daemon.rs:273).  cq.wait_us is CQS_HIP_COMBINE_WAIT_US.
+    cqs_combine::Queue<cqs_combine_req, cqs_idx::kCombineCap> cq;
     bool combine = true;                  // CQS_HIP_COMBINE=0: every caller takes the serial path
     bool combine_relaxed = false;         // CQS_HIP_COMBINE_BITS=relaxed: blocks of >= 9 callers may run on the matrix cores (32 queries per
                                           // sweep instead of 8): answers within the parity tolerance of the lone call's, not its bits
     bool combine_filtered = true;         // CQS_HIP_COMBINE_FILTERED=0: single-query callers with a bitset take the serial path
-    uint32_t combine_wait_us = 100;       // CQS_HIP_COMBINE_WAIT_US: how long after the END of a pass the next leader waits for the callers that pass carried
-    std::chrono::steady_clock::time_point last_pass_end{};   // guarded by cmu (epoch until the first pass: nobody waits)
     std::atomic<uint64_t> stat_passes{0}, stat_queries{0};   // combined passes run / queries they carried (unfiltered callers)
     std::atomic<uint64_t> stat_fpasses{0}, stat_fqueries{0}; // the same for the blocks of callers with a bitset
     std::atomic<int32_t> inject_fail{0};  // test hook (cqs_hip_debug_index_fail_next): the next host search (or remove) fails as a device error
@@ -137,7 +131,6 @@ constexpr size_t kMaxTimingEvents = 8192;
 constexpr uint64_t kNtBytes = 200ull << 20;  // corpus larger than this streams past L2/MALL
 constexpr uint32_t kGauxQueries = 32;        // query blocks up to this size (every gemv block the host paths form) carry the select's (argmax, runner-up) index
 constexpr uint32_t kGauxMinK = 100;          // ... and only from this k on (below it the gather it replaces is a few groups)
-constexpr uint32_t kCombineCap = 32;         // queries per combined block (4 passes of 8) = rows of the handle's bitset table
 constexpr size_t kDirectOutKeys = 8192;      // host searches of up to this many result keys have them written straight to pinned host memory
 
 uint64_t pad_rows(uint64_t n);

@@ -21,16 +21,12 @@
 
 #include <algorithm>
 #include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <deque>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <string>
-#include <thread>
 #include <unordered_map>
 #include <vector>
 
@@ -344,7 +340,7 @@ int32_t finish_create(cqs_hip_sparse_index* s, const std::vector<uint2>& post, i
     if (const char* e = getenv("CQS_HIP_DEBUG_STAMPS"); e && *e == '1')
         if (hipMalloc((void**)&s->d_dbg, 16 * 8) == hipSuccess) (void)hipMemset(s->d_dbg, 0, 16 * 8);
     if (const char* e = getenv("CQS_HIP_COMBINE")) s->combine = !(e[0] == '0');
-    if (const char* e = getenv("CQS_HIP_COMBINE_WAIT_US")) s->combine_wait_us = (uint32_t)strtoul(e, nullptr, 10);
+    s->cq.wait_us = cqs_combine::wait_us_from_env();
     return CQS_HIP_OK;
 }
 
@@ -856,115 +852,50 @@ extern "C" {
 
 namespace {
 
-// ---- the combining queue: the dense index's scheme (index.hip) over the batched launches -----------------
+// ---- the combining queue (combine_queue.h) over the batched launches -----------------------------------------
 // The reference's daemon calls `search_with_filter(&self)` from one thread per client on a shared index
 // (src/cli/batch/view.rs:1621, src/search/query.rs:898-901).  An unfiltered single-query call parks its request; whoever
-// leads next takes the device mutex first, gathers the parked requests with the same k (oldest first, up to 64) and runs
-// them as one batch - every caller gets exactly the bits its own call would have produced (the kernels treat the queries
-// of a batch independently).  Requests are validated BEFORE they park, so a batch can only fail for the device.
-uint32_t count_like_front(const cqs_hip_sparse_index* s) {
-    uint32_t n = 0;
-    for (const cqs_sparse_req* r : s->pending) n += r->k == s->pending.front()->k ? 1u : 0u;
-    return n;
-}
-
-// Lead one batch.  `lk` holds cmu on entry and on exit; s->leader is set by the caller.
-void sparse_combine_lead(cqs_hip_sparse_index* s, std::unique_lock<std::mutex>& lk) {
-    // stragglers of the last pass are on their way back: wait for them until combine_wait_us after that pass ENDED (a caller
-    // that comes alone later than that does not wait), without the device mutex (round 5, as index.hip's combine_lead)
-    const uint32_t target = s->expect < kSparseMaxBatch ? s->expect : kSparseMaxBatch;
-    if (s->combine_wait_us && count_like_front(s) < target) {
-        const auto t_end = s->last_pass_end + std::chrono::microseconds(s->combine_wait_us);
-        while (count_like_front(s) < target && std::chrono::steady_clock::now() < t_end) {
-            lk.unlock();
-            for (int i = 0; i < 64; ++i) __builtin_ia32_pause();
-            lk.lock();
-        }
-    }
-    cqs_sparse_req* batch[kSparseMaxBatch];
-    uint32_t nb = 0, left_like = 0;
-    {
-        const uint32_t k0 = s->pending.front()->k;
-        std::deque<cqs_sparse_req*> keep;
-        for (cqs_sparse_req* r : s->pending) {
-            if (r->k == k0) {
-                if (nb < kSparseMaxBatch) { batch[nb++] = r; continue; }
-                ++left_like;
-            }
-            keep.push_back(r);
-        }
-        s->pending.swap(keep);
-    }
-    s->expect = nb + left_like;
-    lk.unlock();
-    std::unique_lock<std::mutex> dev(s->mu);               // the device, for the batch alone
-
-    int32_t rc = CQS_HIP_OK;
-    const uint32_t k = batch[0]->k;
-    std::vector<uint32_t> counts(nb, 0u);
-    std::vector<uint64_t> chunks;
-    std::vector<float> scores;
-    try {
-        std::vector<uint64_t> q_off(nb + 1, 0);
-        for (uint32_t i = 0; i < nb; ++i) q_off[i + 1] = q_off[i] + batch[i]->n_terms;
-        std::vector<uint32_t> toks((size_t)q_off[nb]);
-        std::vector<float> wts((size_t)q_off[nb]);
-        for (uint32_t i = 0; i < nb; ++i) {
-            if (batch[i]->n_terms == 0) continue;
-            memcpy(toks.data() + q_off[i], batch[i]->q_tokens, (size_t)batch[i]->n_terms * 4);
-            memcpy(wts.data() + q_off[i], batch[i]->q_weights, (size_t)batch[i]->n_terms * 4);
-        }
-        chunks.resize((size_t)nb * k);
-        scores.resize((size_t)nb * k);
-        rc = search_locked(s, q_off.data(), toks.data(), wts.data(), nb, k, nullptr, chunks.data(), scores.data(), counts.data());
-    } catch (const std::bad_alloc&) {
-        rc = sfail(s, CQS_HIP_ERR_NOMEM, "sparse search: out of host memory");
-    } catch (...) {
-        rc = sfail(s, CQS_HIP_ERR_INVALID, "sparse search: unexpected C++ exception");
-    }
-    s->stat_passes.fetch_add(1, std::memory_order_relaxed);
-    s->stat_queries.fetch_add(nb, std::memory_order_relaxed);
-    const bool poisoned = s->poisoned.load(std::memory_order_acquire);
-    if (rc == CQS_HIP_OK)
-        for (uint32_t i = 0; i < nb; ++i) {
-            memcpy(batch[i]->out_chunks, chunks.data() + (size_t)i * k, (size_t)counts[i] * 8);
-            memcpy(batch[i]->out_scores, scores.data() + (size_t)i * k, (size_t)counts[i] * 4);
-            *batch[i]->out_count = counts[i];
-        }
-    dev.unlock();
-
-    lk.lock();
-    s->last_pass_end = std::chrono::steady_clock::now();
-    for (uint32_t i = 0; i < nb; ++i) {
-        batch[i]->rc = (rc != CQS_HIP_OK && i > 0 && poisoned) ? CQS_HIP_ERR_POISONED : rc;
-        batch[i]->done = true;
-    }
-    if (poisoned) {                                        // nobody stays parked on a dead handle
-        for (cqs_sparse_req* r : s->pending) { r->rc = CQS_HIP_ERR_POISONED; r->done = true; }
-        s->pending.clear();
-    } else if (!s->pending.empty()) {
-        uint32_t like = 0;
-        for (const cqs_sparse_req* r : s->pending) like += r->k == k ? 1u : 0u;
-        if (nb + like > s->expect) s->expect = nb + like;
-    }
-}
-
+// leads next gathers the parked requests with the same k (oldest first, up to 64), takes the device mutex and runs them as
+// one batch - every caller gets exactly the bits its own call would have produced (the kernels treat the queries of a
+// batch independently).  Requests are validated BEFORE they park, so a batch can only fail for the device.
 int32_t sparse_combine_search(cqs_hip_sparse_index* s, cqs_sparse_req& r) {
-    std::unique_lock<std::mutex> lk(s->cmu);
-    s->pending.push_back(&r);
-    while (!r.done) {
-        if (!s->leader) {
-            s->leader = true;
-            struct Reset {                                 // whatever happens in there, the next caller can lead
-                cqs_hip_sparse_index* s; std::unique_lock<std::mutex>& lk;
-                ~Reset() { if (!lk.owns_lock()) lk.lock(); s->leader = false; s->ccv.notify_all(); }
-            } reset{s, lk};
-            sparse_combine_lead(s, lk);
-        } else {
-            s->ccv.wait(lk);
+    const auto same_k = [](const cqs_sparse_req* a, const cqs_sparse_req* b) { return a->k == b->k; };
+    return s->cq.search(r, same_k, [s](cqs_sparse_req* const* batch, uint32_t nb) {
+        std::lock_guard<std::mutex> dev(s->mu);            // the device, for the batch alone
+        int32_t rc = CQS_HIP_OK;
+        const uint32_t k = batch[0]->k;
+        std::vector<uint32_t> counts;
+        std::vector<uint64_t> chunks;
+        std::vector<float> scores;
+        try {
+            std::vector<uint64_t> q_off(nb + 1, 0);
+            for (uint32_t i = 0; i < nb; ++i) q_off[i + 1] = q_off[i] + batch[i]->n_terms;
+            std::vector<uint32_t> toks((size_t)q_off[nb]);
+            std::vector<float> wts((size_t)q_off[nb]);
+            for (uint32_t i = 0; i < nb; ++i) {
+                if (batch[i]->n_terms == 0) continue;
+                memcpy(toks.data() + q_off[i], batch[i]->q_tokens, (size_t)batch[i]->n_terms * 4);
+                memcpy(wts.data() + q_off[i], batch[i]->q_weights, (size_t)batch[i]->n_terms * 4);
+            }
+            counts.assign(nb, 0u);
+            chunks.resize((size_t)nb * k);
+            scores.resize((size_t)nb * k);
+            rc = search_locked(s, q_off.data(), toks.data(), wts.data(), nb, k, nullptr, chunks.data(), scores.data(), counts.data());
+        } catch (const std::bad_alloc&) {
+            rc = sfail(s, CQS_HIP_ERR_NOMEM, "sparse search: out of host memory");
+        } catch (...) {
+            rc = sfail(s, CQS_HIP_ERR_INVALID, "sparse search: unexpected C++ exception");
         }
-    }
-    return r.rc;
+        s->stat_passes.fetch_add(1, std::memory_order_relaxed);
+        s->stat_queries.fetch_add(nb, std::memory_order_relaxed);
+        if (rc == CQS_HIP_OK)
+            for (uint32_t i = 0; i < nb; ++i) {
+                memcpy(batch[i]->out_chunks, chunks.data() + (size_t)i * k, (size_t)counts[i] * 8);
+                memcpy(batch[i]->out_scores, scores.data() + (size_t)i * k, (size_t)counts[i] * 4);
+                *batch[i]->out_count = counts[i];
+            }
+        return cqs_combine::Outcome{rc, s->poisoned.load(std::memory_order_acquire)};
+    });
 }
 
 }  // namespace
@@ -1078,37 +1009,17 @@ int32_t cqs_hip_sparse_index_last_search(const cqs_hip_sparse_index* s, float* a
     return CQS_HIP_OK;
 } CQS_ABI_CATCH_VAL(CQS_HIP_ERR_INVALID)
 
-// Diagnostic (not in the header): n_threads native threads, each calling the public single-query entry point per_thread
-// times over its own residue class of the query set (query q's terms: [q_off[q], q_off[q + 1])); results land in the
-// query's own output slot.  Returns the wall time in seconds, < 0 on a failed call.  What bench.py's Python threads cannot
+// Diagnostic (not in the header): combine_queue.h's client storm over the public single-query entry point (query q's
+// terms: [q_off[q], q_off[q + 1])); results land in the query's own output slot.  Returns the wall time in seconds, < 0 on a failed call.  What bench.py's Python threads cannot
 // show behind the interpreter lock.
 double cqs_hip_debug_sparse_client_storm(cqs_hip_sparse_index* s, const uint64_t* q_off, const uint32_t* q_tokens, const float* q_weights,
                                          uint32_t n_queries, uint32_t k, uint32_t n_threads, uint32_t per_thread,
                                          uint64_t* out_chunks, float* out_scores, uint32_t* out_counts) CQS_ABI_TRY {
     if (!s || !q_off || !q_tokens || !q_weights || !n_queries || !n_threads || !out_chunks || !out_scores || !out_counts) return -1.0;
-    std::atomic<int32_t> bad{0};
-    std::atomic<uint32_t> ready{0};
-    std::atomic<bool> go{false};
-    std::vector<std::thread> th;
-    th.reserve(n_threads);
-    for (uint32_t t = 0; t < n_threads; ++t)
-        th.emplace_back([&, t]() {
-            ready.fetch_add(1);
-            while (!go.load(std::memory_order_acquire)) std::this_thread::yield();
-            uint32_t qi = t % n_queries;
-            for (uint32_t i = 0; i < per_thread; ++i) {
-                const int32_t rc = cqs_hip_sparse_index_search(s, q_tokens + q_off[qi], q_weights + q_off[qi], (uint32_t)(q_off[qi + 1] - q_off[qi]),
-                                                               k, nullptr, out_chunks + (size_t)qi * k, out_scores + (size_t)qi * k, out_counts + qi);
-                if (rc != CQS_HIP_OK) { bad.store(rc); break; }
-                qi = (qi + n_threads) % n_queries;
-            }
-        });
-    while (ready.load() < n_threads) std::this_thread::yield();
-    const auto t0 = std::chrono::steady_clock::now();
-    go.store(true, std::memory_order_release);
-    for (std::thread& t : th) t.join();
-    const double el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
-    return bad.load() ? -1.0 : el;
+    return cqs_combine::client_storm(n_threads, per_thread, n_queries, [=](uint32_t qi) {
+        return cqs_hip_sparse_index_search(s, q_tokens + q_off[qi], q_weights + q_off[qi], (uint32_t)(q_off[qi + 1] - q_off[qi]), k, nullptr,
+                                           out_chunks + (size_t)qi * k, out_scores + (size_t)qi * k, out_counts + qi);
+    });
 } CQS_ABI_CATCH_VAL(-1.0)
 
 }  // extern "C"

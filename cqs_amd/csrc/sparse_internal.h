@@ -5,14 +5,12 @@
 #include <hip/hip_runtime.h>
 
 #include <atomic>
-#include <chrono>
-#include <condition_variable>
-#include <deque>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/cqs_hip.h"
+#include "combine_queue.h"
 #include "sparse_geometry.h"
 
 namespace cqs {
@@ -46,15 +44,9 @@ struct cqs_sparse_req {
 
 struct cqs_hip_sparse_index {
     std::mutex mu;
-    // combining queue (as the dense index's, index.hip): concurrent unfiltered single-query calls share launches
-    std::mutex cmu;
-    std::condition_variable ccv;
-    std::deque<cqs_sparse_req*> pending;
-    bool leader = false;
+    // combining queue (combine_queue.h): concurrent unfiltered single-query calls share launches; cq.wait_us is CQS_HIP_COMBINE_WAIT_US
+    cqs_combine::Queue<cqs_sparse_req, cqs::kSparseMaxBatch> cq;
     bool combine = true;                     // CQS_HIP_COMBINE=0 turns it off (read at create)
-    uint32_t combine_wait_us = 100;          // CQS_HIP_COMBINE_WAIT_US
-    std::chrono::steady_clock::time_point last_pass_end{};   // guarded by cmu
-    uint32_t expect = 1;                     // like-parameter callers recent passes saw
     std::atomic<uint64_t> stat_passes{0}, stat_queries{0};
     std::string last_error;
     std::atomic<bool> poisoned{false};
