@@ -75,8 +75,12 @@ SIGNATURES = [
     ("cqs_hip_index_search_tagged", C.c_int32,
      [_c_idx, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float,
       C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("cqs_hip_index_search_tagged_multi", C.c_int32,
+     [_c_idx, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_float,
+      C.c_void_p, C.c_void_p, C.c_void_p]),
     ("cqs_hip_index_combine_stats", None, [_c_idx, _pp(C.c_uint64), _pp(C.c_uint64)]),
     ("cqs_hip_index_combine_filter_stats", None, [_c_idx, _pp(C.c_uint64), _pp(C.c_uint64)]),
+    ("cqs_hip_index_combine_tagged_stats", None, [_c_idx, _pp(C.c_uint64), _pp(C.c_uint64)]),
     ("cqs_hip_index_set_bf16_scan", C.c_int32, [_c_idx, C.c_int32]),
     ("cqs_hip_index_bf16_stats", None, [_c_idx, _pp(C.c_uint64), _pp(C.c_uint64), _pp(C.c_uint64)]),
     ("cqs_hip_index_i8_stats", None, [_c_idx, _pp(C.c_uint64), _pp(C.c_uint64), _pp(C.c_uint64)]),
@@ -154,10 +158,13 @@ SIGNATURES = [
     ("cqs_hip_sparse_index_last_error", C.c_size_t, [_c_idx, C.c_char_p, C.c_size_t]),
 ]
 
-# Test hooks the library exports beside the header's symbols (embedder.hip, index_remove.hip, index_tags.hip; not part of
+# Test hooks the library exports beside the header's symbols (embedder.hip, index_remove.hip, index_tags.hip, index_combine.hip; not part of
 # include/cqs_hip.h).
 DEBUG_SIGNATURES = [
     ("cqs_hip_debug_index_tag_keep", C.c_int32, [_c_idx, C.c_void_p, C.c_void_p]),
+    ("cqs_hip_debug_index_tag_keep_multi", C.c_int32, [_c_idx, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p]),
+    ("cqs_hip_debug_client_storm_tagged", C.c_double,
+     [_c_idx, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("cqs_hip_debug_index_remove_budget", None, [_c_idx, C.c_uint64]),
     ("cqs_hip_debug_embedder_query_state", C.c_int32,
      [_c_idx, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _pp(C.c_int32)]),

@@ -223,6 +223,7 @@ bool ensure_keep_tab(cqs_hip_index* x) {
 void read_combine_env(cqs_hip_index* x) {                                              // read once per handle
     if (const char* ce = getenv("CQS_HIP_COMBINE")) x->combine = ce[0] != '0';
     if (const char* cf = getenv("CQS_HIP_COMBINE_FILTERED")) x->combine_filtered = cf[0] != '0';
+    if (const char* ct = getenv("CQS_HIP_COMBINE_TAGGED")) x->combine_tagged = ct[0] != '0';
     x->cq.wait_us = cqs_combine::wait_us_from_env();
     if (const char* cb = getenv("CQS_HIP_COMBINE_BITS")) x->combine_relaxed = cb[0] == 'r';
 }
@@ -550,8 +551,8 @@ static int32_t host_block(cqs_hip_index* x, const cqs_combine_req* const* qs, ui
 // One staged block to its answers: through the shadow copies first when shadow_takes the block (blocks that run as gemv
 // passes; the matrix-core blocks keep their path, their scores are not the gemv kernel's), then the f32 scan over the
 // queries the certificate did not cover - same call, same slots.  `staged` is left in an unspecified state.
-static int32_t answer_block(cqs_hip_index* x, std::vector<const cqs_combine_req*>& staged, uint8_t* slots, uint32_t k,
-                            const uint32_t* d_keep, uint32_t mode, float thr, bool gemv_only) {
+int32_t answer_block(cqs_hip_index* x, std::vector<const cqs_combine_req*>& staged, uint8_t* slots, uint32_t k,
+                     const uint32_t* d_keep, uint32_t mode, float thr, bool gemv_only) {
     int32_t rc;
     if (shadow_takes(x, (uint32_t)staged.size(), k, gemv_only)) {
         std::vector<const cqs_combine_req*> redo;
@@ -716,6 +717,12 @@ void cqs_hip_index_combine_stats(const cqs_hip_index* x, uint64_t* passes, uint6
 void cqs_hip_index_combine_filter_stats(const cqs_hip_index* x, uint64_t* passes, uint64_t* queries) CQS_ABI_TRY {
     if (passes) *passes = x ? x->stat_fpasses.load(std::memory_order_relaxed) : 0;
     if (queries) *queries = x ? x->stat_fqueries.load(std::memory_order_relaxed) : 0;
+} CQS_ABI_CATCH_VOID
+
+// The same counters for the blocks of callers with a tag filter (cqs_hip_index_search_tagged_multi does not count).
+void cqs_hip_index_combine_tagged_stats(const cqs_hip_index* x, uint64_t* passes, uint64_t* queries) CQS_ABI_TRY {
+    if (passes) *passes = x ? x->stat_tpasses.load(std::memory_order_relaxed) : 0;
+    if (queries) *queries = x ? x->stat_tqueries.load(std::memory_order_relaxed) : 0;
 } CQS_ABI_CATCH_VOID
 
 // `b` queries, each with its own keep-bitset: per query the bytes of cqs_hip_index_search(…, 1, …, that bitset, …).

@@ -33,6 +33,7 @@ struct cqs_combine_req {
     int32_t rc = 0;
     bool done = false;
     const uint32_t* keep = nullptr;   // nullable host keep-bitset of this query, ceil(len/32) words (filtered blocks)
+    const uint32_t* allow = nullptr;  // nullable tag filter of this query, 32 host words (tagged blocks; never beside keep)
 };
 
 struct cqs_hip_index {
@@ -104,6 +105,8 @@ struct cqs_hip_index {
     bool combine_filtered = true;         // CQS_HIP_COMBINE_FILTERED=0: single-query callers with a bitset take the serial path
     std::atomic<uint64_t> stat_passes{0}, stat_queries{0};   // combined passes run / queries they carried (unfiltered callers)
     std::atomic<uint64_t> stat_fpasses{0}, stat_fqueries{0}; // the same for the blocks of callers with a bitset
+    bool combine_tagged = true;           // CQS_HIP_COMBINE_TAGGED=0: single-query callers with a tag filter take the serial path
+    std::atomic<uint64_t> stat_tpasses{0}, stat_tqueries{0}; // the same for the blocks of callers with a tag filter
     std::atomic<int32_t> inject_fail{0};  // test hook (cqs_hip_debug_index_fail_next): the next host search (or remove) fails as a device error
     uint64_t remove_budget_rows = 0;      // test hook (cqs_hip_debug_index_remove_budget): rows per pass of remove; 0 = the bounce buffer's byte budget
 
@@ -123,6 +126,12 @@ struct cqs_hip_index {
     uint64_t tagged = 0;
     uint32_t* d_tag_count = nullptr;      // the kept rows of the last tags_keep_kernel launch, one partial count per workgroup
     uint32_t* h_tag_count = nullptr;      // (kTagMaxBlocks words), and the pinned block they are read back into
+    // tags_keep_multi_kernel (§3.14a): the transposed filters of a block (4 KB, staged pinned, copied on the stream) and
+    // the partial counts [kTagMultiMaxBlocks][32] with their pinned twin.  Made by the first block of tagged queries.
+    uint32_t* d_tag_tbl = nullptr;
+    uint32_t* h_tag_tbl = nullptr;
+    uint32_t* d_tag_mcount = nullptr;
+    uint32_t* h_tag_mcount = nullptr;
 };
 
 namespace cqs_idx {
@@ -206,6 +215,11 @@ int32_t injected_failure(cqs_hip_index* x);
 // ceil(n/32) words; null: every row).  Caller holds mu, has set the device and ordered x->stream after the last search.
 int32_t search_blocks_locked(cqs_hip_index* x, const cqs_combine_req* qs, uint32_t b, uint32_t k_eff, const uint32_t* d_keep,
                              uint32_t mode, float threshold, bool gemv_only);
+// One staged block to its answers (index.hip): queries staged[i] in h_q row i, through the shadow copies where they take
+// the block, then the f32 scan for the rest.  slots (with a null d_keep): query i is filtered by row slots[i] of the handle's
+// bitset table.  Caller holds mu; x->stream is ordered after the last search; ensure_scratch covers the block.
+int32_t answer_block(cqs_hip_index* x, std::vector<const cqs_combine_req*>& staged, uint8_t* slots, uint32_t k,
+                     const uint32_t* d_keep, uint32_t mode, float thr, bool gemv_only);
 // Row tags (index_tags.hip).  Caller holds mu (or owns the handle).
 void tags_free(cqs_hip_index* x);
 // After extend regrew the corpus: the column regrown to cap_rows with its contents.  No memory for it: the tags are dropped
@@ -216,6 +230,13 @@ void tags_regrow(cqs_hip_index* x);
 int32_t search_host_locked(cqs_hip_index* x, const cqs_combine_req* qs, uint32_t b, uint32_t k, const uint32_t* keep_bitset,
                            uint32_t mode, float threshold, bool gemv_only);
 int32_t search_filtered_locked(cqs_hip_index* x, const cqs_combine_req* qs, uint32_t b, uint32_t k, uint32_t mode, float threshold);
+// The tagged twin of search_filtered_locked (index_tags.hip): `b` queries with one (k, mode, threshold) and a tag filter
+// EACH (qs[i].allow), every one answered with the bytes of cqs_hip_index_search_tagged(that query, 1, ..., that filter).
+// Caller holds mu, has passed tagged_ready, checked the arguments and zeroed the counts.
+int32_t search_tagged_locked(cqs_hip_index* x, const cqs_combine_req* qs, uint32_t b, uint32_t k, uint32_t mode, float threshold);
+// The checks every tagged call makes before anything else, under mu: OK = a single-device handle, not poisoned, whose
+// every row has a tag.  None of the refusals poisons; the reason goes to last_error as "<who>: ...".
+int32_t tagged_ready(cqs_hip_index* x, const uint32_t* allow, const char* who);
 // Park one single-query request on the combining queue and return its answer (index_combine.hip).
 int32_t combine_search(cqs_hip_index* x, cqs_combine_req& r);
 

@@ -1,8 +1,9 @@
 // tags_host.h — the device-free part of the row tags: the per-row rule that tags_keep_kernel computes,
 // the all-pass test, the range rules of set_tags, the keep rule over a kept-row COUNT (plan_keep's twin for a bitset that
-// only exists on the device) and where the tagged prefix ends after a removal.  Plain C++ over the caller's arrays, no HIP,
-// no handle: index_tags.hip, index_remove.hip and the sparse index call it under their mutexes, the kernel calls tag_kept,
-// tests/tags_host_driver.cpp runs all of it under ASAN + UBSan on the CPU.
+// only exists on the device), where the tagged prefix ends after a removal, and the transposed table of up to 32 filters
+// with the verdict word tags_keep_multi_kernel looks up in it (§3.14a).  Plain C++ over the caller's arrays, no HIP,
+// no handle: index_tags.hip, index_remove.hip and the sparse index call it under their mutexes, the kernels call tag_kept
+// and tag_verdicts, tests/tags_host_driver.cpp and tests/tags_multi_host_driver.cpp run all of it under ASAN + UBSan on the CPU.
 #pragma once
 #include <algorithm>
 #include <cstddef>
@@ -82,6 +83,33 @@ inline uint64_t tagged_after_remove(const Id* removed, size_t count, uint64_t ta
     const size_t below = (size_t)(std::lower_bound(removed, removed + count, tagged,
                                                    [](const Id& r, uint64_t t) { return (uint64_t)r < t; }) - removed);
     return tagged - below;
+}
+
+// ---- up to 32 filters at once (tags_keep_multi_kernel) ----------------------------------------------
+constexpr uint32_t kMaxFilters = 32;                // filters per table = bits of a verdict word (= cqs_idx::kCombineCap)
+constexpr uint32_t kTableWords = kFields * 256;     // tbl[field][value]: 4 KB
+
+// The filters transposed: bit j of tbl[256 fld + v] is set iff filter j (the 32 words at allows + 32 j) allows value v in
+// field fld; bits >= f are zero.  1 <= f <= kMaxFilters.  Per (field, word of the sets) one 32 x 32 bit-matrix transpose
+// (row j = filter j's word, zero from f on): five masked swap rounds instead of 32 K single-bit moves.
+inline void transpose_filters(const uint32_t* allows, uint32_t f, uint32_t* tbl) {
+    for (uint32_t w = 0; w < kAllowWords; ++w) {            // w = 8 fld + v / 32, and tbl's index is 32 w + v % 32
+        uint32_t a[32];
+        for (uint32_t j = 0; j < 32; ++j) a[j] = j < f ? allows[(size_t)kAllowWords * j + w] : 0u;
+        uint32_t m = 0x0000FFFFu;
+        for (uint32_t s = 16; s != 0; s >>= 1, m ^= m << s)
+            for (uint32_t r = 0; r < 32; r = (r + s + 1) & ~s) {
+                const uint32_t t = ((a[r] >> s) ^ a[r + s]) & m;     // swap (rows r.., columns +s) with (rows r + s.., columns +0)
+                a[r] ^= t << s;
+                a[r + s] ^= t;
+            }
+        for (uint32_t v = 0; v < 32; ++v) tbl[32u * w + v] = a[v];
+    }
+}
+
+// A row's verdicts under all the filters of a table: bit j = tag_kept(tag, filter j).  Four lookups, however many filters.
+CQS_TAGS_HD inline uint32_t tag_verdicts(uint32_t tag, const uint32_t* tbl) {
+    return tbl[tag & 255u] & tbl[256u + ((tag >> 8) & 255u)] & tbl[512u + ((tag >> 16) & 255u)] & tbl[768u + (tag >> 24)];
 }
 
 // The bitset tags_keep_kernel writes for n rows, on the host: ceil(n / 32) words, bits past n are 0.  Returns the kept rows.

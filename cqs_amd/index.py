@@ -488,6 +488,26 @@ class HipIndex(VectorIndex):
             raise HipError(rc, self.last_error())
         return rows[:, :k], scores[:, :k], counts
 
+    def search_tagged_multi(self, queries: np.ndarray, k: int, allows, mode: int = _lib.MODE_RAW, threshold: float = 0.0):
+        """Block of queries with a tag filter EACH (`allows` u32 [b, 32], rows of `tag_filter(...)`) through
+        `cqs_hip_index_search_tagged_multi`: per query the answer of `search_tagged_batch(q, k, its filter)`, the block's
+        bitsets written by one kernel.  Returns (rows u64 [b,k], scores f32 [b,k], counts u32 [b])."""
+        q = np.ascontiguousarray(queries, dtype=np.float32)
+        if q.ndim == 1:
+            q = q[None, :]
+        b, qd = q.shape
+        a = np.ascontiguousarray(allows, dtype=np.uint32).reshape(-1, 32)
+        if a.shape[0] != b:
+            raise ValueError("allows must be [b, 32] uint32 words (tag_filter per query)")
+        rows = np.zeros((b, max(k, 1)), dtype=np.uint64)
+        scores = np.zeros((b, max(k, 1)), dtype=np.float32)
+        counts = np.zeros((b,), dtype=np.uint32)
+        rc = self._lib.cqs_hip_index_search_tagged_multi(self._h, _ptr(q), b, qd, k, _ptr(a), mode, threshold,
+                                                         _ptr(rows), _ptr(scores), _ptr(counts))
+        if rc != _lib.OK:
+            raise HipError(rc, self.last_error())
+        return rows[:, :k], scores[:, :k], counts
+
     def search_tagged(self, query: np.ndarray, k: int, allow) -> List[IndexResult]:
         """`search_with_filter` for a predicate over the rows' tags: no loop over the ids, no bitset.  Like `search`, never
         raises for device trouble (logs + []); that includes tags that do not cover the index."""
@@ -700,6 +720,12 @@ class HipIndex(VectorIndex):
         """(passes, queries) of the combining queue's blocks of callers with a bitset (`cqs_hip_index_combine_filter_stats`)."""
         p, q = C.c_uint64(), C.c_uint64()
         self._lib.cqs_hip_index_combine_filter_stats(self._h, C.byref(p), C.byref(q))
+        return int(p.value), int(q.value)
+
+    def combine_tagged_stats(self) -> Tuple[int, int]:
+        """(passes, queries) of the combining queue's blocks of callers with a tag filter (`cqs_hip_index_combine_tagged_stats`)."""
+        p, q = C.c_uint64(), C.c_uint64()
+        self._lib.cqs_hip_index_combine_tagged_stats(self._h, C.byref(p), C.byref(q))
         return int(p.value), int(q.value)
 
     def set_bf16_scan(self, enable: bool) -> None:

@@ -332,13 +332,35 @@ uint64_t cqs_hip_index_tagged_rows(const cqs_hip_index* idx);
  * that keeps nothing gives counts 0, k is capped at the kept rows, and the bf16 / int8 shadow is used where that call
  * would use it.  A filter of 32 all-ones words costs no device work and runs cqs_hip_index_search with a NULL bitset;
  * any other runs one small kernel on the handle's stream and waits for its exact kept-row count before the scan.
- * Concurrency: the call holds the handle's mutex throughout, like a filtered search with b > 1; tagged callers are NOT
- * combined by the queue (all-pass ones are, being unfiltered searches).
+ * Concurrency: a call with b == 1 whose filter constrains something parks on the handle's combining queue, like a call
+ * of cqs_hip_index_search with a keep_bitset: concurrent tagged callers with the same (k, mode, threshold) share passes
+ * over the corpus in blocks of up to 32, each under its own filter (the block's bitsets are written by one kernel, see
+ * search_tagged_multi), and each gets the bytes of its lone call.  Tagged callers form blocks of their own: they never
+ * share one with unfiltered callers or callers with a keep_bitset (all-pass tagged calls ARE unfiltered searches and
+ * combine as such).  If extend added rows without tags between parking and the pass, every caller of the block gets the
+ * "tags cover X of N rows" refusal.  CQS_HIP_COMBINE=0 or CQS_HIP_COMBINE_TAGGED=0 (read at create) keeps tagged callers
+ * off the queue; a call with b > 1 holds the handle's mutex throughout, like a filtered search with b > 1.
  * count_tagged: *out_kept = the rows `allow` keeps - the same kernel and count, no search (same checks). */
 int32_t  cqs_hip_index_count_tagged(cqs_hip_index* idx, const uint32_t* allow, uint64_t* out_kept);
 int32_t  cqs_hip_index_search_tagged(cqs_hip_index* idx, const float* queries, uint32_t b, uint32_t query_dim,
                                      uint32_t k, const uint32_t* allow, uint32_t mode, float threshold,
                                      uint64_t* out_rows, float* out_scores, uint32_t* out_counts);
+
+/* search_tagged_multi: `b` queries with a tag filter EACH, allows [b * 32] (query i: the 32 words at allows + 32 i).  Per
+ * query the result is exactly the bytes of
+ *   cqs_hip_index_search_tagged(idx, queries + i*dim, 1, dim, k, allows + 32*i, mode, threshold, ...)
+ * with every rule of that call per query: an all-pass filter is the unfiltered answer, a filter that keeps nothing gives
+ * count 0, fewer kept rows than k returns them all, a non-finite query gives count 0 without disturbing its neighbours, a
+ * dimension mismatch gives counts 0 and CQS_HIP_OK, k > max_k or a bad mode is CQS_HIP_ERR_INVALID.  The tag-specific
+ * refusals of search_tagged come first (NULL allows; a row-sharded handle, not built; tagged_rows < len), each
+ * CQS_HIP_ERR_INVALID without poisoning and with the reason in last_error.  The queries run in blocks of up to 32: one
+ * kernel reads each row's tag once and writes the block's bitsets into the handle's bitset table (one small wait for
+ * their exact counts), then the block runs as the blocks of cqs_hip_index_search_filtered run, through the bf16 / int8
+ * shadow like those.  Holds the handle's mutex throughout; moves no combine counter.  out_rows / out_scores [b * k],
+ * out_counts [b]. */
+int32_t  cqs_hip_index_search_tagged_multi(cqs_hip_index* idx, const float* queries, uint32_t b, uint32_t query_dim,
+                                           uint32_t k, const uint32_t* allows, uint32_t mode, float threshold,
+                                           uint64_t* out_rows, float* out_scores, uint32_t* out_counts);
 
 /* Combining-queue counters of a handle since it was made: passes the queue ran and the
  * queries they carried (queries / passes = mean callers per pass), unfiltered callers only.
@@ -346,6 +368,8 @@ int32_t  cqs_hip_index_search_tagged(cqs_hip_index* idx, const float* queries, u
 void cqs_hip_index_combine_stats(const cqs_hip_index* idx, uint64_t* passes, uint64_t* queries);
 /* The same two counters for the blocks of callers with a keep_bitset. */
 void cqs_hip_index_combine_filter_stats(const cqs_hip_index* idx, uint64_t* passes, uint64_t* queries);
+/* ... and for the blocks of single-query callers of cqs_hip_index_search_tagged. */
+void cqs_hip_index_combine_tagged_stats(const cqs_hip_index* idx, uint64_t* passes, uint64_t* queries);
 
 /* ---- bf16 shadow scan --------------------------------------------------------
  * Build (enable != 0) or free (enable == 0) a bf16 copy of the corpus that searches scan first.

@@ -118,6 +118,20 @@ extern "C" {
         out_counts: *mut u32,
     ) -> i32;
     fn cqs_hip_index_combine_filter_stats(idx: *const CqsHipIndex, passes: *mut u64, queries: *mut u64);
+    fn cqs_hip_index_combine_tagged_stats(idx: *const CqsHipIndex, passes: *mut u64, queries: *mut u64);
+    fn cqs_hip_index_search_tagged_multi(
+        idx: *mut CqsHipIndex,
+        queries: *const f32,
+        b: u32,
+        query_dim: u32,
+        k: u32,
+        allows: *const u32,
+        mode: u32,
+        threshold: f32,
+        out_rows: *mut u64,
+        out_scores: *mut f32,
+        out_counts: *mut u32,
+    ) -> i32;
     // row tags (include/cqs_hip.h, "row tags"): one u32 per row beside the corpus, filtered search without a host bitset
     fn cqs_hip_index_set_tags(idx: *mut CqsHipIndex, first_row: u64, tags: *const u32, m: u64) -> i32;
     fn cqs_hip_index_tagged_rows(idx: *const CqsHipIndex) -> u64;
@@ -583,6 +597,13 @@ impl HipIndex {
     pub fn combine_filter_stats(&self) -> (u64, u64) {
         let (mut p, mut q) = (0u64, 0u64);
         unsafe { cqs_hip_index_combine_filter_stats(self.handle, &mut p, &mut q) };
+        (p, q)
+    }
+
+    /// The same for the combined blocks of `search_with_tags` callers (their `b = 1` tagged calls park on the queue).
+    pub fn combine_tagged_stats(&self) -> (u64, u64) {
+        let (mut p, mut q) = (0u64, 0u64);
+        unsafe { cqs_hip_index_combine_tagged_stats(self.handle, &mut p, &mut q) };
         (p, q)
     }
 
