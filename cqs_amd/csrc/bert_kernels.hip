@@ -13,36 +13,7 @@
 
 namespace cqs {
 
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-
 namespace {
-
-// cross-lane-group reductions of the attention's softmax by v_permlane{16,32}_swap (VALU) instead of ds_bpermute
-// (LDS queue): lanes l, l^16, l^32, l^48 hold the same query's other keys
-__device__ __forceinline__ float xg_max(float v) {
-    typedef unsigned pu2 __attribute__((ext_vector_type(2)));
-    const pu2 a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-    const pu2 b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(b[0]), __uint_as_float(b[1]));
-}
-__device__ __forceinline__ float xg_sum(float v) {
-    typedef unsigned pu2 __attribute__((ext_vector_type(2)));
-    const pu2 a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    v = __uint_as_float(a[0]) + __uint_as_float(a[1]);
-    const pu2 b = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
-}
-
-__device__ __forceinline__ float wave_sum64(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 constexpr int kMaxChunks = 8;   // hidden <= 1024
 
@@ -60,7 +31,7 @@ __device__ __forceinline__ void ln_row_store(float (&v)[kMaxChunks][VEC], int nc
 #pragma unroll
             for (int e = 0; e < VEC; ++e) s += v[i][e];
         }
-    const float mean = wave_sum64(s) / (float)H;
+    const float mean = wave_sum64_shfl(s) / (float)H;
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < kMaxChunks; ++i)
@@ -68,7 +39,7 @@ __device__ __forceinline__ void ln_row_store(float (&v)[kMaxChunks][VEC], int nc
 #pragma unroll
             for (int e = 0; e < VEC; ++e) { const float a = v[i][e] - mean; q += a * a; }
         }
-    const float inv = rsqrtf(wave_sum64(q) / (float)H + eps);
+    const float inv = rsqrtf(wave_sum64_shfl(q) / (float)H + eps);
     typedef __bf16 bfv __attribute__((ext_vector_type(VEC)));
 #pragma unroll
     for (int i = 0; i < kMaxChunks; ++i)
@@ -181,13 +152,13 @@ __global__ __launch_bounds__(256) void bert_add_ln2_kernel(const bf16_t* __restr
         for (int i = 0; i < NC; ++i)
 #pragma unroll
             for (int e = 0; e < VEC; ++e) sm += v[t][i][e];
-        const float mean = wave_sum64(sm) / (float)H;
+        const float mean = wave_sum64_shfl(sm) / (float)H;
         float q = 0.f;
 #pragma unroll
         for (int i = 0; i < NC; ++i)
 #pragma unroll
             for (int e = 0; e < VEC; ++e) { const float d = v[t][i][e] - mean; q += d * d; }
-        const float inv = rsqrtf(wave_sum64(q) / (float)H + eps);
+        const float inv = rsqrtf(wave_sum64_shfl(q) / (float)H + eps);
         if (t == 1 && !two) break;
         bf16_t* o = out + (size_t)(t ? m1 : m0) * H;
 #pragma unroll
@@ -202,7 +173,7 @@ __global__ __launch_bounds__(256) void bert_add_ln2_kernel(const bf16_t* __restr
 
 // ---- multi-head attention, head dim HD = 32 or 64, bidirectional over one packed sequence -----------------------
 // One workgroup = 4 waves = 64 consecutive queries of ONE head of one sequence, 16 queries per wave.  Same product
-// layout as attention_dma_kernel (embed_kernels.hip): S^T = K Q^T with keys on MFMA rows (softmax is lane-local), the
+// layout as attention_dma_kernel (embed_attention.hip): S^T = K Q^T with keys on MFMA rows (softmax is lane-local), the
 // S^T tile (t, kt) takes its key rows in the order 32 t + 8 (i >> 2) + 4 kt + (i & 3) so that a lane group's P values
 // are the 8 consecutive keys 8 lg .. 8 lg + 7 = the PV product's k-indices, and the V^T fragments come from the
 // ROW-major V tile by ds_read_b64_tr_b16 (lane 4 q + p of a 16-lane group addresses key 8 lg + 4 h + q, dims
@@ -302,7 +273,7 @@ __global__ __launch_bounds__(256) void bert_attention_kernel(const bf16_t* __res
             for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) mloc = fmaxf(mloc, sc[kt][r]);
-            mloc = xg_max(mloc);
+            mloc = xor32_max(xor16_max(mloc));
             const float m_new = fmaxf(m_run, mloc);    // finite: key k_first < L is attendable for every query
             const float a = __builtin_amdgcn_exp2f((m_run - m_new) * c);     // exp2(-inf) = 0 on the first half
             l_run *= a;
@@ -330,7 +301,7 @@ __global__ __launch_bounds__(256) void bert_attention_kernel(const bf16_t* __res
             }
         }
     }
-    l_run = xg_sum(l_run);
+    l_run = xor32_sum(xor16_sum(l_run));
     if (wave_live && qi < L) {
         const float invl = l_run > 0.f ? 1.0f / l_run : 0.f;
         bf16_t* op = out + (size_t)(s0 + qi) * H + head * HD;
@@ -521,7 +492,7 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void bert_attention_res_k
                 for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) mloc = fmaxf(mloc, sc[t][kt][r]);
-            mloc = xg_max(mloc);
+            mloc = xor32_max(xor16_max(mloc));
             const float m_new = fmaxf(m_run, mloc);               // finite: key kfirst < L is attendable for every query
             const float a = __builtin_amdgcn_exp2f((m_run - m_new) * c);      // exp2(-inf) = 0 on the first group
             ls *= a;
@@ -588,15 +559,14 @@ __global__ __launch_bounds__(64 * NW, NW == 8 ? 2 : 1) void bert_attention_res_k
             // register of a tile pair (d, d + 1) turns them into 16 contiguous bytes per lane (lane groups 0 / 2 keep
             // tile d's dims 8 lg' .. + 7, groups 1 / 3 tile d + 1's), so a store instruction writes 64 contiguous bytes
             // of each of its 16 rows instead of 32
-            typedef unsigned pu2 __attribute__((ext_vector_type(2)));
 #pragma unroll
             for (int d = 0; d < kDT; d += 2) {
                 bf4 w0, w1;
 #pragma unroll
                 for (int e = 0; e < 4; ++e) { w0[e] = (bf16_t)(o[d][e] * invl); w1[e] = (bf16_t)(o[d + 1][e] * invl); }
-                const pu2 a = __builtin_bit_cast(pu2, w0), b2 = __builtin_bit_cast(pu2, w1);
-                const pu2 x = __builtin_amdgcn_permlane16_swap(a[0], b2[0], false, false);
-                const pu2 y = __builtin_amdgcn_permlane16_swap(a[1], b2[1], false, false);
+                const u2 a = __builtin_bit_cast(u2, w0), b2 = __builtin_bit_cast(u2, w1);
+                const u2 x = __builtin_amdgcn_permlane16_swap(a[0], b2[0], false, false);
+                const u2 y = __builtin_amdgcn_permlane16_swap(a[1], b2[1], false, false);
                 // even lane groups: (own tile d, the next group's tile d); odd: (the previous group's tile d + 1, own)
                 u4 v;
                 v[0] = x[0]; v[1] = y[0]; v[2] = x[1]; v[3] = y[1];

@@ -1,7 +1,7 @@
 // gemm_kernels.hip — bf16 GEMM for the embedding forward, second generation: C[M,N] = A[M,K] W[N,K]^T on
 // 256 x (64 TN) x 64 tiles, 8 waves (2 per SIMD, one workgroup per CU), v_mfma_f32_16x16x32_bf16.
 //
-// Why a second kernel (gemm_bf16_kernel in embed_kernels.hip stays for small / odd shapes and partly filled rounds):
+// Why a second kernel (gemm_bf16_kernel in embed_gemm.hip stays for small / odd shapes and partly filled rounds):
 // a 128 x 128 tile moves 32 KB of operands L2 -> LDS per 64-deep K-step for 512 MFMA cycles per SIMD - 64 B/clk/CU
 // against the ~56 B/clk/CU an XCD's L2 delivers - and re-reads the A panel once per 128 output columns (PMC, round 2:
 // 169 MB fetched by the GeGLU GEMM against 28 MB of operands).  A 256 x 256 tile needs half of both.
@@ -18,6 +18,7 @@
 // time, DMA alone the other half, nothing overlapped because every wave did the same thing at the same time);
 // ping-pong 1290-1360 TF.
 #include "embed_kernels.h"
+#include "activations.h"
 
 #include <utility>
 
@@ -26,24 +27,11 @@
 
 namespace cqs {
 
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
 constexpr int kP8M = 256;                 // tile rows
 constexpr int kARegion = 256 * 64;        // elements of the A tile per LDS buffer (32 KB)
 
-// erf GELU (BERT's hidden_act = "gelu"): 0.5 x (1 + erf(x / sqrt 2)), erf by Abramowitz-Stegun 7.1.26 (|error| <=
-// 1.5e-7: one exp + one rcp + a degree-5 polynomial; libm's erff costs 40 % of the whole 768 -> 3072 GEMM here)
-__device__ __forceinline__ float p8_gelu_erf(float x) {
-    const float z = __builtin_fabsf(x) * 0.70710678118654752f;
-    const float t = __frcp_rn(1.0f + 0.3275911f * z);
-    const float poly = ((((1.061405429f * t - 1.453152027f) * t + 1.421413741f) * t - 0.284496736f) * t + 0.254829592f) * t;
-    const float e = 1.0f - poly * __expf(-z * z);            // erf(|x| / sqrt 2)
-    return 0.5f * x * (1.0f + __builtin_copysignf(e, x));
-}
 // gelu_tanh(g) * u for two channels at once, in packed f32 arithmetic (v_pk_mul / v_pk_fma: two lanes' worth per instruction;
 // the epilogue holds no MFMAs for them to disturb): x sigmoid(2 k0 (x + k1 x^3)) = x / (1 + 2^(x (c0 + c1 x^2))),
 // c0 = -2 k0 log2(e), c1 = c0 k1: per pair 2 v_exp + 2 v_rcp + 6 packed operations.
@@ -61,7 +49,7 @@ __device__ __forceinline__ p8_f2 p8_geglu2(p8_f2 g, p8_f2 u) {
     r[1] = __builtin_amdgcn_rcpf(d[1]);
     return g * r * u;
 }
-// erf GELU for two values at once in packed f32 arithmetic (same polynomial and operation order per element as p8_gelu_erf)
+// erf GELU for two values at once in packed f32 arithmetic (same polynomial and operation order per element as gelu_erf, activations.h)
 __device__ __forceinline__ p8_f2 p8_gelu_erf2(p8_f2 x) {
     p8_f2 ax;
     ax[0] = __builtin_fabsf(x[0]); ax[1] = __builtin_fabsf(x[1]);
@@ -82,11 +70,6 @@ __device__ __forceinline__ p8_f2 p8_gelu_erf2(p8_f2 x) {
     se[0] = __builtin_copysignf(e[0], x[0]); se[1] = __builtin_copysignf(e[1], x[1]);
     return (p8_f2)(0.5f) * x * ((p8_f2)(1.0f) + se);
 }
-__device__ __forceinline__ float p8_gelu_tanh(float x) {
-    const float k0 = 0.7978845608028654f, k1 = 0.044715f;
-    const float u2 = 2.0f * k0 * (x + k1 * x * x * x);
-    return x * __frcp_rn(1.0f + __expf(-u2));
-}
 
 #define P8_WAIT_VM(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
 // the LDS reads a phase issued have long returned by its end; the explicit wait makes the refill of their slot
@@ -98,7 +81,7 @@ __device__ __forceinline__ float p8_gelu_tanh(float x) {
 #endif
 
 // LDS image of one buffer: [A: 256 rows][B: 64 TN rows], 128 B (64 bf16) per row, 16-B chunk c of row R stored at
-// chunk c ^ ((R >> 1) & 7) (conflict-free 16 x 32 fragment reads, see embed_kernels.hip swz()).  Row order:
+// chunk c ^ ((R >> 1) & 7) (conflict-free 16 x 32 fragment reads, see embed_gemm.hip swz()).  Row order:
 //   A region row R: piece h = R / 128, m-tile t = (R % 128) / 32, wave row wm = (R / 16) % 2, r = R % 16
 //                   -> tile row m = wm * 128 + (4 h + t) * 16 + r
 //   B region row R: n-tile t = R / 64 (tiles [0, TN0) = piece B0, the rest B1), wn = (R / 16) % 4, r = R % 16
@@ -367,7 +350,7 @@ __device__ __forceinline__ void gemm_pp_body(const bf16_t* __restrict__ A, const
         // The tile = [one whole q or k head: 256 columns | 64 columns of v] (weights in tile order, launch_permute_qkv_rows):
         // head tile t goes to qkv columns [256 t, + 256) after RMSNorm (1 + w), RoPE and (q heads) the attention scale, the
         // v slice to columns [256 (heads + kv) + 64 t, + 64) as it is.  Arithmetic = qk_norm_rope_block / load_q_fragments
-        // (embed_kernels.hip) on the bf16-rounded projection, so the attention kernels read what they used to compute.
+        // (embed_rows.hip / embed_attention.hip) on the bf16-rounded projection, so the attention kernels read what they used to compute.
         // Two passes of 128 rows through the bf16 stage; then wave w takes stage rows 16 w .. 16 w + 15 two at a time: lanes
         // 0-31 one row, lanes 32-63 the next; lane (l = lane & 31) owns dims 4 l + {0..3} and their rotation partners 128 + ...
         // TN = 4 (256-column tiles, the projection's rows in their natural order: partly filled rounds, M <~ 13k): a tile is
@@ -490,8 +473,6 @@ __device__ __forceinline__ void gemm_pp_body(const bf16_t* __restrict__ A, const
         constexpr int kStride = ON + 4;                             // elements
         constexpr int kCPR = ON / 4;                                // 8-byte chunks per row
         bf16_t* const stage = p8smem;                               // 128 x kStride elements <= 42 KiB
-        typedef unsigned pu2 __attribute__((ext_vector_type(2)));
-        typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
 #pragma unroll
         for (int p = 0; p < 2; ++p) {
 #pragma unroll
@@ -500,13 +481,13 @@ __device__ __forceinline__ void gemm_pp_body(const bf16_t* __restrict__ A, const
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
                     const f4 a = acc[4 * p + t][j];
-                    const pu2 s02 = __builtin_amdgcn_permlane16_swap(__float_as_uint(a[0]), __float_as_uint(a[2]), false, false);
-                    const pu2 s13 = __builtin_amdgcn_permlane16_swap(__float_as_uint(a[1]), __float_as_uint(a[3]), false, false);
+                    const u2 s02 = __builtin_amdgcn_permlane16_swap(__float_as_uint(a[0]), __float_as_uint(a[2]), false, false);
+                    const u2 s13 = __builtin_amdgcn_permlane16_swap(__float_as_uint(a[1]), __float_as_uint(a[3]), false, false);
                     p8_f2 gt, up;
                     gt[0] = __uint_as_float(s02[0]); gt[1] = __uint_as_float(s13[0]);                 // gate of channels c + 2 lg, + 1
                     up[0] = __uint_as_float(s02[1]); up[1] = __uint_as_float(s13[1]);
 #if defined(P8_GEGLU4_SCALAR_GELU)   // (round 2's formula, one channel at a time: bit-identical to the f32-stage epilogue)
-                    const p8_f2 res = {p8_gelu_tanh(gt[0]) * up[0], p8_gelu_tanh(gt[1]) * up[1]};
+                    const p8_f2 res = {gelu_tanh(gt[0]) * up[0], gelu_tanh(gt[1]) * up[1]};
 #else
                     const p8_f2 res = p8_geglu2(gt, up);
 #endif
@@ -593,7 +574,7 @@ __device__ __forceinline__ void gemm_pp_body(const bf16_t* __restrict__ A, const
                 const f4 gate = *(const f4*)src, up = *(const f4*)(src + 32);
                 bf4 o;
 #pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] = (bf16_t)(p8_gelu_tanh(gate[e]) * up[e]);
+                for (int e = 0; e < 4; ++e) o[e] = (bf16_t)(gelu_tanh(gate[e]) * up[e]);
 #ifdef P8_ABLATE_NOSTORE
                 if (acc[0][0][0] != 12345.678f) continue;
 #endif

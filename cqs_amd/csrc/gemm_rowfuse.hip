@@ -32,10 +32,6 @@
 
 namespace cqs {
 
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-
 namespace {
 
 constexpr int kRfRows = 64;                              // token rows per workgroup
@@ -45,12 +41,6 @@ constexpr int kRfWRing = 8 * 6 * kRfSlot;                // 8 waves x 6 private 
 constexpr int kRfATile = kRfRows * 128;                  // the shared A tile of one k-step: 8 KB, double-buffered
 constexpr int kRfLds = kRfWRing + 2 * kRfATile;          // 112 KB
 constexpr int kRfLdy = kRfH + 8;                         // epilogue row stride (elements): 64 x 776 x 2 B = 97 KB <= kRfLds
-
-__device__ __forceinline__ float rf_wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
 
 #define RF_WAIT_VM(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
 
@@ -80,7 +70,7 @@ __global__ __launch_bounds__(512, 2) void gemm_rowfuse_kernel(const bf16_t* __re
     const uint32_t nk = K / 64u;
 
     // ---- DMA sources.  One instruction = 8 LDS rows x 128 B: lane -> row (lane >> 3), physical chunk (lane & 7) ->
-    // logical chunk (lane & 7) ^ ((R >> 1) & 7), R = the row's index inside its 16-row group (embed_kernels.hip swz()).
+    // logical chunk (lane & 7) ^ ((R >> 1) & 7), R = the row's index inside its 16-row group (embed_gemm.hip swz()).
     const uint32_t r8 = (uint32_t)lane >> 3;
     const uint32_t pc = (uint32_t)lane & 7u;
     // W slot j, half hf (rows 8 hf + r8 of n-tile j): row 96 wid + 16 j + 8 hf + r8; the (j, hf, kt) parts are scalar
@@ -232,7 +222,7 @@ __global__ __launch_bounds__(512, 2) void gemm_rowfuse_kernel(const bf16_t* __re
 #pragma unroll
             for (int e = 0; e < 4; ++e) { yv[c][e] = (float)yb[e]; ss += yv[c][e] * yv[c][e]; }
         }
-        const float invy = rsqrtf(rf_wave_sum(ss) / (float)kRfH + eps);
+        const float invy = rsqrtf(wave_sum64_shfl(ss) / (float)kRfH + eps);
         float sx = 0.f;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
@@ -243,7 +233,7 @@ __global__ __launch_bounds__(512, 2) void gemm_rowfuse_kernel(const bf16_t* __re
             }
             *(f4*)(x + row * kRfH + c * 256 + lane * 4) = xv[i][c];
         }
-        const float invx = rsqrtf(rf_wave_sum(sx) / (float)kRfH + eps);
+        const float invx = rsqrtf(wave_sum64_shfl(sx) / (float)kRfH + eps);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             if (FINAL) {
@@ -280,7 +270,7 @@ __global__ __launch_bounds__(512, 2) void gemm_rowfuse_kernel(const bf16_t* __re
 //     k-step kt + 2 as soon as its fragments are in registers): ~10 KB per wave always in flight, no barrier;
 //   * A: the shared 128 x 64 tile of a k-step, THREE buffers, requested two k-steps ahead, one barrier per k-step;
 //   * every counted wait is vmcnt(14): between a DMA and its use the wave issues exactly 14 more (see kstep);
-//   * row sums half by half, left + right: the order add_norm_kernel uses too (embed_kernels.hip) -> same bits as the
+//   * row sums half by half, left + right: the order add_norm_kernel uses too (embed_rows.hip) -> same bits as the
 //     two-launch chain.
 constexpr int kR2Rows = 128;                              // token rows per workgroup pair
 constexpr int kR2Half = 384;                              // columns per workgroup
@@ -510,7 +500,6 @@ __global__ __launch_bounds__(512, 2) void gemm_rowfuse2_kernel(const bf16_t* __r
         }
         return theirs;
     };
-    auto half_sum = [&](float v) -> float { return half_wave_sum32(v); };   // over the 32 lanes of the half-wave (same bits in all of them)
 
     // phase 1: this half's sum of squares of every y row
     float mine1 = 0.f;
@@ -524,7 +513,7 @@ __global__ __launch_bounds__(512, 2) void gemm_rowfuse2_kernel(const bf16_t* __r
 #pragma unroll
             for (int e = 0; e < 4; ++e) { const float v = (float)yb[e]; ss += v * v; }
         }
-        ss = half_sum(ss);
+        ss = half_wave_sum32(ss);   // over the 32 lanes of the half-wave (same bits in all of them)
         mine1 = (l31 == i) ? ss : mine1;
     }
     const float theirs1 = exchange(0u, mine1);
@@ -547,7 +536,7 @@ __global__ __launch_bounds__(512, 2) void gemm_rowfuse2_kernel(const bf16_t* __r
             }
             if (r < rows_left) *(f4*)(x + (size_t)(m0 + r) * kRfH + cbase + c * 128) = xv[i][c];
         }
-        sx = half_sum(sx);
+        sx = half_wave_sum32(sx);
         mine2 = (l31 == i) ? sx : mine2;
     }
     const float theirs2 = exchange(1u, mine2);

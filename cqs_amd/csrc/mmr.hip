@@ -125,18 +125,15 @@ __device__ __forceinline__ uint64_t key_dpp(uint64_t k) {
 __device__ __forceinline__ uint64_t key_max(uint64_t a, uint64_t b) { return a > b ? a : b; }
 // cqs::wave_max64 for packed keys: the same four DPP steps and two lane swaps, both halves of the key moved alike.
 __device__ __forceinline__ uint64_t wave_max_key(uint64_t k) {
-    typedef unsigned u2 __attribute__((ext_vector_type(2)));
     k = key_max(k, key_dpp<0xB1>(k));
     k = key_max(k, key_dpp<0x4E>(k));
     k = key_max(k, key_dpp<0x141>(k));
     k = key_max(k, key_dpp<0x140>(k));
     {
-        const u2 lo = __builtin_amdgcn_permlane16_swap((uint32_t)k, (uint32_t)k, false, false);
-        const u2 hi = __builtin_amdgcn_permlane16_swap((uint32_t)(k >> 32), (uint32_t)(k >> 32), false, false);
+        const cqs::lane_u2 lo = cqs::swap16_self((uint32_t)k), hi = cqs::swap16_self((uint32_t)(k >> 32));
         k = key_max(((uint64_t)hi[0] << 32) | lo[0], ((uint64_t)hi[1] << 32) | lo[1]);
     }
-    const u2 lo = __builtin_amdgcn_permlane32_swap((uint32_t)k, (uint32_t)k, false, false);
-    const u2 hi = __builtin_amdgcn_permlane32_swap((uint32_t)(k >> 32), (uint32_t)(k >> 32), false, false);
+    const cqs::lane_u2 lo = cqs::swap32_self((uint32_t)k), hi = cqs::swap32_self((uint32_t)(k >> 32));
     return key_max(((uint64_t)hi[0] << 32) | lo[0], ((uint64_t)hi[1] << 32) | lo[1]);
 }
 

@@ -33,6 +33,7 @@
 // K order differs from the batch kernels (K split over a workgroup's waves) -> results agree with the batch path to bf16
 // rounding noise (cosine >= 0.9999, tests/test_query_path_gpu.py), not bit for bit.  Numbers: DESIGN.md 3.8.
 #include "embed_kernels.h"
+#include "activations.h"
 #include "launch_util.h"
 
 #include <cmath>
@@ -40,68 +41,16 @@
 
 namespace cqs {
 
-typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
-typedef float f4 __attribute__((ext_vector_type(4)));
-typedef unsigned qf_u2 __attribute__((ext_vector_type(2)));
-
 namespace {
 
 constexpr int kQfPad = 8;            // bf16 elements of row padding in the LDS activation tile
 
-template <int CTRL>
-__device__ __forceinline__ float qf_dpp(float v) {
-    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, false));
-}
-// sum over the wave: four DPP steps inside each 16-lane row (quad_perm xor 1, xor 2, row_half_mirror, row_mirror),
-// then the four row sums through v_readlane (uniform result; no LDS round trip as with ds_bpermute shuffles)
-__device__ __forceinline__ float qf_wave_sum(float v) {
-    v += qf_dpp<0xB1>(v);
-    v += qf_dpp<0x4E>(v);
-    v += qf_dpp<0x141>(v);
-    v += qf_dpp<0x140>(v);
-    const int b = __builtin_bit_cast(int, v);
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 0)) + __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 16)) +
-           __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 32)) + __builtin_bit_cast(float, __builtin_amdgcn_readlane(b, 48));
-}
-__device__ __forceinline__ float qf_xor32(float v, int lane) {       // the value of lane ^ 32
-    const qf_u2 a = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(lane < 32 ? a[1] : a[0]);
-}
-__device__ __forceinline__ float qf_xor16_max(float v) {
-    const qf_u2 a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-}
-__device__ __forceinline__ float qf_xor32_max(float v) {
-    const qf_u2 a = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return fmaxf(__uint_as_float(a[0]), __uint_as_float(a[1]));
-}
-__device__ __forceinline__ float qf_xor16_sum(float v) {
-    const qf_u2 a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(a[0]) + __uint_as_float(a[1]);
-}
-__device__ __forceinline__ float qf_xor32_sum(float v) {
-    const qf_u2 a = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
-    return __uint_as_float(a[0]) + __uint_as_float(a[1]);
-}
-__device__ __forceinline__ float qf_gelu_tanh(float x) {      // as gelu_tanh (embed_kernels.hip)
-    const float k0 = 0.7978845608028654f, k1 = 0.044715f;
-    const float u2 = 2.0f * k0 * (x + k1 * x * x * x);
-    return x * __frcp_rn(1.0f + __expf(-u2));
-}
-__device__ __forceinline__ float qf_gelu_erf(float x) {       // as gelu_erf (embed_kernels.hip): Abramowitz-Stegun 7.1.26
-    const float z = __builtin_fabsf(x) * 0.70710678118654752f;
-    const float t = __frcp_rn(1.0f + 0.3275911f * z);
-    const float poly = ((((1.061405429f * t - 1.453152027f) * t + 1.421413741f) * t - 0.284496736f) * t + 0.254829592f) * t;
-    const float e = 1.0f - poly * __expf(-z * z);
-    return 0.5f * x * (1.0f + __builtin_copysignf(e, x));
-}
 // bias + activation of the plain / staged kernels' epilogue (columns col .. col + 3)
 __device__ __forceinline__ f4 qf_bias_act(f4 v, const float* __restrict__ bias, int32_t act, uint32_t col) {
     if (bias) v += *(const f4*)(bias + col);
     if (act == 1) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = qf_gelu_erf(v[r]);
+        for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
     }
     return v;
 }
@@ -245,7 +194,6 @@ __global__ __launch_bounds__(256) void qf_gemm_staged_kernel(const QfGemmParams 
     constexpr int AR = ONE ? 1 : 16 * MT;
     float* const red = (float*)(sA + (size_t)AR * ldk);            // [4 waves][MT][64 lanes] f4
 
-    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
     const uint32_t rg = (uint32_t)tid >> 5, l32 = (uint32_t)tid & 31u;
     constexpr int AI = ONE ? 0 : 2 * MT;                           // activation row iterations of 8 rows
     u4 wreg[KC32], areg[AI > 0 ? AI : 1][KC32], oreg[ONE ? (KC32 + 7) / 8 : 1];
@@ -388,7 +336,6 @@ __global__ __launch_bounds__(64 * NW) void qf_gemm_kernel(const QfGemmParams p) 
     // fragment gather of 16 rows x 64 B costs ~44 clocks of address processing per instruction against ~16), lands while
     // the rows are normalised and goes through LDS: sW [NT][NC][LDA].
     static_assert(NC == 8 || NC == 16, "an 8- or 16-row weight slice per tile");
-    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
     // slice row i = NC tile + r (i < NT NC) is copied by the 32-thread group i % (2 NW), pass i / (2 NW)
     constexpr int WG32 = 2 * NW;                                   // 32-thread groups of the workgroup
     constexpr int WL = (NT * NC + WG32 - 1) / WG32;                // slice rows per group
@@ -438,13 +385,13 @@ __global__ __launch_bounds__(64 * NW) void qf_gemm_kernel(const QfGemmParams p) 
             for (int c = 0; c < NCH; ++c)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) sm += xv[c][i];
-            const float mean = qf_wave_sum(sm) / (float)H;
+            const float mean = wave_sum64_readlane(sm) / (float)H;
             float q = 0.f;
 #pragma unroll
             for (int c = 0; c < NCH; ++c)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) { const float a = xv[c][i] - mean; q += a * a; }
-            const float inv = rsqrtf(qf_wave_sum(q) / (float)H + p.eps);
+            const float inv = rsqrtf(wave_sum64_readlane(q) / (float)H + p.eps);
 #pragma unroll
             for (int c = 0; c < NCH; ++c) {
                 bf4 o;
@@ -461,7 +408,7 @@ __global__ __launch_bounds__(64 * NW) void qf_gemm_kernel(const QfGemmParams p) 
             for (int c = 0; c < NCH; ++c)
 #pragma unroll
                 for (int i = 0; i < 4; ++i) ss += yv[c][i] * yv[c][i];
-            const float invy = rsqrtf(qf_wave_sum(ss) / (float)H + p.eps);
+            const float invy = rsqrtf(wave_sum64_readlane(ss) / (float)H + p.eps);
 #pragma unroll
             for (int c = 0; c < NCH; ++c)
 #pragma unroll
@@ -472,7 +419,7 @@ __global__ __launch_bounds__(64 * NW) void qf_gemm_kernel(const QfGemmParams p) 
         for (int c = 0; c < NCH; ++c)
 #pragma unroll
             for (int i = 0; i < 4; ++i) sx += xv[c][i] * xv[c][i];
-        const float invx = rsqrtf(qf_wave_sum(sx) / (float)H + p.eps);
+        const float invx = rsqrtf(wave_sum64_readlane(sx) / (float)H + p.eps);
 #pragma unroll
         for (int c = 0; c < NCH; ++c) {
             if (PRO == QF_PRO_POOL) {
@@ -597,7 +544,7 @@ __global__ __launch_bounds__(64 * NW) void qf_gemm_kernel(const QfGemmParams p) 
     bf4 o;
     if (EPI == QF_EPI_GEGLU) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) o[r] = (bf16_t)(qf_gelu_tanh(v[0][r]) * v[NT - 1][r]);
+        for (int r = 0; r < 4; ++r) o[r] = (bf16_t)(gelu_tanh(v[0][r]) * v[NT - 1][r]);
     } else {
         if (PRO == QF_PRO_ADDLN) v[0] = qf_bias_act(v[0], p.bias, p.act, blockIdx.x * (uint32_t)NC + 4u * (uint32_t)lg);
 #pragma unroll
@@ -611,7 +558,7 @@ __global__ __launch_bounds__(64 * NW) void qf_gemm_kernel(const QfGemmParams p) 
 // Staging (one WAVE per token row; lane owns dims [4 lane, 4 lane + 4), rotate_half partner = lane ^ 32 - the arithmetic
 // of qk_norm_rope_block): per row the k head and the NH q heads are RMS-normalised, rotated (q also scaled) and written
 // to LDS as bf16 rows, V is written transposed.  S^T = K Q^T with keys on MFMA rows (softmax lane-local + two
-// cross-lane steps), O^T = V^T P^T with the S^T accumulators as the B operand (embed_kernels.hip's key permutation: lane
+// cross-lane steps), O^T = V^T P^T with the S^T accumulators as the B operand (embed_attention.hip's key permutation: lane
 // group g holds keys {4g..4g+3} of each 16-key tile, so the 8 slots of a 32-key step are keys {4g.., 16 + 4g..} and V^T
 // is read in that order).  Two users: qf_attention_kernel (one workgroup per q head; queries of 49-64 tokens) and
 // qf_attn_oproj_kernel (every o_proj workgroup redoes the attention of all heads in its own LDS: one launch and one
@@ -673,12 +620,12 @@ __device__ __forceinline__ void qf_attn_stage(const QfAttnParams& p, uint32_t h0
         float ss = 0.f;
 #pragma unroll
         for (int i = 0; i < 4; ++i) { x[i] = (float)in[i]; ss += x[i] * x[i]; }
-        const float inv = rsqrtf(qf_wave_sum(ss) / (float)kQfHD + p.eps);
+        const float inv = rsqrtf(wave_sum64_readlane(ss) / (float)kQfHD + p.eps);
         bf4 o;
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
             const float n = x[i] * inv * w1[i];
-            const float other = qf_xor32(n, lane);                    // rotate_half partner: dim +/- 128
+            const float other = xor32_value(n, lane);                    // rotate_half partner: dim +/- 128
             o[i] = (bf16_t)(((lane < 32) ? (n * c4[i] - other * s4[i]) : (n * c4[i] + other * s4[i])) * scale);
         }
         return o;
@@ -763,8 +710,8 @@ __device__ __forceinline__ float qf_attn_unit(const QfAttnParams& p, const bf16_
             sc[kt][r] = ok ? sc[kt][r] : -INFINITY;
             mx = fmaxf(mx, sc[kt][r]);
         }
-    mx = qf_xor16_max(mx);
-    mx = qf_xor32_max(mx);
+    mx = xor16_max(mx);
+    mx = xor32_max(mx);
     float sum = 0.f;
     constexpr int KT2 = 2 * ((MT + 1) / 2);
     bf4 pb[KT2];
@@ -776,8 +723,8 @@ __device__ __forceinline__ float qf_attn_unit(const QfAttnParams& p, const bf16_
             pb[kt][r] = (bf16_t)e;
             sum += (float)pb[kt][r];                                   // the rounded weights are what multiplies V
         }
-    sum = qf_xor16_sum(sum);
-    sum = qf_xor32_sum(sum);
+    sum = xor16_sum(sum);
+    sum = xor32_sum(sum);
 #pragma unroll
     for (int j = 0; j < NDT; ++j) o[j] = (f4)(0.f);
 #pragma unroll
@@ -865,7 +812,6 @@ __global__ __launch_bounds__(64 * NW) void qf_attn_oproj_kernel(const QfAttnPara
     static_assert(NC <= 2 * NW, "one slice row per 32-thread group");
     constexpr bool kStageW = MT < 3 || MTQ < MT;                     // (a block of the queries leaves LDS room at any key count)
     constexpr int LDW = K + 8;
-    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
     bf16_t* const sW = (bf16_t*)(red + NW * MTQ * 64 * 4);
     const uint32_t wg = (uint32_t)tid >> 5, wl32 = (uint32_t)tid & 31u;
     u4 wreg[NH];
@@ -967,7 +913,6 @@ __global__ __launch_bounds__(64 * NW) void qf_attn_oproj_long_kernel(const QfAtt
     QF_STAMP(p, 0);
     const uint32_t T = p.T, last = T - 1u;
     const uint32_t qrow0 = blockIdx.y * 16u;
-    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
     const uint32_t wg = (uint32_t)tid >> 5, wl32 = (uint32_t)tid & 31u;   // 16 groups of 32 threads: slice rows wg and wg + 16
     u4 wreg[2][NH];
 #pragma unroll
@@ -1064,7 +1009,7 @@ __global__ __launch_bounds__(64 * NW) void qf_attn_oproj_long_kernel(const QfAtt
                     sc[kt][r] = ok ? sc[kt][r] : -INFINITY;
                     mx = fmaxf(mx, sc[kt][r]);
                 }
-            mx = qf_xor32_max(qf_xor16_max(mx));
+            mx = xor32_max(xor16_max(mx));
             const float m_new = fmaxf(m_run, mx);
             const float mb = m_new == -INFINITY ? 0.f : m_new;        // no attendable key so far: every weight is exp(-inf) = 0
             if (half) {                                               // O and the row sum of the first half shrink by exp(m_old - m_new)
@@ -1103,7 +1048,7 @@ __global__ __launch_bounds__(64 * NW) void qf_attn_oproj_long_kernel(const QfAtt
     }
     QF_STAMP(p, 1);
     if (wid < NH) {                                                   // O / sum over the head's Q rows (this wave is their only reader)
-        const float sum = qf_xor32_sum(qf_xor16_sum(l_run));
+        const float sum = xor32_sum(xor16_sum(l_run));
         const float rinv = 1.0f / sum;                                // (a live query sees itself: sum > 0; rows past T are never stored)
         bf16_t* orow = sQ + ((size_t)wid * 16 + (uint32_t)l15) * kQfKRow + 4 * lg;
 #pragma unroll

@@ -5,8 +5,8 @@ set -e
 cd "$(dirname "$0")/.."
 if [ "$1" = build ]; then
   mkdir -p build/variants
-  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $3 -c cqs_amd/csrc/embed_kernels.hip -o build/variants/att_$2.o
-  objs=$(ls cqs_amd/csrc/build/*.o | grep -v -e embed_kernels.o -e amdgcn)
+  /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC $3 -c cqs_amd/csrc/embed_attention.hip -o build/variants/att_$2.o
+  objs=$(ls cqs_amd/csrc/build/*.o | grep -v -e embed_attention.o -e amdgcn)
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -o build/variants/lib_att_$2.so build/variants/att_$2.o $objs -ldl
   rm build/variants/att_$2.o
 else
