@@ -49,6 +49,7 @@ SIGNATURES = [
      [_c_idx, C.c_uint32, _pp(C.c_int32), _pp(C.c_uint64), _pp(C.c_uint64), _pp(C.c_int32)]),
     ("cqs_hip_index_extend", C.c_int32, [_c_idx, C.c_void_p, C.c_uint64]),
     ("cqs_hip_index_remove", C.c_int32, [_c_idx, C.c_void_p, C.c_uint64, _pp(C.c_uint64)]),
+    ("cqs_hip_index_update", C.c_int32, [_c_idx, C.c_void_p, C.c_void_p, C.c_uint64, _pp(C.c_uint64)]),
     ("cqs_hip_index_destroy", None, [_c_idx]),
     ("cqs_hip_index_save", C.c_int32, [_c_idx, C.c_char_p, _pp(C.c_uint64)]),
     ("cqs_hip_index_load", C.c_int32, [C.c_char_p, C.c_uint32, C.c_uint64, C.c_int32, C.c_uint64, _pp(_c_idx)]),
@@ -166,6 +167,7 @@ DEBUG_SIGNATURES = [
     ("cqs_hip_debug_client_storm_tagged", C.c_double,
      [_c_idx, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("cqs_hip_debug_index_remove_budget", None, [_c_idx, C.c_uint64]),
+    ("cqs_hip_debug_index_update_budget", None, [_c_idx, C.c_uint64]),
     ("cqs_hip_debug_embedder_query_state", C.c_int32,
      [_c_idx, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _pp(C.c_int32)]),
 ]

@@ -1,5 +1,5 @@
 // index_internal.h — the index handle and the host helpers shared by the index's translation units (index.hip,
-// index_persist.hip, index_combine.hip, index_shadow.hip, index_remove.hip, mmr.hip, sharded.hip).
+// index_persist.hip, index_combine.hip, index_shadow.hip, index_remove.hip, index_update.hip, mmr.hip, sharded.hip).
 // Internal to libcqs_hip.so (the public boundary is include/cqs_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -109,6 +109,13 @@ struct cqs_hip_index {
     std::atomic<uint64_t> stat_tpasses{0}, stat_tqueries{0}; // the same for the blocks of callers with a tag filter
     std::atomic<int32_t> inject_fail{0};  // test hook (cqs_hip_debug_index_fail_next): the next host search (or remove) fails as a device error
     uint64_t remove_budget_rows = 0;      // test hook (cqs_hip_debug_index_remove_budget): rows per pass of remove; 0 = the bounce buffer's byte budget
+    uint64_t update_budget_rows = 0;      // test hook (cqs_hip_debug_index_update_budget): rows per pass of update; 0 = the staging buffer's byte budget
+
+    // Staging of cqs_hip_index_update (index_update.hip; null until the first update): a pass's new rows and their
+    // destination list, pinned, and the device block they are copied into.  Kept between calls, freed at destroy.
+    void* upd_h = nullptr;
+    void* upd_d = nullptr;
+    uint64_t upd_bytes = 0;
 
     // bf16 shadow (index_shadow.hip; null = off).  Its certified / fallback counts outlive it: they live on the handle.
     cqs_idx::Shadow* shadow = nullptr;
@@ -193,6 +200,16 @@ void shadow_free(cqs_hip_index* x);
 // The shadow's per-row buffers, which remove compacts beside d_rows (index_remove.hip); null: that copy is off.
 struct ShadowBuffers { uint16_t* bf16; int8_t* i8; float* i8_scale; };
 ShadowBuffers shadow_buffers(const cqs_hip_index* x);
+// Around the launches of an update on a handle with the shadow on (index_update.hip), the stream idle: begin clears the
+// outlier word and hands out the stats words the two build bodies fold into (*stats8: the int8 copy's); end reads the
+// maxima back once and refreshes r / norm / r8 / norm8 as the build passes do.  An outlier row turns the shadow off as in
+// extend (the call still succeeds).
+int32_t shadow_update_begin(cqs_hip_index* x, unsigned long long** stats, unsigned long long** stats8);
+int32_t shadow_update_end(cqs_hip_index* x);
+// cqs_hip_index_update on one single-device index, planned (update_host.h): index_update.hip.  Caller holds x->mu.
+int32_t update_entries(cqs_hip_index* x, const uint32_t* local, uint64_t local_off, const uint64_t* order, uint64_t count,
+                       const float* vectors);
+void update_free(cqs_hip_index* x);
 bool shadow_takes(const cqs_hip_index* x, uint32_t b, uint32_t k, bool gemv_only);
 bool shadow_uses_i8(const cqs_hip_index* x, uint32_t b, uint32_t k);   // of a block shadow_takes: the int8 copy serves it
 int32_t shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k, const uint32_t* d_keep, uint32_t mode,
@@ -281,6 +298,8 @@ int32_t search_combined(cqs_hip_index* parent, cqs_combine_req* const* batch, ui
 int32_t neighbors(cqs_hip_index* parent, uint64_t target_row, uint32_t limit, uint64_t* out_rows, float* out_scores,
                   uint32_t* out_count);
 int32_t extend(cqs_hip_index* parent, const float* rows, uint64_t n_new);
+int32_t update(cqs_hip_index* parent, const uint64_t* rows, const float* vectors, uint64_t m, uint64_t* out_updated);
+void update_budget(cqs_hip_index* parent, uint64_t rows);   // (the test hook, handed to every shard; caller holds the parent's mutex)
 int32_t save(cqs_hip_index* parent, const char* path, uint64_t* out_checksum);
 uint64_t len(const cqs_hip_index* parent);
 int32_t poisoned(const cqs_hip_index* parent);

@@ -130,6 +130,40 @@ static int32_t i8_convert(cqs_hip_index* x, uint64_t row0) {
     return CQS_HIP_OK;
 }
 
+int32_t shadow_update_begin(cqs_hip_index* x, unsigned long long** stats, unsigned long long** stats8) {
+    Shadow* s = x->shadow;
+    HIP_TRY(x, hipMemsetAsync(s->d_stats + 2, 0, sizeof(unsigned long long), x->stream));
+    *stats = s->d_stats;
+    *stats8 = s->d_stats + kStatI8;
+    return CQS_HIP_OK;
+}
+
+// d_stats[0..2] and [kStatI8, +2) hold the maxima over every row ever converted (the build passes never clear them), the
+// rewritten rows' old contents among them: a superset of the rows now stored, so r / norm stay valid and at worst looser.
+int32_t shadow_update_end(cqs_hip_index* x) {
+    Shadow* s = x->shadow;
+    unsigned long long st[kStatI8 + 2];
+    HIP_TRY(x, hipMemcpyAsync(st, s->d_stats, sizeof st, hipMemcpyDeviceToHost, x->stream));
+    HIP_TRY(x, hipStreamSynchronize(x->stream));
+    if (st[2] != 0) {
+        shadow_free(x);
+        x->last_error = "update: a new row has a component of magnitude >= 2^64; bf16 shadow turned off";
+        return CQS_HIP_OK;
+    }
+    double v[4];
+    memcpy(&v[0], &st[0], sizeof(double));
+    memcpy(&v[1], &st[1], sizeof(double));
+    memcpy(&v[2], &st[kStatI8], sizeof(double));
+    memcpy(&v[3], &st[kStatI8 + 1], sizeof(double));
+    s->r = v[0] * (1.0 + 0x1p-30);   // (the slack of shadow_convert / i8_convert)
+    s->norm = v[1] * (1.0 + 0x1p-30);
+    if (s->d_i8) {
+        s->r8 = v[2] * (1.0 + 0x1p-30);
+        s->norm8 = v[3] * (1.0 + 0x1p-30);
+    }
+    return CQS_HIP_OK;
+}
+
 static uint64_t i8_bytes(uint64_t cap, uint32_t dim) { return cap * dim + cap * sizeof(float); }
 
 // Allocate and build the int8 copy over rows [0, n) beside a bf16 copy that is in place.  *built = false: no memory (freed again).

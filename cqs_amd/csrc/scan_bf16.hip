@@ -20,15 +20,12 @@
 #include "rank_sort.h"
 #include "scan_gemv_device.h"
 #include "select_device.h"
+#include "shadow_build_device.h"
 
 namespace cqs {
 
 static_assert(kShadowKMax == kMaxK, "shadow k' policy and the select agree on max k");
 
-typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ float bf_lo(uint32_t w) { return __uint_as_float(w << 16); }          // component 2i
-__device__ __forceinline__ float bf_hi(uint32_t w) { return __uint_as_float(w & 0xFFFF0000u); }  // component 2i + 1
 __device__ __forceinline__ float key_score(uint64_t key) {                                        // inverse of okey
     const uint32_t ok = (uint32_t)(key >> 32);
     return __uint_as_float((ok & 0x80000000u) ? (ok ^ 0x80000000u) : ~ok);
@@ -41,38 +38,7 @@ __global__ __launch_bounds__(256) void shadow_build_kernel(const float* __restri
     const int lane = threadIdx.x & 63;
     const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
     for (uint64_t r = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); r < n_rows; r += waves) {
-        const float* xp = rows + (row0 + r) * dim;
-        uint16_t* op = shadow + (row0 + r) * dim;
-        double d2 = 0.0, n2 = 0.0, t2 = 0.0;
-        bool fin = true, big = false;
-        for (uint32_t i = (uint32_t)lane * 2u; i < dim; i += 128u) {   // dim % 8 == 0: pairs never straddle the row end
-            const f2 v = *(const f2*)(xp + i);
-            const bf2 h = __builtin_convertvector(v, bf2);
-            const uint32_t w = __builtin_bit_cast(uint32_t, h);
-            *(uint32_t*)(op + i) = w;
-            const float t0 = bf_lo(w), t1 = bf_hi(w);
-            fin = fin && __builtin_isfinite(v.x) && __builtin_isfinite(v.y);
-            big = big || __builtin_fabsf(v.x) >= 0x1p64f || __builtin_fabsf(v.y) >= 0x1p64f;
-            const double e0 = (double)v.x - (double)t0, e1 = (double)v.y - (double)t1;   // exact in f64
-            d2 += e0 * e0 + e1 * e1;
-            n2 += (double)v.x * (double)v.x + (double)v.y * (double)v.y;
-            t2 += (double)t0 * (double)t0 + (double)t1 * (double)t1;
-        }
-#pragma unroll
-        for (int m = 32; m >= 1; m >>= 1) {
-            d2 += __shfl_xor(d2, m, 64);
-            n2 += __shfl_xor(n2, m, 64);
-            t2 += __shfl_xor(t2, m, 64);
-        }
-        const bool all_fin = __ballot(!fin) == 0ull;
-        const bool any_big = __ballot(big) != 0ull;
-        if (lane == 0 && all_fin) {   // rows with a non-finite component score non-finite in both paths: no part in R
-            const double nx = sqrt(n2), nt = sqrt(t2);
-            const double rb = sqrt(d2) + gamma * (nx + nt);
-            atomicMax(&stats[0], (unsigned long long)__double_as_longlong(rb));
-            atomicMax(&stats[1], (unsigned long long)__double_as_longlong(nx > nt ? nx : nt));
-            if (any_big) atomicMax(&stats[2], 1ull);
-        }
+        shadow_build_row(rows + (row0 + r) * dim, shadow + (row0 + r) * dim, dim, gamma, stats, lane);
     }
 }
 

@@ -10,6 +10,7 @@
 #include "scan_i8.h"
 #include "launch_util.h"
 #include "scan_gemv_device.h"
+#include "shadow_build_device.h"
 
 namespace cqs {
 
@@ -18,67 +19,13 @@ template <int I>
 __device__ __forceinline__ float code_f32(uint32_t w) { return (float)(int)(int8_t)(w >> (8 * I)); }
 
 // ---- build ------------------------------------------------------------------------------------------------------
-constexpr int kI8BuildVecs = (int)(kShadowMaxDim / 256u);   // f4 per lane that hold a row of up to kShadowMaxDim
-
 __global__ __launch_bounds__(256) void i8_build_kernel(const float* __restrict__ rows, int8_t* __restrict__ codes,
                                                        float* __restrict__ scales, uint64_t row0, uint64_t n_rows,
                                                        uint32_t dim, double gamma, unsigned long long* __restrict__ stats) {
     const uint32_t lane = threadIdx.x & 63u;
     const uint64_t waves = (uint64_t)gridDim.x * (blockDim.x >> 6);
     for (uint64_t r = (uint64_t)blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6); r < n_rows; r += waves) {
-        const float* xp = rows + (row0 + r) * dim;
-        int8_t* op = codes + (row0 + r) * dim;
-        f4 v[kI8BuildVecs];
-        float m = 0.f;
-        bool fin = true;
-#pragma unroll
-        for (int j = 0; j < kI8BuildVecs; ++j) {   // dim % 16 == 0: a lane's four floats never straddle the row end
-            const uint32_t i = (uint32_t)j * 256u + lane * 4u;
-            v[j] = i < dim ? *(const f4*)(xp + i) : (f4)(0.f);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                fin = fin && __builtin_isfinite(v[j][e]);
-                m = fmaxf(m, __builtin_fabsf(v[j][e]));   // (fmaxf drops a NaN operand; `fin` carries it)
-            }
-        }
-        m = wave_max64(m);
-        const bool all_fin = __ballot(!fin) == 0ull;
-        const float scale = all_fin ? m / 127.f : __builtin_nanf("");
-        const bool zero = !(scale > 0.f);   // (and the non-finite rows: their codes are 0, their scale NaN)
-        double d2 = 0.0, n2 = 0.0, t2 = 0.0;
-#pragma unroll
-        for (int j = 0; j < kI8BuildVecs; ++j) {
-            const uint32_t i = (uint32_t)j * 256u + lane * 4u;
-            if (i >= dim) continue;
-            uint32_t w = 0u;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float c = zero ? 0.f : __builtin_rintf(v[j][e] / scale);
-                c = c < -127.f ? -127.f : (c > 127.f ? 127.f : c);
-                w |= ((uint32_t)(int)c & 0xFFu) << (8 * e);
-                const double t = (double)scale * (double)c;   // x~: exact in f64 (24-bit scale, 7-bit code)
-                const double d = (double)v[j][e] - t;
-                d2 += d * d;
-                n2 += (double)v[j][e] * (double)v[j][e];
-                t2 += t * t;
-            }
-            *(uint32_t*)(op + i) = w;
-        }
-#pragma unroll
-        for (int s = 32; s >= 1; s >>= 1) {
-            d2 += __shfl_xor(d2, s, 64);
-            n2 += __shfl_xor(n2, s, 64);
-            t2 += __shfl_xor(t2, s, 64);
-        }
-        if (lane == 0u) {
-            scales[row0 + r] = scale;
-            if (all_fin) {   // rows with a non-finite component score non-finite in both paths: no part in R
-                const double nx = sqrt(n2), nt = sqrt(t2);
-                atomicMax(&stats[0], (unsigned long long)__double_as_longlong(sqrt(d2) + gamma * (nx + nt)));
-                atomicMax(&stats[1], (unsigned long long)__double_as_longlong(nx > nt ? nx : nt));
-                if (m >= 0x1p64f) atomicMax(&stats[2], 1ull);
-            }
-        }
+        i8_build_row(rows + (row0 + r) * dim, codes + (row0 + r) * dim, scales + row0 + r, dim, gamma, stats, lane);
     }
 }
 

@@ -27,6 +27,7 @@
 #include "index_internal.h"
 #include "mmr_host.h"
 #include "search_host.h"
+#include "update_host.h"
 
 using namespace cqs_idx;
 using cqs_search::popcount_bits;
@@ -597,6 +598,42 @@ int32_t extend(cqs_hip_index* p, const float* rows, uint64_t n_new) {
         ss->shard[s]->row_base = p->row_base + ss->lo[s];
     }
     return CQS_HIP_OK;
+}
+
+// Shard starts do not move under an update (what DESIGN.md §7 holds against remove here does not apply).  Every id is
+// checked against the whole handle before any shard is touched; the plan's order is ascending by row, so each shard's
+// entries are one range of it, and the shard (a single-device index with its own row_base) runs the same update.
+int32_t update(cqs_hip_index* p, const uint64_t* rows, const float* vectors, uint64_t m, uint64_t* out_updated) {
+    std::lock_guard<std::mutex> g(p->mu);
+    if (poisoned(p)) return CQS_HIP_ERR_POISONED;
+    std::vector<uint32_t> local;
+    std::vector<uint64_t> order;
+    const char* why = "";
+    const cqs_update::Plan plan = cqs_update::plan_update(rows, vectors, m, p->row_base, len(p), &local, &order, &why);
+    if (plan == cqs_update::Plan::Invalid) return pfail(p, CQS_HIP_ERR_INVALID, std::string("update: ") + why);
+    if (plan == cqs_update::Plan::Nothing) return CQS_HIP_OK;
+    ShardSet* ss = p->sh;
+    for (size_t s = 0; s < ss->shard.size(); ++s) {
+        cqs_hip_index* c = ss->shard[s];
+        size_t first = 0;
+        const size_t count = cqs_update::entries_in(local, order, ss->lo[s], ss->lo[s] + c->n, &first);
+        if (count == 0) continue;
+        int32_t rc;
+        {
+            std::lock_guard<std::mutex> gc(c->mu);
+            rc = update_entries(c, local.data(), ss->lo[s], order.data() + first, count, vectors);
+        }
+        if (rc != CQS_HIP_OK) return child_fail(p, s, rc);
+    }
+    if (out_updated) *out_updated = m;
+    return CQS_HIP_OK;
+}
+
+void update_budget(cqs_hip_index* p, uint64_t rows) {
+    for (cqs_hip_index* c : p->sh->shard) {
+        std::lock_guard<std::mutex> gc(c->mu);
+        c->update_budget_rows = rows;
+    }
 }
 
 int32_t save(cqs_hip_index* p, const char* path, uint64_t* out_checksum) {

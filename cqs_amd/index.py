@@ -289,6 +289,53 @@ class HipIndex(VectorIndex):
             self.__dict__.pop("_row_of", None)
         return removed
 
+    def update_rows(self, rows, vectors) -> int:
+        """`cqs_hip_index_update`: `vectors[i]` replaces the stored row `rows[i]` (global row ids, any order, each at most
+        once) where it lies, in the f32 corpus and in the shadow copies; nothing moves and nothing is renumbered.  Returns
+        the number of rows written.  Raises HipError (INVALID: an id the index does not hold, an id named twice, a
+        borrowed handle)."""
+        r = np.ascontiguousarray(rows, dtype=np.uint64).reshape(-1)
+        v = np.ascontiguousarray(vectors, dtype=np.float32)
+        if v.ndim != 2 or v.shape[0] != r.shape[0] or (v.shape[0] and v.shape[1] != self.dim()):
+            raise ValueError("vectors must be [len(rows), dim]")
+        updated = C.c_uint64()
+        rc = self._lib.cqs_hip_index_update(self._h, _ptr(r), _ptr(v), r.shape[0], C.byref(updated))
+        if rc != _lib.OK:
+            raise HipError(rc, self.last_error())
+        return int(updated.value)
+
+    def update(self, ids: Sequence[str], vectors) -> int:
+        """Write new embeddings back under ids the index already holds (`Store::update_embeddings_batch`,
+        src/store/chunks/crud.rs:349-480: the enrichment pass; `upsert_chunks_batch`'s conflict arm in the watch loop).
+        Ids the index does not hold are skipped, as the reference's UPDATE matches no row for them; an id named twice
+        raises ValueError, as its staging table's primary key refuses it.  Returns the number of rows written;
+        `id_map` is untouched."""
+        ids = list(ids)
+        v = np.ascontiguousarray(vectors, dtype=np.float32)
+        if v.ndim != 2 or v.shape[0] != len(ids) or v.shape[1] != self.dim():
+            raise ValueError("vectors must be [len(ids), dim]")
+        if len(set(ids)) != len(ids):
+            raise ValueError("update: an id is named twice")
+        base = int(self._lib.cqs_hip_index_row_base(self._h))
+        if self.id_map is None:
+            n = len(self)
+            held = []
+            for i, cid in enumerate(ids):
+                try:
+                    row = int(cid)
+                except ValueError:
+                    continue
+                if base <= row < base + n:
+                    held.append((i, row))
+            if len({row for _, row in held}) != len(held):
+                raise ValueError("update: an id is named twice")       # ("7" and "07")
+        else:
+            row_of = self._rows_by_id()
+            held = [(i, base + row_of[cid]) for i, cid in enumerate(ids) if cid in row_of]
+        if not held:
+            return 0
+        return self.update_rows([row for _, row in held], v[[i for i, _ in held]])
+
     # ---- persistence: blob + CagraMeta-style sidecar (src/cagra.rs:973-1157, 1174-1330) -----------
     META_MAGIC = "cqs-hip-flat-meta"
     META_VERSION = 1

@@ -130,6 +130,24 @@ int32_t cqs_hip_index_extend(cqs_hip_index* idx, const float* rows, uint64_t n_n
  * borrowing index (the rows are the caller's), a row-sharded handle.  Waits for the searches in flight, as extend does;
  * a device failure half-way leaves the rows half-moved and poisons the handle. */
 int32_t cqs_hip_index_remove(cqs_hip_index* idx, const uint64_t* rows, uint64_t m, uint64_t* out_removed);
+/* Rewrite stored rows of an owning index in place — what the reference's enrichment pass and its watch loop do to chunks
+ * that keep their id (Store::update_embeddings_batch, src/store/chunks/crud.rs:349-480; upsert_chunks_batch's ON
+ * CONFLICT(id) DO UPDATE, src/store/chunks/async_helpers.rs:314-330).  `rows` are `m` global row ids (row_base included,
+ * as remove and neighbors take them), in any order, each at most once; `vectors` is [m, dim] f32, host, row-major, and
+ * vectors[i] replaces stored row rows[i].  *out_updated (may be NULL) = m on success.  Afterwards len, row_base, the row
+ * numbering, the tag column, capacity and every scratch buffer are what they were, and in every other respect the index
+ * is indistinguishable from one created from the patched rows: searches return the same bytes, save writes the same
+ * blob, the bf16 / int8 shadow copies hold the bytes a fresh build holds.  The shadow's bounds take the new rows in and
+ * let nothing out (still valid, at worst looser, as after remove).  Rows are taken as extend takes them: none is skipped
+ * or checked for finiteness; a finite row with a component of magnitude >= 2^64 turns the shadow off (last_error says so)
+ * and the call still succeeds.  The new rows are staged through a buffer of at most 64 MiB, pinned and on the device,
+ * which the handle keeps until destroy; larger updates run in passes.  m == 0 changes nothing.  Supported on a
+ * row-sharded handle (shard starts do not move).  CQS_HIP_ERR_INVALID, with the index untouched, the handle not poisoned
+ * and the reason in last_error: an id outside [row_base, row_base + len), an id named twice, NULL rows or vectors with
+ * m > 0, a borrowing index (the rows are the caller's).  Waits for the searches in flight, as extend does; a device
+ * failure half-way leaves some rows written and poisons the handle. */
+int32_t cqs_hip_index_update(cqs_hip_index* idx, const uint64_t* rows, const float* vectors, uint64_t m,
+                             uint64_t* out_updated);
 /* Synchronises the index's streams, then frees everything (src/cagra.rs:289-302). */
 void cqs_hip_index_destroy(cqs_hip_index* idx);
 

@@ -75,6 +75,7 @@ extern "C" {
     fn cqs_hip_index_metric(idx: *const CqsHipIndex) -> u32;
     fn cqs_hip_index_extend(idx: *mut CqsHipIndex, rows: *const f32, n_new: u64) -> i32;
     fn cqs_hip_index_remove(idx: *mut CqsHipIndex, rows: *const u64, m: u64, out_removed: *mut u64) -> i32;
+    fn cqs_hip_index_update(idx: *mut CqsHipIndex, rows: *const u64, vectors: *const f32, m: u64, out_updated: *mut u64) -> i32;
     // persistence (the index.cagra + .meta analogue, src/cagra.rs:973-1157, 1174-1330): the blob is written /
     // validated by the library, the CagraMeta-style sidecar (magic, version, dim, chunk_count, id_map,
     // checksum, metric) by `HipIndex::save` / `HipIndex::load` below via serde_json like src/cagra.rs:1128-1147
@@ -446,6 +447,50 @@ impl HipIndex {
         });
         self.row_of = std::sync::OnceLock::new();
         Ok(removed as usize)
+    }
+
+    /// Write re-embedded chunks back under the ids the index already holds (`Store::update_embeddings_batch`,
+    /// src/store/chunks/crud.rs:349-480, after the enrichment pass; the conflict arm of `upsert_chunks_batch` in the watch
+    /// loop): the library rewrites the rows where they lie, shadow copies included; `id_map`, the row numbering and the
+    /// tags stay.  Ids the index does not hold are skipped, as the reference's UPDATE matches no row for them.  Returns
+    /// the number of rows written; an id named twice or a misshapen embedding is an error and writes nothing.
+    pub fn update_embeddings(&mut self, updates: &[(String, Embedding)]) -> Result<usize, String> {
+        let row_of = self.row_of.get_or_init(|| {
+            let mut m = std::collections::HashMap::with_capacity(self.id_map.len());
+            for (i, id) in self.id_map.iter().enumerate() {
+                m.entry(id.clone()).or_insert(i as u64);
+            }
+            m
+        });
+        let mut seen: std::collections::HashSet<&str> = std::collections::HashSet::with_capacity(updates.len());
+        let mut rows: Vec<u64> = Vec::new();
+        let mut flat: Vec<f32> = Vec::new();
+        for (id, embedding) in updates {
+            if !seen.insert(id.as_str()) {
+                return Err(format!("HIP update: id {id} named twice"));
+            }
+            let v = embedding.as_slice();
+            if v.len() != self.dim {
+                return Err(format!("HIP update: dimension mismatch: expected {}, got {}", self.dim, v.len()));
+            }
+            // (handles made here have row_base 0: global row ids are `id_map` positions)
+            if let Some(row) = row_of.get(id.as_str()) {
+                rows.push(*row);
+                flat.extend_from_slice(v);
+            }
+        }
+        if rows.is_empty() {
+            return Ok(0);
+        }
+        let mut updated: u64 = 0;
+        let rc = unsafe { cqs_hip_index_update(self.handle, rows.as_ptr(), flat.as_ptr(), rows.len() as u64, &mut updated) };
+        if rc != CQS_HIP_OK {
+            if unsafe { cqs_hip_index_poisoned(self.handle) } != 0 {
+                self.poisoned.store(true, Ordering::Release);
+            }
+            return Err(self.last_error());
+        }
+        Ok(updated as usize)
     }
 
     /// `CagraIndex::save` (src/cagra.rs:1086-1157): the library streams the rows HBM -> `<path>.tmp` -> fsync -> `.bak`
