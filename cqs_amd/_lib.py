@@ -26,6 +26,7 @@ MODE_RAW = 0
 MODE_PIPELINE = 1
 MAX_K = 1024
 NEIGHBORS_MAX = 100
+KNN_MAX_TARGETS = 65536
 MMR_MAX = 1024
 
 _c_idx = C.c_void_p
@@ -86,6 +87,8 @@ SIGNATURES = [
     ("cqs_hip_index_bf16_stats", None, [_c_idx, _pp(C.c_uint64), _pp(C.c_uint64), _pp(C.c_uint64)]),
     ("cqs_hip_index_i8_stats", None, [_c_idx, _pp(C.c_uint64), _pp(C.c_uint64), _pp(C.c_uint64)]),
     ("cqs_hip_index_neighbors", C.c_int32, [_c_idx, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, _pp(C.c_uint32)]),
+    ("cqs_hip_index_knn_graph", C.c_int32,
+     [_c_idx, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("cqs_hip_index_pairwise", C.c_int32, [_c_idx, C.c_void_p, C.c_uint32, C.c_void_p]),
     ("cqs_hip_index_mmr", C.c_int32,
      [_c_idx, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, _pp(C.c_uint32)]),

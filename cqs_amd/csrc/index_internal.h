@@ -1,5 +1,6 @@
 // index_internal.h — the index handle and the host helpers shared by the index's translation units (index.hip,
-// index_persist.hip, index_combine.hip, index_shadow.hip, index_remove.hip, index_update.hip, mmr.hip, sharded.hip).
+// index_persist.hip, index_combine.hip, index_shadow.hip, index_remove.hip, index_update.hip, index_knn.hip, mmr.hip,
+// sharded.hip).
 // Internal to libcqs_hip.so (the public boundary is include/cqs_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -117,6 +118,12 @@ struct cqs_hip_index {
     void* upd_d = nullptr;
     uint64_t upd_bytes = 0;
 
+    // Staging of cqs_hip_index_knn_graph (index_knn.hip; null until the first such call): a call's rows, scores and counts
+    // in one block on the device and its pinned twin.  Kept between calls, freed at destroy.
+    void* knn_h = nullptr;
+    void* knn_d = nullptr;
+    size_t knn_bytes = 0;
+
     // bf16 shadow (index_shadow.hip; null = off).  Its certified / fallback counts outlive it: they live on the handle.
     cqs_idx::Shadow* shadow = nullptr;
     std::atomic<uint64_t> stat_certified{0}, stat_fallbacks{0};
@@ -210,6 +217,7 @@ int32_t shadow_update_end(cqs_hip_index* x);
 int32_t update_entries(cqs_hip_index* x, const uint32_t* local, uint64_t local_off, const uint64_t* order, uint64_t count,
                        const float* vectors);
 void update_free(cqs_hip_index* x);
+void knn_free(cqs_hip_index* x);   // the staging of cqs_hip_index_knn_graph (index_knn.hip)
 bool shadow_takes(const cqs_hip_index* x, uint32_t b, uint32_t k, bool gemv_only);
 bool shadow_uses_i8(const cqs_hip_index* x, uint32_t b, uint32_t k);   // of a block shadow_takes: the int8 copy serves it
 int32_t shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k, const uint32_t* d_keep, uint32_t mode,

@@ -686,6 +686,39 @@ class HipIndex(VectorIndex):
         rows, scores = self.neighbors_rows(row, limit)
         return [IndexResult(self._id(int(r)), float(s)) for r, s in zip(rows, scores)]
 
+    def knn_graph_rows(self, limit: int, first: int = 0, count: Optional[int] = None, rows_per_call: int = 4096):
+        """`cqs_hip_index_knn_graph`: the neighbours of the `count` stored rows from the index's `first`-th on (default: to
+        the end), each as `neighbors_rows` defines them.  Returns (rows u64 [count, L] global row ids, scores f32
+        [count, L], counts u32 [count]) with L = clamp(limit, 1, 100); slots past a count are 0.  The range goes to the
+        library in calls of `rows_per_call` targets cut at multiples of 256 rows - whole tiles, so no tile is scanned
+        twice - and the answer does not depend on the cut; searches from other threads get the handle between calls."""
+        n = len(self)
+        first = int(first)
+        count = n - first if count is None else int(count)
+        if first < 0 or count < 0 or first + count > n:
+            raise ValueError("knn_graph_rows: range not in this index")
+        lim = max(1, min(int(limit), _lib.NEIGHBORS_MAX))
+        per = max(256, min(int(rows_per_call), _lib.KNN_MAX_TARGETS)) // 256 * 256
+        rows = np.zeros((count, lim), dtype=np.uint64)
+        scores = np.zeros((count, lim), dtype=np.float32)
+        counts = np.zeros((count,), dtype=np.uint32)
+        base = int(self._lib.cqs_hip_index_row_base(self._h))
+        at = first
+        while at < first + count:
+            stop = min(first + count, (at // per + 1) * per)
+            o = at - first
+            rc = self._lib.cqs_hip_index_knn_graph(self._h, base + at, stop - at, lim, _ptr(rows[o:]), _ptr(scores[o:]), _ptr(counts[o:]))
+            if rc != _lib.OK:
+                raise HipError(rc, self.last_error())
+            at = stop
+        return rows, scores, counts
+
+    def knn_graph(self, limit: int) -> List[List[IndexResult]]:
+        """The exact kNN graph of the index by chunk id: entry i is `find_neighbors(id of row i, limit)`."""
+        rows, scores, counts = self.knn_graph_rows(limit)
+        return [[IndexResult(self._id(int(rows[i, j])), float(scores[i, j])) for j in range(int(counts[i]))]
+                for i in range(rows.shape[0])]
+
     # ---- cosine MMR over the resident rows (src/search/mmr.rs:59-126) ------------
     def pairwise_rows(self, rows) -> np.ndarray:
         """`cqs_hip_index_pairwise`: the [m, m] f32 dots of the stored rows `rows` (global row ids)."""

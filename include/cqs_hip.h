@@ -255,6 +255,34 @@ int32_t cqs_hip_index_search_device(cqs_hip_index* idx, const float* d_queries, 
 int32_t cqs_hip_index_neighbors(cqs_hip_index* idx, uint64_t target_row, uint32_t limit, uint64_t* out_rows,
                                 float* out_scores, uint32_t* out_count);
 
+/* ---- exact kNN graph of the stored rows ----------------------------------------
+ * `find_neighbors` applied to each of the `m` stored rows first_row .. first_row + m - 1 (GLOBAL row ids) in one call:
+ * what `cqs index --umap` needs before anything else (umap-learn accepts a precomputed graph), near-duplicate detection,
+ * `neighbors` / `related` for a whole file's functions.  The rows are read where they lie in HBM; only the answer
+ * crosses the bus, once.
+ * Results: L = clamp(limit, 1, CQS_HIP_NEIGHBORS_MAX).  Target i owns out_rows[i*L .. i*L + out_counts[i]) and the same
+ * range of out_scores (each [m * L], host; out_counts [m]), ordered (score desc under the f32 total order, row asc), the
+ * target itself excluded, out_counts[i] <= min(L, len - 1).  Scores are raw dots (RAW mode); rows with a non-finite
+ * score are never emitted; slots past the count are written as 0.  An index of one row gives count 0.
+ * Tiles: T = min(256, the handle's largest query block) depends on len alone; local rows are cut into fixed tiles
+ * [T*t, min(T*t + T, len)), and the call runs every tile its range touches as ONE block of T queries - all rows of the
+ * tile - through the f32 scan and select every block of that size uses, at k1 = min(L + 1, len), then emits the targets
+ * that were asked for.  So a target's answer depends on the corpus and the target only, not on how the caller cuts the
+ * range into calls; it is byte for byte what cqs_hip_index_search returns for the block of its tile's rows at k1 with the
+ * target dropped; and where its tile has at most 8 rows (the ragged last one can) it is byte for byte
+ * cqs_hip_index_neighbors' answer.  Against the reference's find_neighbors: ids exact outside near-ties, scores to 1e-5.
+ * Refused with CQS_HIP_ERR_INVALID, the outputs untouched, the handle not poisoned and the reason in last_error, in this
+ * order: a NULL handle; a NULL output with m > 0; m > CQS_HIP_KNN_MAX_TARGETS; any part of the range outside the index;
+ * a row-sharded handle.  m == 0 returns CQS_HIP_OK and touches nothing.  A poisoned handle -> CQS_HIP_ERR_POISONED; a
+ * device failure poisons the handle.
+ * The call holds the handle for its whole length: searches on the same handle wait for it, so a daemon that serves
+ * queries meanwhile should pass a few tiles per call, not the corpus.  A first call grows the scratch to the 256-query
+ * block's (256 * padded rows * 4 bytes of scores, as any 256-query search does) and a staging block of m * (12 L + 4)
+ * bytes, pinned and on the device, which the handle keeps until destroy. */
+#define CQS_HIP_KNN_MAX_TARGETS 65536u
+int32_t cqs_hip_index_knn_graph(cqs_hip_index* idx, uint64_t first_row, uint64_t m, uint32_t limit,
+                                uint64_t* out_rows, float* out_scores, uint32_t* out_counts);
+
 /* ---- cosine MMR re-rank of a candidate pool ------------------------------------
  * The reference diversifies its top-K pool with `mmr_rerank` (src/search/mmr.rs:59-126) over a surface-feature
  * similarity, because it drops the embeddings after scoring: "embedding-MMR is a follow-up" (mmr.rs:30-37,

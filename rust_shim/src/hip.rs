@@ -68,6 +68,8 @@ extern "C" {
                                   n_devices: u32, row_base: u64, out: *mut *mut CqsHipIndex) -> i32;
     fn cqs_hip_index_neighbors(idx: *mut CqsHipIndex, target_row: u64, limit: u32, out_rows: *mut u64,
                                out_scores: *mut f32, out_count: *mut u32) -> i32;
+    fn cqs_hip_index_knn_graph(idx: *mut CqsHipIndex, first_row: u64, m: u64, limit: u32, out_rows: *mut u64,
+                               out_scores: *mut f32, out_counts: *mut u32) -> i32;
     // cosine MMR over the resident rows (src/search/mmr.rs:59-126 with the stored rows' dot as `similarity`)
     fn cqs_hip_index_pairwise(idx: *mut CqsHipIndex, cand_rows: *const u64, m: u32, out: *mut f32) -> i32;
     fn cqs_hip_index_mmr(idx: *mut CqsHipIndex, cand_rows: *const u64, cand_scores: *const f32, m: u32, limit: u32,
@@ -598,6 +600,38 @@ impl HipIndex {
         Some((0..count as usize)
             .filter_map(|i| self.id_map.get(rows[i] as usize).map(|id| IndexResult { id: id.to_string(), score: scores[i] }))
             .collect())
+    }
+
+    /// The exact kNN graph of the resident corpus: entry i is `find_neighbors` of `id_map[i]` - what `cqs index --umap`
+    /// hands umap-learn as its precomputed graph instead of streaming every embedding to it.  The rows go to the library
+    /// in calls of 4096 targets (whole tiles of 256), so searches on the same handle get their turn between calls.
+    /// `None` = the device failed or the handle is row-sharded: the caller keeps its CPU path.
+    pub fn knn_graph(&self, limit: usize) -> Option<Vec<Vec<IndexResult>>> {
+        let n = self.id_map.len();
+        let l = limit.clamp(1, 100);
+        let mut graph = Vec::with_capacity(n);
+        let (mut rows, mut scores, mut counts) = (vec![0u64; 4096 * l], vec![0f32; 4096 * l], vec![0u32; 4096]);
+        let mut first = 0usize;
+        while first < n {
+            let m = (n - first).min(4096);
+            let rc = unsafe {
+                cqs_hip_index_knn_graph(self.handle, first as u64, m as u64, l as u32, rows.as_mut_ptr(),
+                                        scores.as_mut_ptr(), counts.as_mut_ptr())
+            };
+            if rc != CQS_HIP_OK {
+                tracing::warn!(error = %self.last_error(), rc, "HIP kNN graph failed");
+                return None;
+            }
+            for i in 0..m {
+                graph.push((0..counts[i] as usize)
+                    .filter_map(|j| {
+                        self.id_map.get(rows[i * l + j] as usize).map(|id| IndexResult { id: id.to_string(), score: scores[i * l + j] })
+                    })
+                    .collect());
+            }
+            first += m;
+        }
+        Some(graph)
     }
 
     /// `mmr_rerank` (src/search/mmr.rs:59-126) over `(chunk id, relevance)` candidates of this index, in the caller's
