@@ -1,5 +1,5 @@
 // persist_util.h - file helpers shared by the two persisted forms (the dense index's `.hipflat` blob, index_persist.hip, and the
-// sparse index's blob, sparse_index.hip): the streaming content checksum, whole-buffer read / write, a durable rename.
+// sparse index's blob, sparse_file_host.h): the streaming content checksum, whole-buffer read / write, a durable rename.
 // Internal to libcqs_hip.so.
 #pragma once
 #include <cerrno>

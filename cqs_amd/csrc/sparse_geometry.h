@@ -1,7 +1,8 @@
 // sparse_geometry.h — everything the sparse index derives from its chunk count and its list lengths: the padded row, the
 // chunks a wave owns, the select's group size, and which lists get a range directory.  Plain C++, no HIP: the constructors
-// (sparse_index.hip, finish_create) and the in-place updates (sparse_index_update.hip) derive it with this one code, so an
-// updated handle has the geometry a fresh create of the same documents would have.
+// (sparse_index_create.hip, finish_create) and the in-place updates (sparse_index_update.hip) derive it with this one code,
+// so an updated handle has the geometry a fresh create of the same documents would have.  Also the constants and the
+// resolved query term that the host headers (sparse_build_host.h) share with the scoring kernel.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -12,6 +13,17 @@ namespace cqs {
 constexpr uint32_t kSparsePad = 1024;                  // n_pad granule (a multiple of every wave range)
 constexpr unsigned long long kNoDir = ~0ull;           // a list without a range directory: the wave bisects it
 constexpr uint64_t kSparseMaxChunks = 0xFFFFFFFFull - kSparsePad;   // create refuses n >= this
+constexpr uint32_t kUnscored = 0xFFFFFFFFu;    // LDS marker: `scores.entry(chunk)` does not exist yet (a NaN bit pattern: weights that
+                                               // carry it are refused at build / search, a sum that lands on it is stored as 0x7FC00000)
+constexpr uint32_t kMaxTerms = 1u << 16;        // per query
+constexpr uint32_t kSparseMaxBatch = 64;       // queries per cqs_hip_sparse_index_search_batch call
+
+struct SparseTerm {            // one query term, resolved on the host
+    unsigned long long start;  // first posting of the token's list
+    unsigned long long dir;    // first entry of the list's range directory (kNoDir: none - the wave bisects the list)
+    uint32_t len;              // postings in the list
+    float w;                   // query weight
+};
 
 struct SparseGeometry {
     uint32_t n_pad, rw, sh;

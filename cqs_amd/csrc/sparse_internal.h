@@ -1,33 +1,26 @@
-// sparse_internal.h — the sparse index handle and the host helpers shared by its translation units (sparse_index.hip:
-// constructors, persistence, search; sparse_index_update.hip: remove / extend in place).
+// sparse_internal.h — the sparse index handle and what crosses its translation units: sparse_index.hip (the scoring kernel
+// and the search), sparse_index_create.hip (constructors, destroy, accessors), sparse_index_persist.hip (save / load),
+// sparse_index_tags.hip (chunk tags), sparse_index_update.hip (remove / extend in place).
 // Internal to libcqs_hip.so (the public boundary is include/cqs_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <atomic>
+#include <cstddef>
+#include <functional>
 #include <mutex>
 #include <string>
 #include <vector>
 
 #include "../../include/cqs_hip.h"
 #include "combine_queue.h"
+#include "sparse_build_host.h"
 #include "sparse_geometry.h"
 
-namespace cqs {
-
-constexpr uint32_t kUnscored = 0xFFFFFFFFu;    // LDS marker: `scores.entry(chunk)` does not exist yet (a NaN bit pattern: weights that
-                                               // carry it are refused at build / search, a sum that lands on it is stored as 0x7FC00000)
-constexpr uint32_t kMaxTerms = 1u << 16;        // per query
-constexpr uint32_t kSparseMaxBatch = 64;       // queries per cqs_hip_sparse_index_search_batch call
-
-struct SparseTerm {            // one query term, resolved on the host
-    unsigned long long start;  // first posting of the token's list
-    unsigned long long dir;    // first entry of the list's range directory (kNoDir: none - the wave bisects the list)
-    uint32_t len;              // postings in the list
-    float w;                   // query weight
-};
-
-}  // namespace cqs
+// the host headers' posting is the device's uint2, member for member
+static_assert(sizeof(cqs_sparse_build::Posting) == sizeof(uint2) && alignof(cqs_sparse_build::Posting) == alignof(uint2) &&
+                  offsetof(cqs_sparse_build::Posting, x) == offsetof(uint2, x) && offsetof(cqs_sparse_build::Posting, y) == offsetof(uint2, y),
+              "cqs_sparse_build::Posting must have uint2's layout");
 
 // One single-query search waiting for a shared pair of launches (the combining queue of cqs_hip_sparse_index_search).
 // Lives on its caller's stack; the pointers are the caller's own buffers.
@@ -101,7 +94,23 @@ inline int32_t sfail(cqs_hip_sparse_index* s, int32_t code, const std::string& w
     return code;
 }
 
-// The tags follow an update that succeeded (sparse_index.hip).  Caller holds mu; the stream is idle.  Memory that fails
+// sparse_index_create.hip.  create_handle is every constructor: the device checked (CQS_HIP_ERR_NO_DEVICE), a fresh handle
+// given to `fill` - which sets n, ranked, chunk_of_rank, tok and off, hands back the host postings and says false to
+// refuse its arguments (CQS_HIP_ERR_INVALID) - then finish_create (device, wave ranges, range directories, scratch), and
+// the handle is the caller's.  On every failure what exists so far is released.
+using Fill = std::function<bool(cqs_hip_sparse_index* s, std::vector<cqs_sparse_build::Posting>* post)>;
+int32_t create_handle(int32_t device, const Fill& fill, cqs_hip_sparse_index** out);
+
+// sparse_index.hip.  ensure_batch: score rows, maxima and result keys for `b` queries (grown on demand).  search_locked:
+// shared by the search entry points; the caller holds s->mu.  q_off [b + 1]: the terms of query q are q_tokens / q_weights
+// [q_off[q], q_off[q + 1]).  allow (with a null keep_bitset; every chunk has a tag): the keep-bitset is the tag filter's,
+// written into d_keep by tags_keep_kernel in front of the scoring launch instead of copied from the host.
+int32_t ensure_batch(cqs_hip_sparse_index* s, uint32_t b);
+int32_t search_locked(cqs_hip_sparse_index* s, const uint64_t* q_off, const uint32_t* q_tokens, const float* q_weights, uint32_t b,
+                      uint32_t k, const uint32_t* keep_bitset, uint64_t* out_chunks, float* out_scores, uint32_t* out_counts,
+                      const uint32_t* allow = nullptr);
+
+// The tags follow an update that succeeded (sparse_index_tags.hip).  Caller holds mu; the stream is idle.  Memory that fails
 // here drops the tags (reason in last_error), never the update.
 void tags_after_remove(cqs_hip_sparse_index* s, const std::vector<uint32_t>& removed);   // distinct chunk indices, ascending
 void tags_after_extend(cqs_hip_sparse_index* s);

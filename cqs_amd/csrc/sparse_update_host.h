@@ -14,6 +14,7 @@
 #include <numeric>
 #include <vector>
 
+#include "sparse_build_host.h"
 #include "sparse_geometry.h"
 
 #if defined(__HIPCC__)
@@ -25,10 +26,9 @@
 namespace cqs_sparse_update {
 
 constexpr uint32_t kGone = 0xFFFFFFFFu;             // remap[] of a removed chunk's position; "no old list" of a new token
-constexpr uint32_t kReservedWeight = 0xFFFFFFFFu;   // the NaN payload the scoring kernel keeps for itself (kUnscored)
 constexpr uint64_t kChunkLimit = cqs::kSparseMaxChunks;   // create refuses n >= this
 
-struct Posting { uint32_t x, y; };                  // {position, weight bits}: the layout of the device's uint2
+using cqs_sparse_build::Posting;                    // {position, weight bits}: the layout of the device's uint2
 
 enum class Plan : int32_t {
     Invalid = -1,   // CQS_HIP_ERR_INVALID; *why says which argument; nothing planned
@@ -152,17 +152,8 @@ inline Plan plan_extend(const uint64_t* doc_off, const uint32_t* tokens, const f
     out->n_total = n_old;
     if (n_new == 0) return Plan::Nothing;
     if (n_new >= kChunkLimit || n_old + n_new >= kChunkLimit) { *why = "too many chunks"; return Plan::Invalid; }   // (before doc_off[n_new] is read)
-    if (!doc_off) { *why = "null doc_off"; return Plan::Invalid; }
-    if (doc_off[0] != 0) { *why = "doc_off does not start at 0"; return Plan::Invalid; }
-    for (uint64_t i = 0; i < n_new; ++i)
-        if (doc_off[i + 1] < doc_off[i]) { *why = "doc_off not ascending"; return Plan::Invalid; }
+    if (!cqs_sparse_build::check_csr(doc_off, n_new, tokens, weights, why)) return Plan::Invalid;
     const uint64_t PA = doc_off[n_new];
-    if (PA && (!tokens || !weights)) { *why = "null tokens / weights"; return Plan::Invalid; }
-    for (uint64_t e = 0; e < PA; ++e) {
-        uint32_t bits;
-        memcpy(&bits, &weights[e], 4);
-        if (bits == kReservedWeight) { *why = "reserved NaN payload in a weight"; return Plan::Invalid; }
-    }
     if (new_rank && !ranked) { *why = "new_rank on an index created without id_rank"; return Plan::Invalid; }
     const uint64_t n_total = n_old + n_new;
     // final position of every new chunk; the new ranks in ascending order

@@ -1,7 +1,7 @@
 // sparse_update_host_driver.cpp — cqs_amd/csrc/sparse_update_host.h as a stand-alone CPU program (built with ASAN + UBSan
 // by tests/test_sparse_update_host_cpu.py): for every case on stdin, the canonical arrays of the index built from the
-// documents on the host (what cqs_hip_sparse_index_create builds), the plan of a remove or an extend, and the position
-// rules the kernels implement replayed over host arrays.  Prints the resulting index; the test compares it with its own
+// documents by the library's own host builder (sparse_build_host.h: what cqs_hip_sparse_index_create builds), the plan of
+// a remove or an extend, and the position rules the kernels implement replayed over host arrays.  Prints the resulting index; the test compares it with its own
 // from-scratch build of the resulting documents.
 //
 // One case per line, fields separated by '|', lists of integers separated by spaces, "null" = a NULL pointer:
@@ -10,6 +10,7 @@
 // Output: name|plan|why|chunks|tokens|offsets|postings position:bits|chunk_of_rank|checks
 #include <cstdint>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <iostream>
 #include <sstream>
@@ -60,34 +61,25 @@ struct Index {
     std::vector<uint32_t> chunk_of_rank;
 };
 
-// cqs_hip_sparse_index_create's arrays: sorted distinct tokens, every list in ascending position, a chunk's postings in
-// document order.
+// cqs_hip_sparse_index_create's arrays, by the library's own builder (sparse_build_host.h).
 static Index build(uint64_t n, const std::vector<uint64_t>& doc_off, const std::vector<uint32_t>& tokens, const std::vector<uint32_t>& wbits,
                    const List& id_rank) {
     Index x;
     x.n = n;
     x.ranked = !id_rank.null;
-    if (x.ranked) {
-        x.chunk_of_rank.resize(n);
-        for (uint64_t i = 0; i < n; ++i) x.chunk_of_rank[id_rank.v[i]] = (uint32_t)i;
+    const std::vector<uint32_t> rank = narrow<uint32_t>(id_rank);
+    std::vector<float> w(wbits.size());
+    if (!wbits.empty()) memcpy(w.data(), wbits.data(), wbits.size() * 4);
+    const char* why = "";
+    if (!cqs_sparse_build::check_csr(doc_off.data(), n, tokens.data(), w.data(), &why) ||
+        !cqs_sparse_build::rank_table(n, x.ranked ? rank.data() : nullptr, &x.chunk_of_rank)) {
+        fprintf(stderr, "bad case index: %s\n", why);
+        exit(2);
     }
-    std::vector<uint32_t> sorted(tokens);
-    std::sort(sorted.begin(), sorted.end());
-    sorted.erase(std::unique(sorted.begin(), sorted.end()), sorted.end());
-    x.tok = sorted;
-    std::vector<std::vector<su::Posting>> lists(x.tok.size());
-    for (uint64_t r = 0; r < n; ++r) {
-        const uint64_t d = x.ranked ? x.chunk_of_rank[r] : r;
-        for (uint64_t e = doc_off[d]; e < doc_off[d + 1]; ++e) {
-            const size_t slot = (size_t)(std::lower_bound(x.tok.begin(), x.tok.end(), tokens[e]) - x.tok.begin());
-            lists[slot].push_back(su::Posting{(uint32_t)r, wbits[e]});
-        }
-    }
-    x.off.push_back(0);
-    for (const auto& l : lists) {
-        x.post.insert(x.post.end(), l.begin(), l.end());
-        x.off.push_back(x.post.size());
-    }
+    cqs_sparse_build::Built b = cqs_sparse_build::from_documents(doc_off.data(), tokens.data(), w.data(), n, x.chunk_of_rank);
+    x.tok.swap(b.tok);
+    x.off.swap(b.off);
+    x.post.swap(b.post);
     return x;
 }
 

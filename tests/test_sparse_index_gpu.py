@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 
 import sparse_cases as sc
+from sparse_host_cases import _csr, _docs, _forge_sparse_file, _ranks, canonical
 
 pytestmark = pytest.mark.gpu
 
@@ -435,32 +436,6 @@ def test_persistence_round_trip_and_rejections(S, oracle, tmp_path):
         x.close()
 
 
-def _forge_sparse_file(path, chunks, tok, off, post, rank=None, generation=1, fix_checksum=True):
-    """A file in the library's sparse-index format with a VALID checksum (the multiply-rotate hash of persist_util.h restated
-    here), whatever its sections hold - to reach the loader's structure checks behind the checksum."""
-    import struct
-    M = (1 << 64) - 1
-    P1, P2 = 0x9E3779B185EBCA87, 0xC2B2AE3D27D4EB4F
-
-    def pad8(b):
-        return b + b"\0" * (-len(b) % 8)
-
-    secs = [pad8(np.asarray(tok, np.uint32).tobytes()), pad8(np.asarray(off, np.uint64).tobytes()),
-            pad8(np.asarray(post, np.uint32).reshape(-1, 2).tobytes() if len(post) else b""),
-            pad8(np.asarray(rank, np.uint32).tobytes()) if rank is not None else b""]
-    body = b"".join(secs)
-    h = 0x27D4EB2F165667C5 ^ len(body)
-    for (w,) in struct.iter_unpack("<Q", body):
-        h ^= (w * P1) & M
-        h = ((((h << 31) | (h >> 33)) & M) * P2) & M
-    h ^= h >> 29; h = (h * P2) & M; h ^= h >> 32
-    if not fix_checksum:
-        h ^= 1
-    header = struct.pack("<8sIIQQQQQ8s", b"CQSHIPS1", 1, 1 if rank is not None else 0, chunks, len(tok), len(post), generation, h, b"\0" * 8)
-    assert len(header) == 64
-    open(path, "wb").write(header + body)
-
-
 def test_loader_rejects_forged_structure(S, tmp_path):
     """The loader is handed a file from disk: behind a matching checksum it still re-checks everything the kernels rely on
     (they index LDS by posting position).  A well-formed forged file loads and answers; each single defect - a position past
@@ -499,3 +474,23 @@ def test_loader_rejects_forged_structure(S, tmp_path):
     assert S.HipSpladeIndex.load(p, 1) is None                                       # and the checksum itself
     _forge_sparse_file(p, **good)
     assert S.HipSpladeIndex.load(p, 1) is not None                                   # (the forger is sound)
+
+
+@pytest.mark.parametrize("ranked", [False, True])
+def test_saved_bytes_are_the_documented_format(S, tmp_path, ranked):
+    """The on-disk format byte for byte: `save` of an index built from documents writes exactly the file the Python
+    restatement of the format writes from the Python restatement of the build - header, the four padded sections (71 chunks
+    and an odd token count: both u32 sections end in a padded word), checksum."""
+    rng = np.random.default_rng(71)
+    docs = _docs(rng, 71, 41, lo=7, hi=11)
+    rank = _ranks(rng, 71) if ranked else None
+    off, tok, w = _csr(docs)
+    h = S.HipSpladeIndex.build_from_csr(None, np.asarray(off, np.uint64), np.asarray(tok, np.uint32), np.asarray(w, np.uint32).view(np.float32),
+                                        id_rank=None if rank is None else np.asarray(rank, np.uint32))
+    n, ctok, coff, cpost, cor = canonical(docs, rank)
+    assert len(ctok) % 2 == 1 and h.unique_tokens() == len(ctok) and h.postings() == len(cpost)
+    got, want = tmp_path / "saved.bin", tmp_path / "forged.bin"
+    h.save(got, generation=5)
+    h.close()
+    _forge_sparse_file(want, n, ctok, coff, cpost, rank=cor if ranked else None, generation=5)
+    assert got.read_bytes() == want.read_bytes()

@@ -11,42 +11,11 @@ import subprocess
 import numpy as np
 import pytest
 
+from sparse_host_cases import _csr, _docs, _ranks, canonical
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 INVALID, NOTHING, UPDATE = -1, 0, 1
 RESERVED = 0xFFFFFFFF
-
-
-def _docs(rng, n, vocab, lo=0, hi=6, base=100, step=3):
-    """n documents of lo..hi postings over token ids base, base + step, ...; about a third repeat one of their tokens."""
-    docs = []
-    for _ in range(n):
-        k = int(rng.integers(lo, hi + 1))
-        t = np.sort(rng.integers(0, vocab, size=k)) * step + base
-        if k >= 2 and rng.random() < 0.35:
-            t[1] = t[0]
-        w = (rng.random(k, dtype=np.float32) * 3 - 1).astype(np.float32).view(np.uint32)
-        docs.append([(int(a), int(b)) for a, b in zip(t, w)])
-    return docs
-
-
-def _ranks(rng, n):
-    return [int(x) for x in rng.permutation(n)]
-
-
-def canonical(docs, id_rank):
-    """What cqs_hip_sparse_index_create builds: (n, tokens, offsets, postings [(position, weight bits)], chunk_of_rank)."""
-    n = len(docs)
-    cor = list(np.argsort(np.asarray(id_rank, dtype=np.int64))) if id_rank is not None else list(range(n))
-    lists = {}
-    for r in range(n):
-        for t, w in docs[cor[r]]:
-            lists.setdefault(t, []).append((r, w))
-    tok = sorted(lists)
-    off, post = [0], []
-    for t in tok:
-        post += lists[t]
-        off.append(len(post))
-    return n, tok, off, post, ([int(c) for c in cor] if id_rank is not None else [])
 
 
 def expect_remove(docs, id_rank, chunks):
@@ -130,13 +99,6 @@ def _cases():
 
 
 CASES = _cases()
-
-
-def _csr(docs):
-    off = [0]
-    for d in docs:
-        off.append(off[-1] + len(d))
-    return off, [t for d in docs for t, _ in d], [w for d in docs for _, w in d]
 
 
 def _fmt(xs):
