@@ -19,8 +19,9 @@ constexpr uint64_t kShadowAutoBytes = 1ull << 30;
 constexpr uint64_t kShadowFreeMinBytes = 4ull << 30;
 constexpr double kShadowFreeFrac = 0.10;
 // Device counters behind the maxima of the two build passes: [3, 5) certified / fallback queries of the device-API
-// searches, whichever copy served them; [8, 10) those of them the int8 copy served.
-constexpr uint32_t kStatWords = 10, kStatCounts = 3, kStatI8 = 5, kStatI8Counts = 8;
+// searches, whichever copy served them; [8, 10) those of them the int8 copy served; [10, 12) queries of any search whose
+// finisher certified on a prefix of the candidates / whose prefix failed (cqs_hip_debug_tail_verdicts).
+constexpr uint32_t kStatWords = 12, kStatCounts = 3, kStatI8 = 5, kStatI8Counts = 8, kStatPrefix = 10;
 
 // Built at create / load where it pays, CQS_HIP_SCAN_BF16, or cqs_hip_index_set_bf16_scan: searches of gemv blocks scan it
 // first, rescore the candidates from the f32 rows and fall back to the f32 scan for any query the certificate does not
@@ -49,6 +50,8 @@ struct Shadow {
                                           // launch (scan_fallback.h)
     bool fb_one_launch = true;            // CQS_HIP_FALLBACK_ONE_LAUNCH, read when the shadow is built: 0 = the device-API searches'
                                           // f32 fallback is always the gated scan + select pair
+    bool tail_prefix = true;              // CQS_HIP_TAIL_PREFIX, read when the shadow is built: 0 = the tail kernel's finisher always
+                                          // sorts every candidate at once (the A/B arm and the tests' reference; same answers)
     uint32_t* h_cert = nullptr;           // pinned [kShadowMaxQ]
     uint32_t* h_cert_dev = nullptr;       // its device-visible address (null: not mappable)
 };
@@ -259,6 +262,8 @@ static int32_t shadow_enable(cqs_hip_index* x, const char* what) {
     if ((e = hipMemsetAsync(s->d_tickets, 0, (size_t)cqs::kShadowMaxQ * sizeof(uint32_t), x->stream)) != hipSuccess) return oom(e);
     const char* fb_env = getenv("CQS_HIP_FALLBACK_ONE_LAUNCH");
     s->fb_one_launch = !(fb_env && fb_env[0] == '0');
+    const char* tp_env = getenv("CQS_HIP_TAIL_PREFIX");
+    s->tail_prefix = !(tp_env && tp_env[0] == '0');
     if ((e = hipMalloc(&s->d_fb_lists, cqs::f32_topk_fallback_words(x->n_cu) * sizeof(uint64_t))) != hipSuccess) return oom(e);
     if ((e = hipMalloc(&s->d_fb_tickets, (size_t)cqs::kMaxGemvQ * sizeof(uint32_t))) != hipSuccess) return oom(e);
     if ((e = hipMemsetAsync(s->d_fb_tickets, 0, (size_t)cqs::kMaxGemvQ * sizeof(uint32_t), x->stream)) != hipSuccess) return oom(e);
@@ -391,7 +396,8 @@ int32_t shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k,
         HIP_TRY(x, cqs::launch_rescore_certify(a, (uint32_t)x->row_base, k, kp, bound_first ? 0u : (i8 ? 2u : 1u), r_max, norm_max,
                                                s->d_bq, s->d_tickets, s->d_ekeys, out_keys, out_counts, cert,
                                                device_gate ? s->d_stats + kStatCounts : nullptr,
-                                               device_gate && i8 ? s->d_stats + kStatI8Counts : nullptr, st));
+                                               device_gate && i8 ? s->d_stats + kStatI8Counts : nullptr, s->tail_prefix,
+                                               s->d_stats + kStatPrefix, x->d_dbg, st));
     return rc;
 }
 
@@ -536,6 +542,51 @@ int32_t cqs_hip_debug_shadow_bq(cqs_hip_index* x, uint32_t b, float* out) CQS_AB
     HIP_TRY(x, hipSetDevice(x->device));
     HIP_TRY(x, quiesce(x));
     HIP_TRY(x, hipMemcpyAsync(out, s->d_bq, (size_t)b * sizeof(float), hipMemcpyDeviceToHost, x->stream));
+    HIP_TRY(x, hipStreamSynchronize(x->stream));
+    return CQS_HIP_OK;
+} CQS_ABI_CATCH(x)
+
+// Test hook: out[0, b) = the tail kernel's ticket words as the last search left them (0 between searches), once every search
+// has completed.  INVALID without a shadow or for b > kShadowMaxQ.
+int32_t cqs_hip_debug_shadow_tickets(cqs_hip_index* x, uint32_t b, uint32_t* out) CQS_ABI_TRY {
+    if (!x || x->sh || !out || b == 0) return CQS_HIP_ERR_INVALID;
+    std::lock_guard<std::mutex> g(x->mu);
+    const Shadow* s = x->shadow;
+    if (!s || b > cqs::kShadowMaxQ) return CQS_HIP_ERR_INVALID;
+    HIP_TRY(x, hipSetDevice(x->device));
+    HIP_TRY(x, quiesce(x));
+    HIP_TRY(x, hipMemcpyAsync(out, s->d_tickets, (size_t)b * sizeof(uint32_t), hipMemcpyDeviceToHost, x->stream));
+    HIP_TRY(x, hipStreamSynchronize(x->stream));
+    return CQS_HIP_OK;
+} CQS_ABI_CATCH(x)
+
+// Test hook: out[0, b) = the verdicts of the last device-API search's queries (d_cert: 1 = certified, 0 = the gated f32
+// launches answered), out_prefix[0, 2) = queries since the shadow was built whose finisher certified on the prefix / whose
+// prefix failed and that went on to sort every candidate; once every search has completed.  INVALID without a shadow.
+int32_t cqs_hip_debug_tail_verdicts(cqs_hip_index* x, uint32_t b, uint32_t* out, uint64_t* out_prefix) CQS_ABI_TRY {
+    if (!x || x->sh || !out || !out_prefix || b == 0) return CQS_HIP_ERR_INVALID;
+    std::lock_guard<std::mutex> g(x->mu);
+    const Shadow* s = x->shadow;
+    if (!s || b > cqs::kShadowMaxQ) return CQS_HIP_ERR_INVALID;
+    HIP_TRY(x, hipSetDevice(x->device));
+    HIP_TRY(x, quiesce(x));
+    HIP_TRY(x, hipMemcpyAsync(out, s->d_cert, (size_t)b * sizeof(uint32_t), hipMemcpyDeviceToHost, x->stream));
+    HIP_TRY(x, hipMemcpyAsync(out_prefix, s->d_stats + kStatPrefix, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost, x->stream));
+    HIP_TRY(x, hipStreamSynchronize(x->stream));
+    return CQS_HIP_OK;
+} CQS_ABI_CATCH(x)
+
+// Diagnostic hook (CQS_HIP_DEBUG_STAMPS=1 handles; tools/tail_stamps.py): out[0, 16) = the phase stamps query 0 of the last
+// shadow search left (select_body's and the tail kernel's, 10 ns ticks), once every search has completed; the words are
+// zeroed for the next search.  INVALID on a handle without the stamp buffer.
+int32_t cqs_hip_debug_tail_stamps(cqs_hip_index* x, uint64_t* out) CQS_ABI_TRY {
+    if (!x || x->sh || !out) return CQS_HIP_ERR_INVALID;
+    std::lock_guard<std::mutex> g(x->mu);
+    if (!x->d_dbg) return CQS_HIP_ERR_INVALID;
+    HIP_TRY(x, hipSetDevice(x->device));
+    HIP_TRY(x, quiesce(x));
+    HIP_TRY(x, hipMemcpyAsync(out, x->d_dbg, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost, x->stream));
+    HIP_TRY(x, hipMemsetAsync(x->d_dbg, 0, 16 * sizeof(uint64_t), x->stream));
     HIP_TRY(x, hipStreamSynchronize(x->stream));
     return CQS_HIP_OK;
 } CQS_ABI_CATCH(x)

@@ -21,6 +21,7 @@
 #include "scan_gemv_device.h"
 #include "select_device.h"
 #include "shadow_build_device.h"
+#include "tail_prefix.h"
 
 namespace cqs {
 
@@ -348,6 +349,9 @@ struct TailParams {
     uint32_t* cert;            // [b]
     unsigned long long* counters;   // nullable [2]: certified, not certified
     unsigned long long* counters2;  // nullable [2]: the same again (the int8 copy's own counts)
+    uint32_t prefix;           // 1: the finisher sorts a prefix first (tail_prefix.h), 0: all candidates at once
+    unsigned long long* prefix_counts;   // nullable [2]: queries certified on the prefix, queries that went on to sort all
+    unsigned long long* dbg;   // CQS_HIP_DEBUG_STAMPS (DBG instantiations only): [0, 16) phase stamps of query 0's tail
 };
 
 constexpr uint32_t kTailWaves = 16;   // 1024 threads: the block shape select_body and rank_sort_keys are written for
@@ -374,7 +378,10 @@ constexpr uint32_t kTailWaves = 16;   // 1024 threads: the block shape select_bo
 // write-through by an agent-scope atomic store, each wave drains its stores before the workgroup's barrier, one lane then
 // adds to the ticket, and the finisher reads those words by agent-scope atomic loads only, after the add has returned and a
 // barrier that the adding wave joins.  scores / gmax / gaux come from an earlier launch and are read plainly.
-template <int NCH>
+// DBG: phase stamps of query 0's tail (s_memrealtime) into p.dbg: [0, 6) select_body's, 6 / 7 first rows issued / reduced
+// (lane 0 of workgroup 0's wave 1), 10 workgroup 0's ticket returned, 14 the finisher's, 11 / 12 / 13 the finisher's keys
+// listed / sorted / outputs stored.
+template <int NCH, bool DBG>
 __global__ __launch_bounds__(1024) void rescore_certify_kernel(const TailParams p) {
     __shared__ uint64_t s_keys[kShadowKMax];
     __shared__ uint64_t s_sorted[kShadowKMax];
@@ -382,23 +389,53 @@ __global__ __launch_bounds__(1024) void rescore_certify_kernel(const TailParams 
     __shared__ uint32_t s_cnt, s_flag, s_last;
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t qi = blockIdx.y;
-    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * kTailWaves + (threadIdx.x >> 6)));
+    const uint32_t wib = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t wave = blockIdx.x * kTailWaves + wib;
     const uint32_t n_waves = gridDim.x * kTailWaves;
     const uint32_t dim = p.dim;
     const float* qp = p.q + (size_t)qi * dim;
+    unsigned long long* const dbg = DBG && qi == 0u ? p.dbg : nullptr;
+#define CQS_TAIL_STAMP(i, who) do { if (DBG && dbg && (who)) dbg[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
     if (threadIdx.x == 0) s_cnt = 0u;
     if (qi == 0u && blockIdx.x == 0u)
         for (uint32_t i = threadIdx.x; i < kWorkWords; i += 1024u) p.work[i] = 0u;
-
     // the approximate top k' + 1, sorted: what select_finish_kernel wrote to akeys / acounts when it was a launch of its own
     const uint32_t n_tasks = p.tiers.total();
     uint32_t found;
     const uint64_t* akeys = select_body(p.scores + (size_t)qi * p.n_pad, p.gmax + (size_t)qi * n_tasks,
                                         p.gaux ? p.gaux + (size_t)qi * n_tasks : nullptr, p.n_pad, p.tiers, p.kprime + 1u,
-                                        p.row_base, p.bins, nullptr, found);
+                                        p.row_base, p.bins, DBG ? dbg : nullptr, found);
+    found = (uint32_t)__builtin_amdgcn_readfirstlane((int)found);   // (workgroup-uniform: a scalar from here on)
     const uint32_t ac = found < p.kprime + 1u ? found : p.kprime + 1u;
     const uint32_t nc = ac < p.kprime ? ac : p.kprime;
     const uint64_t key_next = ac > p.kprime ? akeys[p.kprime] : 0ull;   // the (k' + 1)-th approximate key (the finisher's)
+
+    // top k of the m kept exact keys in s_keys, the outputs, the verdict: what the last workgroup to arrive does, and
+    // workgroup 0 on the path of its own
+    auto write_out = [&](uint32_t m, bool ok) {
+        const uint32_t k = p.k;
+        const uint32_t outc = m < k ? m : k;
+        for (uint32_t i = threadIdx.x; i < k; i += 1024u) p.out_keys[(size_t)qi * k + i] = (i < outc) ? s_sorted[i] : 0ull;
+        if (threadIdx.x == 0) {
+            p.out_counts[qi] = outc;
+            p.cert[qi] = ok ? 1u : 0u;   // (before the kernel ends: the gated f32 launches that follow read it at entry)
+            if (p.counters) atomicAdd(&p.counters[ok ? 0 : 1], 1ull);
+            if (p.counters2) atomicAdd(&p.counters2[ok ? 0 : 1], 1ull);
+        }
+    };
+    // today's rules on all min(count, k') candidates, m of them kept
+    auto full_verdict = [&](uint32_t m, float bq) {
+        bool ok = false;
+        if (__builtin_fabsf(bq) <= 3.4028234664e38f) {
+            if (ac <= p.kprime) ok = true;   // (a) every row the approximate rules keep was rescored
+            else if (m >= p.k) {             // (b) every outsider j: s_j <= s~_j + B_q <= s~_(k'+1) + B_q < s_(k)
+                float t = key_score(key_next) + bq;
+                if (p.mode == 1u) t = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);
+                ok = t < key_score(s_sorted[p.k - 1u]);
+            }
+        }
+        return ok;
+    };
 
     for (uint32_t slot = wave; slot <= nc; slot += n_waves) {
         if (slot == 0u) {
@@ -417,11 +454,13 @@ __global__ __launch_bounds__(1024) void rescore_certify_kernel(const TailParams 
         // the exact score and scan_gemv_kernel's epilogue: f32_score.h, shared with the one-launch f32 fallback
         f4 x[NCH], qv[NCH];
         f32_fragments<NCH>(rp, qp, dim, lane, x, qv);
+        CQS_TAIL_STAMP(6, slot == 1u && threadIdx.x == 64u);
         float s = f32_dot_chain<NCH>(x, qv);
         const bool keep = f32_emit(s, p.mode, p.thr);
         if (lane == 0u)
             __hip_atomic_store(p.ekeys + (size_t)qi * p.kprime + i, keep ? pack_key(okey(s), grow) : 0ull, __ATOMIC_RELAXED,
                                __HIP_MEMORY_SCOPE_AGENT);
+        CQS_TAIL_STAMP(7, slot == 1u && threadIdx.x == 64u);
     }
     // hand-off: every wave drains its stores, the barrier, then one lane signals for the workgroup
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -431,47 +470,74 @@ __global__ __launch_bounds__(1024) void rescore_certify_kernel(const TailParams 
         const bool last = t == gridDim.x - 1u;
         if (last) __hip_atomic_store(p.tickets + qi, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // armed for the next search
         s_last = last ? 1u : 0u;
+        CQS_TAIL_STAMP(10, blockIdx.x == 0u);
+        CQS_TAIL_STAMP(14, last);
     }
     __syncthreads();
     if (s_last == 0u) return;   // (workgroup-uniform) not the last to arrive: done
 
-    // the finisher: every other workgroup of the query has stored, drained and signalled
-    if (threadIdx.x < nc) {
+    // the finisher: every other workgroup of the query has stored, drained and signalled.  The certificate holds for any
+    // prefix of the candidates (tail_prefix_first), and the rank sort is quadratic in what it sorts: first the prefix alone;
+    // the rest only if the prefix does not certify, and then today's rules on all of them.
+    const uint32_t j1 = p.prefix ? tail_prefix_first(p.k, nc) : nc;
+    if (threadIdx.x < j1) {
         const uint64_t key = __hip_atomic_load(p.ekeys + (size_t)qi * p.kprime + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (key != 0ull) s_keys[atomicAdd(&s_cnt, 1u)] = key;
     }
     __syncthreads();
-    const uint32_t m = s_cnt;
-    rank_sort_keys(s_keys, m, s_sorted, s_ok, &s_flag);
-    const uint32_t k = p.k;
-    const uint32_t outc = m < k ? m : k;
-    for (uint32_t i = threadIdx.x; i < k; i += 1024u) p.out_keys[(size_t)qi * k + i] = (i < outc) ? s_sorted[i] : 0ull;
-    if (threadIdx.x == 0) {
-        p.out_counts[qi] = outc;
-        const float bq = __uint_as_float(__hip_atomic_load((uint32_t*)p.bq + qi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-        bool ok = false;
-        if (__builtin_fabsf(bq) <= 3.4028234664e38f) {
-            if (ac <= p.kprime) ok = true;   // (a) every row the approximate rules keep was rescored
-            else if (m >= k) {               // (b) every outsider j: s_j <= s~_j + B_q <= s~_(k'+1) + B_q < s_(k)
-                float t = key_score(key_next) + bq;
-                if (p.mode == 1u) t = t < 0.f ? 0.f : (t > 1.f ? 1.f : t);
-                ok = t < key_score(s_sorted[k - 1u]);
-            }
+    CQS_TAIL_STAMP(11, threadIdx.x == 0u);
+    uint32_t m = s_cnt;
+    float bq = 0.f;   // (asked for ahead of the sort: the prefix's verdict stands between the sort and the outputs)
+    if (threadIdx.x == 0) bq = __uint_as_float(__hip_atomic_load((uint32_t*)p.bq + qi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    // a proper prefix is short (6k + 40 keys): all 1024 threads rank it; every candidate at once is the sort it always was
+    if (j1 < nc) rank_sort_keys_wide(s_keys, m, s_sorted, s_ok, &s_flag);
+    else rank_sort_keys(s_keys, m, s_sorted, s_ok, &s_flag);
+    if (j1 < nc) {   // (workgroup-uniform) a proper prefix: candidate j1 is the first row outside it
+        if (threadIdx.x == 0) {
+            bool ok = false;
+            if (__builtin_fabsf(bq) <= 3.4028234664e38f && m >= p.k)
+                ok = tail_prefix_certifies(akeys[j1], bq, p.mode, key_score(s_sorted[p.k - 1u]));
+            s_last = ok ? 2u : 1u;
+            if (p.prefix_counts) atomicAdd(&p.prefix_counts[ok ? 0 : 1], 1ull);
         }
-        p.cert[qi] = ok ? 1u : 0u;   // (before the kernel ends: the gated f32 launches that follow read it at entry)
-        if (p.counters) atomicAdd(&p.counters[ok ? 0 : 1], 1ull);
-        if (p.counters2) atomicAdd(&p.counters2[ok ? 0 : 1], 1ull);
+        __syncthreads();
+        if (s_last == 2u) {
+            CQS_TAIL_STAMP(12, threadIdx.x == 0u);
+            write_out(m, true);
+            CQS_TAIL_STAMP(13, threadIdx.x == 0u);
+            return;
+        }
+        if (threadIdx.x >= j1 && threadIdx.x < nc) {
+            const uint64_t key = __hip_atomic_load(p.ekeys + (size_t)qi * p.kprime + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (key != 0ull) s_keys[atomicAdd(&s_cnt, 1u)] = key;
+        }
+        __syncthreads();
+        m = s_cnt;
+        rank_sort_keys(s_keys, m, s_sorted, s_ok, &s_flag);
     }
+    CQS_TAIL_STAMP(12, threadIdx.x == 0u);
+    bool ok = false;
+    if (threadIdx.x == 0) ok = full_verdict(m, bq);
+    write_out(m, ok);
+    CQS_TAIL_STAMP(13, threadIdx.x == 0u);
+#undef CQS_TAIL_STAMP
 }
 
 #ifndef CQS_TAIL_MAX_BLOCKS_PER_CU
 #define CQS_TAIL_MAX_BLOCKS_PER_CU 1u   // the select's LDS leaves room for one workgroup per CU: the grid stays one round
 #endif
 
+template <int NCH>
+static void launch_tail(dim3 grid, dim3 block, hipStream_t st, const TailParams& tp) {
+    if (tp.dbg) hipLaunchKernelGGL((rescore_certify_kernel<NCH, true>), grid, block, 0, st, tp);
+    else hipLaunchKernelGGL((rescore_certify_kernel<NCH, false>), grid, block, 0, st, tp);
+}
+
 hipError_t launch_rescore_certify(const ScanArgs& a, uint32_t row_base, uint32_t k, uint32_t kprime, uint32_t bound,
                                   double r_max, double norm_max, float* bq, uint32_t* tickets, uint64_t* ekeys,
                                   uint64_t* out_keys, uint32_t* out_counts, uint32_t* cert, unsigned long long* counters,
-                                  unsigned long long* counters2, hipStream_t st) {
+                                  unsigned long long* counters2, bool prefix, unsigned long long* prefix_counts, unsigned long long* dbg,
+                                  hipStream_t st) {
     const uint32_t b = a.b, dim = a.dim;
     if (b == 0) return hipSuccess;
     if (b > kShadowMaxQ || k == 0 || kprime < k || kprime >= kShadowKMax || a.k != kprime + 1u || dim % 8u != 0u ||
@@ -479,7 +545,7 @@ hipError_t launch_rescore_certify(const ScanArgs& a, uint32_t row_base, uint32_t
         return hipErrorInvalidValue;
     const TailParams tp{a.rows, a.q, dim, k, kprime, a.mode, row_base, a.threshold, a.scores, a.gmax, a.gaux, a.n_pad, a.tiers,
                         a.range_bins ? 2u : (a.linear_bins ? 1u : 0u), a.work, ekeys, bq, tickets, bound, r_max, norm_max,
-                        out_keys, out_counts, cert, counters, counters2};
+                        out_keys, out_counts, cert, counters, counters2, prefix ? 1u : 0u, prefix_counts, dbg};
     // One wave per slot (B_q + k' candidates) while the block's workgroups fit the device in one round; beyond that
     // (b * ceil((k' + 1) / 16) > CUs: from b = 4 at k = 500) fewer workgroups whose waves take several slots each, because
     // every workgroup repeats the select's front end and a second round would repeat it behind the first.
@@ -488,14 +554,14 @@ hipError_t launch_rescore_certify(const ScanArgs& a, uint32_t row_base, uint32_t
     if (cap < 1u) cap = 1u;
     const dim3 grid(want < cap ? want : cap, b), block(64u * kTailWaves);
     switch ((dim + 255u) / 256u) {
-        case 1: hipLaunchKernelGGL(rescore_certify_kernel<1>, grid, block, 0, st, tp); break;
-        case 2: hipLaunchKernelGGL(rescore_certify_kernel<2>, grid, block, 0, st, tp); break;
-        case 3: hipLaunchKernelGGL(rescore_certify_kernel<3>, grid, block, 0, st, tp); break;
-        case 4: hipLaunchKernelGGL(rescore_certify_kernel<4>, grid, block, 0, st, tp); break;
-        case 5: hipLaunchKernelGGL(rescore_certify_kernel<5>, grid, block, 0, st, tp); break;
-        case 6: hipLaunchKernelGGL(rescore_certify_kernel<6>, grid, block, 0, st, tp); break;
-        case 7: hipLaunchKernelGGL(rescore_certify_kernel<7>, grid, block, 0, st, tp); break;
-        case 8: hipLaunchKernelGGL(rescore_certify_kernel<8>, grid, block, 0, st, tp); break;
+        case 1: launch_tail<1>(grid, block, st, tp); break;
+        case 2: launch_tail<2>(grid, block, st, tp); break;
+        case 3: launch_tail<3>(grid, block, st, tp); break;
+        case 4: launch_tail<4>(grid, block, st, tp); break;
+        case 5: launch_tail<5>(grid, block, st, tp); break;
+        case 6: launch_tail<6>(grid, block, st, tp); break;
+        case 7: launch_tail<7>(grid, block, st, tp); break;
+        case 8: launch_tail<8>(grid, block, st, tp); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
