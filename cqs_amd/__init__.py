@@ -3,8 +3,8 @@
 Product code lives here and in cqs_amd/csrc (HIP kernels + C ABI, include/cqs_hip.h).
 It never imports anything from oracle/ (test infrastructure).
 """
-from .index import (BackendContext, DistanceMetric, HipBackend, HipError, HipIndex, IndexResult,
-                    VectorIndex, merge_keys, prepare_index_data, tag_filter, unpack_keys)
+from .index import (BackendContext, DiffEntry, DiffResult, DistanceMetric, DriftEntry, DriftResult, HipBackend, HipError,
+                    HipIndex, IndexResult, VectorIndex, merge_keys, prepare_index_data, tag_filter, unpack_keys)
 
-__all__ = ["BackendContext", "DistanceMetric", "HipBackend", "HipError", "HipIndex", "IndexResult",
-           "VectorIndex", "merge_keys", "prepare_index_data", "tag_filter", "unpack_keys"]
+__all__ = ["BackendContext", "DiffEntry", "DiffResult", "DistanceMetric", "DriftEntry", "DriftResult", "HipBackend", "HipError",
+           "HipIndex", "IndexResult", "VectorIndex", "merge_keys", "prepare_index_data", "tag_filter", "unpack_keys"]

@@ -89,6 +89,8 @@ SIGNATURES = [
     ("cqs_hip_index_neighbors", C.c_int32, [_c_idx, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, _pp(C.c_uint32)]),
     ("cqs_hip_index_knn_graph", C.c_int32,
      [_c_idx, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("cqs_hip_index_diff", C.c_int32,
+     [_c_idx, C.c_void_p, _c_idx, C.c_void_p, C.c_uint64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("cqs_hip_index_pairwise", C.c_int32, [_c_idx, C.c_void_p, C.c_uint32, C.c_void_p]),
     ("cqs_hip_index_mmr", C.c_int32,
      [_c_idx, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, _pp(C.c_uint32)]),
@@ -162,7 +164,7 @@ SIGNATURES = [
     ("cqs_hip_sparse_index_last_error", C.c_size_t, [_c_idx, C.c_char_p, C.c_size_t]),
 ]
 
-# Test hooks the library exports beside the header's symbols (embedder.hip, index_remove.hip, index_tags.hip, index_combine.hip; not part of
+# Test hooks the library exports beside the header's symbols (embedder.hip, index_remove.hip, index_update.hip, index_diff.hip, index_tags.hip, index_combine.hip; not part of
 # include/cqs_hip.h).
 DEBUG_SIGNATURES = [
     ("cqs_hip_debug_index_tag_keep", C.c_int32, [_c_idx, C.c_void_p, C.c_void_p]),
@@ -171,6 +173,7 @@ DEBUG_SIGNATURES = [
      [_c_idx, C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("cqs_hip_debug_index_remove_budget", None, [_c_idx, C.c_uint64]),
     ("cqs_hip_debug_index_update_budget", None, [_c_idx, C.c_uint64]),
+    ("cqs_hip_debug_index_diff_budget", None, [_c_idx, C.c_uint64]),
     ("cqs_hip_debug_embedder_query_state", C.c_int32,
      [_c_idx, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _pp(C.c_int32)]),
 ]

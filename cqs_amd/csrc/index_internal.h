@@ -1,6 +1,6 @@
 // index_internal.h — the index handle and the host helpers shared by the index's translation units (index.hip,
-// index_persist.hip, index_combine.hip, index_shadow.hip, index_remove.hip, index_update.hip, index_knn.hip, mmr.hip,
-// sharded.hip).
+// index_persist.hip, index_combine.hip, index_shadow.hip, index_remove.hip, index_update.hip, index_knn.hip, index_diff.hip,
+// mmr.hip, sharded.hip).
 // Internal to libcqs_hip.so (the public boundary is include/cqs_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -111,6 +111,7 @@ struct cqs_hip_index {
     std::atomic<int32_t> inject_fail{0};  // test hook (cqs_hip_debug_index_fail_next): the next host search (or remove) fails as a device error
     uint64_t remove_budget_rows = 0;      // test hook (cqs_hip_debug_index_remove_budget): rows per pass of remove; 0 = the bounce buffer's byte budget
     uint64_t update_budget_rows = 0;      // test hook (cqs_hip_debug_index_update_budget): rows per pass of update; 0 = the staging buffer's byte budget
+    uint64_t diff_budget_pairs = 0;       // test hook (cqs_hip_debug_index_diff_budget): pairs per pass of diff, on the `a` handle; 0 = cqs_diff::kPassPairs
 
     // Staging of cqs_hip_index_update (index_update.hip; null until the first update): a pass's new rows and their
     // destination list, pinned, and the device block they are copied into.  Kept between calls, freed at destroy.
@@ -123,6 +124,13 @@ struct cqs_hip_index {
     void* knn_h = nullptr;
     void* knn_d = nullptr;
     size_t knn_bytes = 0;
+
+    // Staging of cqs_hip_index_diff (index_diff.hip; null until the first such call with this handle as `a`): a pass's
+    // local row lists, sims, class words, compacted list and counts in one block on the device and its pinned twin, sized
+    // for diff_pairs pairs (the largest pass seen).  Kept between calls, freed at destroy.
+    void* diff_h = nullptr;
+    void* diff_d = nullptr;
+    uint64_t diff_pairs = 0;
 
     // bf16 shadow (index_shadow.hip; null = off).  Its certified / fallback counts outlive it: they live on the handle.
     cqs_idx::Shadow* shadow = nullptr;
@@ -218,6 +226,7 @@ int32_t update_entries(cqs_hip_index* x, const uint32_t* local, uint64_t local_o
                        const float* vectors);
 void update_free(cqs_hip_index* x);
 void knn_free(cqs_hip_index* x);   // the staging of cqs_hip_index_knn_graph (index_knn.hip)
+void diff_free(cqs_hip_index* x);  // the staging of cqs_hip_index_diff (index_diff.hip)
 bool shadow_takes(const cqs_hip_index* x, uint32_t b, uint32_t k, bool gemv_only);
 bool shadow_uses_i8(const cqs_hip_index* x, uint32_t b, uint32_t k);   // of a block shadow_takes: the int8 copy serves it
 int32_t shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k, const uint32_t* d_keep, uint32_t mode,

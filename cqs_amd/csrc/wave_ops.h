@@ -93,5 +93,12 @@ __device__ __forceinline__ float wave_sum64_shfl(float v) {
     for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
 }
+// the same butterfly over f64 (two ds_bpermute a step): every lane ends with the same bits, v[l] + v[l ^ off] being the
+// same addition in both partners.  index_diff.hip's three sums add in this order; diff_host.h restates it on 64 host slots.
+__device__ __forceinline__ double wave_sum64_shfl(double v) {
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
+    return v;
+}
 }  // namespace cqs
 #endif

@@ -56,6 +56,82 @@ class IndexResult:
     score: float
 
 
+@dataclass
+class DiffEntry:
+    """`DiffEntry` (src/diff.rs) by chunk id; `similarity` is the f32 cosine, None where there is none to give."""
+
+    id: str
+    similarity: Optional[float]
+
+
+@dataclass
+class DiffResult:
+    """`DiffResult` (src/diff.rs:238-245)."""
+
+    added: List[DiffEntry]
+    removed: List[DiffEntry]
+    modified: List[DiffEntry]
+    unchanged_count: int
+
+
+@dataclass
+class DriftEntry:
+    """`DriftEntry` (src/drift.rs:12-25)."""
+
+    id: str
+    similarity: float
+    drift: float
+
+
+@dataclass
+class DriftResult:
+    """`DriftResult` (src/drift.rs:27-42)."""
+
+    threshold: float
+    min_drift: float
+    drifted: List[DriftEntry]
+    total_compared: int
+    unchanged: int
+
+
+def _total_order_key(x: float) -> int:
+    """f32 -> int in the order of Rust's `f32::total_cmp`."""
+    b = int(np.float32(x).view(np.uint32))
+    return b ^ (0xFFFFFFFF if b >> 31 else 0x80000000)
+
+
+def match_ids(source_ids: Sequence[str], target_ids: Sequence[str], key: Optional[Callable[[str], object]] = None):
+    """The matching of `semantic_diff` (src/diff.rs:130-170) over two id lists in row order.  Returns (added: target rows
+    whose key the source lacks; removed: source rows whose key the target lacks; matched: [(source row, target row)]).
+    Of several rows with one key the last stands for the key, on each side."""
+    key = key or (lambda cid: cid)
+    src = {key(cid): i for i, cid in enumerate(source_ids)}
+    tgt = {key(cid): i for i, cid in enumerate(target_ids)}
+    added = [i for k, i in tgt.items() if k not in src]
+    removed = [i for k, i in src.items() if k not in tgt]
+    matched = [(src[k], i) for k, i in tgt.items() if k in src]
+    return added, removed, matched
+
+
+def sort_modified(entries: Sequence[DiffEntry]) -> List[DiffEntry]:
+    """src/diff.rs:226-236: most changed first (similarity ascending under the f32 total order), entries without a
+    similarity behind every entry with one, ties by id."""
+    return sorted(entries, key=lambda e: (e.similarity is None, 0 if e.similarity is None else _total_order_key(e.similarity), e.id))
+
+
+def drift_entries(modified: Sequence[DiffEntry], min_drift: float) -> List[DriftEntry]:
+    """src/drift.rs:73-101: entries without a similarity are skipped; drift = 1.0 - similarity in f32, kept where
+    drift >= min_drift; sorted by (drift descending under the f32 total order, id)."""
+    out = []
+    for e in modified:
+        if e.similarity is None:
+            continue
+        drift = np.float32(1.0) - np.float32(e.similarity)
+        if drift >= np.float32(min_drift):
+            out.append(DriftEntry(e.id, float(np.float32(e.similarity)), float(drift)))
+    return sorted(out, key=lambda d: (-_total_order_key(d.drift), d.id))
+
+
 class HipError(RuntimeError):
     def __init__(self, code: int, msg: str):
         super().__init__(f"cqs_hip error {code}: {msg}")
@@ -718,6 +794,64 @@ class HipIndex(VectorIndex):
         rows, scores, counts = self.knn_graph_rows(limit)
         return [[IndexResult(self._id(int(rows[i, j])), float(scores[i, j])) for j in range(int(counts[i]))]
                 for i in range(rows.shape[0])]
+
+    # ---- semantic diff of two resident indexes (src/diff.rs:99-246, src/drift.rs:51-120) ------------
+    def diff_rows(self, other: "HipIndex", rows_a, rows_b, threshold: float, want_sims: bool = False):
+        """`cqs_hip_index_diff`: pair i is (stored row `rows_a[i]` of this index, stored row `rows_b[i]` of `other`), global
+        row ids.  Returns (mod_pairs u64: the indices of the pairs with sim < threshold, ascending; mod_sims f32: their
+        sims; counts u64 [3]: modified, unchanged, undefined[; sims f32 [m] with `want_sims`]).  Raises HipError (INVALID:
+        a row outside its index, different dims or devices, a sharded handle, a NaN threshold)."""
+        ra = np.ascontiguousarray(rows_a, dtype=np.uint64).reshape(-1)
+        rb = np.ascontiguousarray(rows_b, dtype=np.uint64).reshape(-1)
+        if ra.shape[0] != rb.shape[0]:
+            raise ValueError("one row of each index per pair")
+        m = ra.shape[0]
+        mod_pairs = np.zeros((m,), dtype=np.uint64)
+        mod_sims = np.zeros((m,), dtype=np.float32)
+        counts = np.zeros((3,), dtype=np.uint64)
+        sims = np.zeros((m,), dtype=np.float32) if want_sims else None
+        rc = self._lib.cqs_hip_index_diff(self._h, _ptr(ra), other._h, _ptr(rb), m, float(threshold), _ptr(sims),
+                                          _ptr(mod_pairs), _ptr(mod_sims), _ptr(counts))
+        if rc != _lib.OK:
+            raise HipError(rc, self.last_error())
+        c = int(counts[0])
+        out = (mod_pairs[:c], mod_sims[:c], counts)
+        return out + (sims,) if want_sims else out
+
+    def _all_ids(self) -> List[str]:
+        """The id of every stored row, in row order."""
+        if self.id_map is not None:
+            return self.id_map
+        base = self._row_base()
+        return [str(base + i) for i in range(len(self))]
+
+    def _row_base(self) -> int:
+        return int(self._lib.cqs_hip_index_row_base(self._h))
+
+    def semantic_diff(self, other: "HipIndex", threshold: float, key: Optional[Callable[[str], object]] = None) -> "DiffResult":
+        """`semantic_diff(source_store, target_store, .., threshold, ..)` (src/diff.rs:99-246) with this index as the source
+        and `other` as the target.  Ids are matched by `key(id)` (default: the id itself; the reference's ChunkKey is
+        (file, name, chunk_type) without the line); of several ids with one key the last wins (:130-137).  `added`: in
+        the target only; `removed`: in the source only; matched pairs go through `diff_rows`: `modified` holds the
+        target's id and the similarity of those below the threshold, sorted by (similarity under the f32 total order
+        ascending, entries without a similarity last, id) (:226-236); `unchanged_count` the rest.  Matching and sorting
+        are string work and stay on the host; the cosines are computed where the rows lie."""
+        src, tgt = self._all_ids(), other._all_ids()
+        added, removed, matched = match_ids(src, tgt, key)
+        ra = np.asarray([s for s, _ in matched], dtype=np.uint64) + np.uint64(self._row_base())
+        rb = np.asarray([t for _, t in matched], dtype=np.uint64) + np.uint64(other._row_base())
+        mod_pairs, mod_sims, counts = self.diff_rows(other, ra, rb, threshold)[:3]
+        modified = [DiffEntry(tgt[matched[int(p)][1]], float(s)) for p, s in zip(mod_pairs, mod_sims)]
+        return DiffResult([DiffEntry(tgt[t], None) for t in added], [DiffEntry(src[s], None) for s in removed],
+                          sort_modified(modified), int(counts[1]))
+
+    def detect_drift(self, other: "HipIndex", threshold: float, min_drift: float) -> "DriftResult":
+        """`detect_drift(ref_store, project_store, .., threshold, min_drift, ..)` (src/drift.rs:51-120) with this index as the
+        reference and `other` as the project: the modified entries of `semantic_diff` as drift = 1.0 - similarity in f32,
+        kept where drift >= min_drift, sorted by (drift descending, id)."""
+        diff = self.semantic_diff(other, threshold)
+        return DriftResult(float(threshold), float(min_drift), drift_entries(diff.modified, min_drift),
+                           len(diff.modified) + diff.unchanged_count, diff.unchanged_count)
 
     # ---- cosine MMR over the resident rows (src/search/mmr.rs:59-126) ------------
     def pairwise_rows(self, rows) -> np.ndarray:

@@ -283,6 +283,42 @@ int32_t cqs_hip_index_neighbors(cqs_hip_index* idx, uint64_t target_row, uint32_
 int32_t cqs_hip_index_knn_graph(cqs_hip_index* idx, uint64_t first_row, uint64_t m, uint32_t limit,
                                 uint64_t* out_rows, float* out_scores, uint32_t* out_counts);
 
+/* ---- semantic diff of two resident indexes --------------------------------------
+ * The arithmetic of `semantic_diff` (src/diff.rs:99-246; `detect_drift`, src/drift.rs:51-120, sits on it): for every
+ * chunk present in both stores the reference fetches both embeddings from SQLite in batches of 1000, computes
+ * `full_cosine_similarity` (src/math.rs:35-67) and keeps the pairs below a threshold.  Here both corpora are resident:
+ * the rows are read where they lie in HBM and only the answer crosses the bus.  Matching chunks and sorting the result
+ * are string work and stay with the caller.
+ * Pair i is (stored row rows_a[i] of `a`, stored row rows_b[i] of `b`), both GLOBAL row ids (row_base included, as
+ * neighbors / remove / update take them); order is free and a row may appear in any number of pairs.  `a == b` is
+ * allowed, and so are borrowing handles (rows are only read).
+ * Per pair, exactly src/diff.rs:191-202: sim = full_cosine_similarity(row_a, row_b).unwrap_or(0.0) - dot and both squared
+ * norms accumulated in f64 from the f32 rows, denom = sqrt(na) * sqrt(nb); denom == 0 or a non-finite f32 result means
+ * "undefined": sim is 0.0f and the pair counts in out_counts[2].  The pair is modified iff sim < threshold (an f32
+ * compare), else unchanged; an undefined pair is classified through its 0.0 like any other, as the reference does.
+ * out_sims      [m] host, nullable: sim of pair i.  NULL: only the modified list and the counts cross the bus.
+ * out_mod_pairs [m] host, nullable: the pair indices of the modified pairs in ascending order, out_counts[0] of them;
+ * out_mod_sims  [m] host, nullable: their sims in the same order.  Both or neither.  Slots past the count are untouched.
+ * out_counts    [3] host: modified, unchanged, undefined; out_counts[0] + out_counts[1] == m.
+ * A pair's sim depends on its two rows and dim only - not on m, the pair's position, the passes or the grid - and
+ * sim(x, y) and sim(y, x) are the same bits.  Against the reference's left-to-right f64 loop the three sums differ by at
+ * most ~dim * 2^-53 relative, so the f32 result is the reference's or an adjacent f32; where the three sums are exact
+ * and the squared norms perfect squares it is the reference's bits.
+ * Refused with CQS_HIP_ERR_INVALID, all outputs untouched, neither handle poisoned and the reason in `a`'s last_error,
+ * in this order: a NULL a or b; (m == 0 returns CQS_HIP_OK here: out_counts = {0,0,0} if non-NULL, nothing else
+ * touched); NULL rows_a, rows_b or out_counts; exactly one of out_mod_pairs / out_mod_sims NULL; a NaN threshold (a
+ * stated departure: the reference's `sim < NaN` makes every pair unchanged); either handle row-sharded; the handles on
+ * different devices; dim(a) != dim(b) (a stated departure: the reference scores such pairs 0.0); any row outside its
+ * index (the text names the first offending pair index and which side).  A poisoned handle on either side ->
+ * CQS_HIP_ERR_POISONED.  A device failure poisons `a` only.
+ * The call holds BOTH handles' mutexes for its whole length (taken in address order, once when a == b) and orders its
+ * launches after the last search of each: searches and maintenance on either handle wait for it.  Work runs in passes of
+ * at most 2^20 pairs; a first call makes a staging block of 24 bytes per pair of the largest pass seen, pinned and on the
+ * device, which `a` keeps until destroy.  A handle that never calls diff pays nothing. */
+int32_t cqs_hip_index_diff(cqs_hip_index* a, const uint64_t* rows_a, cqs_hip_index* b, const uint64_t* rows_b,
+                           uint64_t m, float threshold, float* out_sims, uint64_t* out_mod_pairs, float* out_mod_sims,
+                           uint64_t* out_counts);
+
 /* ---- cosine MMR re-rank of a candidate pool ------------------------------------
  * The reference diversifies its top-K pool with `mmr_rerank` (src/search/mmr.rs:59-126) over a surface-feature
  * similarity, because it drops the embeddings after scoring: "embedding-MMR is a follow-up" (mmr.rs:30-37,

@@ -70,6 +70,10 @@ extern "C" {
                                out_scores: *mut f32, out_count: *mut u32) -> i32;
     fn cqs_hip_index_knn_graph(idx: *mut CqsHipIndex, first_row: u64, m: u64, limit: u32, out_rows: *mut u64,
                                out_scores: *mut f32, out_counts: *mut u32) -> i32;
+    // semantic diff of two resident indexes (src/diff.rs:172-215: full_cosine_similarity of matched pairs, the threshold)
+    fn cqs_hip_index_diff(a: *mut CqsHipIndex, rows_a: *const u64, b: *mut CqsHipIndex, rows_b: *const u64, m: u64,
+                          threshold: f32, out_sims: *mut f32, out_mod_pairs: *mut u64, out_mod_sims: *mut f32,
+                          out_counts: *mut u64) -> i32;
     // cosine MMR over the resident rows (src/search/mmr.rs:59-126 with the stored rows' dot as `similarity`)
     fn cqs_hip_index_pairwise(idx: *mut CqsHipIndex, cand_rows: *const u64, m: u32, out: *mut f32) -> i32;
     fn cqs_hip_index_mmr(idx: *mut CqsHipIndex, cand_rows: *const u64, cand_scores: *const f32, m: u32, limit: u32,
@@ -632,6 +636,34 @@ impl HipIndex {
             first += m;
         }
         Some(graph)
+    }
+
+    /// The embedding loop of `semantic_diff` (src/diff.rs:172-215) for matched pairs of two resident indexes: pair i is
+    /// (row `rows_a[i]` of `self`, row `rows_b[i]` of `other`), rows being `id_map` positions.  Returns the modified
+    /// pairs as (pair index, similarity) in ascending pair index - `sim < threshold` with
+    /// `sim = full_cosine_similarity(..).unwrap_or(0.0)` - and the unchanged count; matching ChunkKeys before and sorting
+    /// `modified` after (diff.rs:130-170, :226-236) stay with the caller.  `None` = the device failed, the handles do
+    /// not go together (dim, device, sharding) or the threshold is NaN: the caller keeps its SQLite loop.
+    pub fn semantic_diff_rows(&self, other: &HipIndex, rows_a: &[u64], rows_b: &[u64], threshold: f32)
+                              -> Option<(Vec<(usize, f32)>, usize)> {
+        if rows_a.len() != rows_b.len() {
+            return None;
+        }
+        let m = rows_a.len();
+        let (mut pairs, mut sims, mut counts) = (vec![0u64; m], vec![0f32; m], [0u64; 3]);
+        let rc = unsafe {
+            cqs_hip_index_diff(self.handle, rows_a.as_ptr(), other.handle, rows_b.as_ptr(), m as u64, threshold,
+                               std::ptr::null_mut(), pairs.as_mut_ptr(), sims.as_mut_ptr(), counts.as_mut_ptr())
+        };
+        if rc != CQS_HIP_OK {
+            if unsafe { cqs_hip_index_poisoned(self.handle) } != 0 {
+                self.poisoned.store(true, Ordering::Release);
+            }
+            tracing::warn!(error = %self.last_error(), rc, "HIP semantic diff failed");
+            return None;
+        }
+        let modified = (0..counts[0] as usize).map(|i| (pairs[i] as usize, sims[i])).collect();
+        Some((modified, counts[1] as usize))
     }
 
     /// `mmr_rerank` (src/search/mmr.rs:59-126) over `(chunk id, relevance)` candidates of this index, in the caller's
