@@ -10,7 +10,7 @@
 namespace cqs {
 
 typedef __bf16 bf16_t;
-// the vector types of the embedding-side kernel files (embed_*, gemm_*, query_kernels, bert_kernels)
+// the vector types of the embedding-side kernel files (embed_*, gemm_*, query_*, bert_kernels)
 typedef __bf16 bf8 __attribute__((ext_vector_type(8)));
 typedef __bf16 bf4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
@@ -179,7 +179,7 @@ hipError_t launch_attention(const bf16_t* qkv, const bf16_t* vt, bf16_t* out, co
 hipError_t launch_mean_pool(const float* hidden, const int32_t* seq_start, const int32_t* seq_len, bf16_t* pooled,
                             uint32_t B, uint32_t H, hipStream_t st);
 
-// ---- the search-time forward (query_kernels.hip): ONE sequence of <= 64 tokens, 5 launches per layer + 2 for the head ----
+// ---- the search-time forward (query_forward.hip): ONE sequence of <= 128 tokens, 4-5 launches per layer + 2 for the head ----
 struct QueryFwdLayer {
     const bf16_t *wqkv, *wo, *wgu, *wd;
     const float *n_in, *n_post_attn, *n_pre_ffw, *n_post_ffw, *n_q, *n_k;
@@ -202,7 +202,7 @@ struct QueryFwd {
     float *x0, *x1;
     bf16_t *qkv, *attn, *y, *h, *d1;
     float* out;
-    unsigned long long* dbg;          // nullable: [5 layers + 2 kernel slots][256 workgroups][8] diagnostic stamps (query_kernels.hip)
+    unsigned long long* dbg;          // nullable: [5 layers + 2 kernel slots][256 workgroups][8] diagnostic stamps (query_device.h)
 };
 constexpr uint32_t kQueryFwdMaxTokens = 128;
 bool query_forward_supported(const EmbedGeom& g);
@@ -212,7 +212,7 @@ hipError_t launch_query_forward(const QueryFwd& f, hipStream_t st);
 // f32 -> bf16 (round to nearest even), n elements
 hipError_t launch_f32_to_bf16(const float* in, bf16_t* out, size_t n, hipStream_t st);
 
-// C[M, N] = act(A W^T + bias) for M <= 64 rows through the search-time GEMM kernels (query_kernels.hip): N % 8 == 0,
+// C[M, N] = act(A W^T + bias) for M <= 64 rows through the search-time GEMM kernels (query_gemm.hip): N % 8 == 0,
 // K % 128 == 0, out in {BF16, BF16_GELU, F32}; hipErrorNotSupported otherwise (the caller falls back to launch_gemm_bias's
 // other kernels).  Not bit-identical to them: K is split over a workgroup's four waves.
 hipError_t launch_gemm_small_rows(const bf16_t* A, const bf16_t* W, const float* bias, void* C, uint32_t M, uint32_t N,

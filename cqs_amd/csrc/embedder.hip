@@ -95,7 +95,7 @@ struct cqs_hip_embedder {
         uint32_t xch_tag = 0;  // sequence number of the last launch that used xch (the granules' tag; never 0)
         int32_t *d_tok = nullptr, *d_pos = nullptr, *d_seq_start = nullptr, *d_seq_len = nullptr,
                 *d_vt_start = nullptr, *d_blk = nullptr;
-        // search-time path (query_kernels.hip): fixed 64-row scratch, allocated once and never moved, so that the
+        // search-time path (query_forward.hip): fixed 64-row scratch, allocated once and never moved, so that the
         // captured graphs' kernel arguments stay valid; the token ids arrive in q_meta by one H2D per query
         int32_t* q_meta = nullptr;
         int32_t* q_pos = nullptr;          // [kQueryFwdMaxTokens] = 0, 1, 2, ...
@@ -391,7 +391,7 @@ int32_t run_layers(cqs_hip_embedder* e, Ctx& c, Slot& sl) {
 }
 
 // ---- the search-time path: ONE sequence of <= 64 tokens (`embed_query`, src/embedder/core.rs:768-856) ---------------
-// 98 launches (4 per layer + 2) of query_kernels.hip instead of the batch chain's ~230, replayed from a hipGraph
+// 98 launches (4 per layer + 2) of query_forward.hip instead of the batch chain's ~230, replayed from a hipGraph
 // captured on the context's second query (eager launches of 2-3 us kernels are host-bound: ~3.5 us of host time each).
 bool slot_takes_query_path(const cqs_hip_embedder* e, const Slot& sl) {
     return e->query_path && sl.B == 1 && sl.M >= 1 && sl.M <= e->query_max_tokens;

@@ -2,7 +2,7 @@
 shadow_emul.py): the per-token measures, their committed bounds, the oracle-side recording through
 `gemma3_ref.forward(tap=...)`, the planted errors, and a bf16-operand emulation of a correct device.
 
-The search-time chain (cqs_amd/csrc/query_kernels.hip) pools its token rows on the device; a mean over T tokens divides
+The search-time chain (cqs_amd/csrc/query_forward.hip) pools its token rows on the device; a mean over T tokens divides
 a one-row error by about T, which is why the pooled-vector bounds of test_query_path_gpu.py (cos > 0.999) let every
 error below through except the window ones.  Here each token row is compared on its own."""
 import math
@@ -21,7 +21,7 @@ FULL_W32 = G.GemmaConfig(vocab_size=4096, hidden=768, layers=4, heads=3, kv_head
                          dense_hidden=3072, sliding_window=32, sliding_pattern=2, max_seq=2048)
 GEOMS = {"small": (SMALL, 31), "full": (FULL, 35), "full_w32": (FULL_W32, 35)}
 
-# every length where a launcher in query_kernels.hip changes form, and one on either side of each ...
+# every length where a plan of cqs_amd/csrc/query_plan.h changes form (tests/test_query_plan_cpu.py holds the two together), and one on either side of each ...
 BREAKS = [1, 4, 5, 8, 9, 16, 17, 32, 33, 48, 49, 64, 65, 80, 81, 96, 97, 128]
 # ... and partly filled last blocks: T % 8 and T % 16 zero and non-zero inside every class
 PARTIAL = [2, 3, 7, 12, 13, 24, 27, 40, 43, 56, 59, 72, 75, 88, 91, 104, 112, 123]

@@ -1,4 +1,4 @@
-"""The search-time chain (cqs_amd/csrc/query_kernels.hip) token by token.  tests/test_query_path_gpu.py compares the POOLED
+"""The search-time chain (cqs_amd/csrc/query_forward.hip) token by token.  tests/test_query_path_gpu.py compares the POOLED
 sentence vector; a mean over T tokens divides what a kernel gets wrong on one row - a partly filled row block, the last
 key of a tile, the seam between the key halves, the window compare, which of x0 / x1 holds the residual - by about T.
 Here the test hook `cqs_hip_debug_embedder_query_state` reads the chain's per-token state off the device after a blocking
