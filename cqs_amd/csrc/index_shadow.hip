@@ -52,6 +52,9 @@ struct Shadow {
                                           // f32 fallback is always the gated scan + select pair
     bool tail_prefix = true;              // CQS_HIP_TAIL_PREFIX, read when the shadow is built: 0 = the tail kernel's finisher always
                                           // sorts every candidate at once (the A/B arm and the tests' reference; same answers)
+    uint8_t i8_groups = 2;                // CQS_HIP_I8_GROUPS, read when the shadow is built: 0 = the int8 scan publishes one maximum per
+                                          // task, as the other scans do (the A/B arm and the tests' reference); 1 = one per workgroup of
+                                          // four tasks in every int8 block; unset = where that pays (shadow_group_tasks).  Same answers
     uint32_t* h_cert = nullptr;           // pinned [kShadowMaxQ]
     uint32_t* h_cert_dev = nullptr;       // its device-visible address (null: not mappable)
 };
@@ -264,6 +267,8 @@ static int32_t shadow_enable(cqs_hip_index* x, const char* what) {
     s->fb_one_launch = !(fb_env && fb_env[0] == '0');
     const char* tp_env = getenv("CQS_HIP_TAIL_PREFIX");
     s->tail_prefix = !(tp_env && tp_env[0] == '0');
+    const char* ig_env = getenv("CQS_HIP_I8_GROUPS");
+    s->i8_groups = ig_env && ig_env[0] == '0' ? 0 : (ig_env && ig_env[0] == '1' ? 1 : 2);
     if ((e = hipMalloc(&s->d_fb_lists, cqs::f32_topk_fallback_words(x->n_cu) * sizeof(uint64_t))) != hipSuccess) return oom(e);
     if ((e = hipMalloc(&s->d_fb_tickets, (size_t)cqs::kMaxGemvQ * sizeof(uint32_t))) != hipSuccess) return oom(e);
     if ((e = hipMemsetAsync(s->d_fb_tickets, 0, (size_t)cqs::kMaxGemvQ * sizeof(uint32_t), x->stream)) != hipSuccess) return oom(e);
@@ -363,6 +368,20 @@ bool shadow_uses_i8(const cqs_hip_index* x, uint32_t b, uint32_t k) {
     return x->shadow && x->shadow->d_i8 && b <= cqs::kI8MaxQ && cqs::i8_k_ok(k);
 }
 
+// Tasks per entry of the shadow scan's gmax / gaux (ScanArgs::group_tasks): 4, the int8 scan's workgroup maxima, where they
+// pay.  They take 4 us off the select's walk over the maxima whatever k' is, and cost a gather that grows with k'^2 / n: a
+// listed group of up to 256 rows holds a second entry at or above the threshold bin four times as often as a task of 64, and
+// then all four of its tasks are read, 128 to a round trip - about 4 * 255 * (k' + 1)^2 / n tasks.  Measured at 1M rows
+// ("Workgroup maxima"): -2.4 to -2.9 us per search at k' + 1 = 351, +8 at 1021; the rule keeps the estimate
+// under two round trips.
+static uint32_t shadow_group_tasks(const cqs_hip_index* x, bool i8, uint32_t kp) {
+    const Shadow* s = x->shadow;
+    if (!i8 || s->i8_groups == 0) return 1u;
+    if (s->i8_groups == 1) return cqs::kMaxGroupTasks;
+    const uint64_t kk = (uint64_t)kp + 1u;
+    return 4u * kk * kk <= pad_rows(x->n) ? cqs::kMaxGroupTasks : 1u;
+}
+
 // The shadow half of a gemv block on `st`: shadow scan -> one tail launch (select k' + 1, B_q, rescore, certify) into
 // out_keys / out_counts.  PIPELINE searches alone launch the bound kernel first: only their scan reads B_q (its drop rule).
 // device_gate (device-API searches): `st` is ordered after the last search here, certify counts outcomes on the device,
@@ -389,7 +408,8 @@ int32_t shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k,
     }
     // gemv passes over the copy's rows (non-uniform tiers, no debug stamps), top k' + 1; the select's (argmax, runner-up)
     // index from kGauxMinK on whatever CQS_HIP_SELECT_AUX says (that A/B hook is the f32 select's)
-    const cqs::ScanArgs a = scan_args(x, d_q, nb, kp + 1u, d_keep, mode, threshold, i8 ? sizeof(int8_t) : sizeof(uint16_t), true, nullptr, nullptr, tab);
+    cqs::ScanArgs a = scan_args(x, d_q, nb, kp + 1u, d_keep, mode, threshold, i8 ? sizeof(int8_t) : sizeof(uint16_t), true, nullptr, nullptr, tab);
+    a.group_tasks = shadow_group_tasks(x, i8, kp);   // (the scan publishes, the tail kernel's select walks: one maximum per that many tasks)
     const ShadowRows rows{i8 ? nullptr : s->d_bf16, i8 ? s->d_i8 : nullptr, s->d_i8_scale, s->d_bq};
     const int32_t rc = scan_select(x, a, st, &rows, nullptr, nullptr);   // (the scan alone: the tail kernel selects)
     if (rc == CQS_HIP_OK)
@@ -659,7 +679,8 @@ int32_t cqs_hip_debug_shadow_scores(cqs_hip_index* x, uint32_t copy, const float
         const cqs::ScanArgs a = scan_args(x, x->d_q, b, k, d_keep, mode, threshold, sizeof(float), false, x->d_dbg, nullptr);
         HIP_TRY(x, cqs::launch_scan(a, st));
     } else {
-        const cqs::ScanArgs a = scan_args(x, x->d_q, b, k_scan, d_keep, mode, threshold, i8 ? sizeof(int8_t) : sizeof(uint16_t), true, nullptr, nullptr);
+        cqs::ScanArgs a = scan_args(x, x->d_q, b, k_scan, d_keep, mode, threshold, i8 ? sizeof(int8_t) : sizeof(uint16_t), true, nullptr, nullptr);
+        a.group_tasks = shadow_group_tasks(x, i8, kp);
         if (i8) HIP_TRY(x, cqs::launch_scan_i8(a, s->d_i8, s->d_i8_scale, s->d_bq, st));
         else HIP_TRY(x, cqs::launch_scan_bf16(a, s->d_bf16, s->d_bq, st));
     }

@@ -314,7 +314,7 @@ static hipError_t launch_bf16_groups(const ScanArgs& a, const uint16_t* shadow, 
 
 hipError_t launch_scan_bf16(const ScanArgs& a, const uint16_t* shadow, const float* bq, hipStream_t st) {
     if (a.b == 0 || a.n == 0) return hipSuccess;
-    if (a.b > kShadowMaxQ || a.dim % 8u != 0u || a.dim > kShadowMaxDim) return hipErrorInvalidValue;
+    if (a.b > kShadowMaxQ || a.dim % 8u != 0u || a.dim > kShadowMaxDim || a.group_tasks != 1u) return hipErrorInvalidValue;
     if (a.keep_tab && !keep_tab_ok(a)) return hipErrorInvalidValue;
     switch ((a.dim + 511u) / 512u) {
         case 1: return a.keep_tab ? launch_bf16_groups<1, true>(a, shadow, bq, st) : launch_bf16_groups<1, false>(a, shadow, bq, st);
@@ -332,10 +332,11 @@ struct TailParams {
     uint32_t dim, k, kprime, mode, row_base;
     float thr;
     const float* scores;       // [b, n_pad]   the shadow scan's output (an earlier launch): approximate scores,
-    const float* gmax;         // [b, n_tasks] task maxima,
-    const uint64_t* gaux;      // nullable [b, n_tasks] (argmax, runner-up)
+    const float* gmax;         // [b, n_groups] maxima of the scan's groups (GroupMap{tiers, group_tasks}),
+    const uint64_t* gaux;      // nullable [b, n_groups] (argmax, runner-up)
     uint32_t n_pad;
     TaskTiers tiers;
+    uint32_t group_tasks;      // ScanArgs::group_tasks: 1, or 4 behind the int8 scan's workgroup maxima
     uint32_t bins;             // select_body's `linear`
     uint32_t* work;            // [kWorkWords] the scans' work-queue heads: zeroed here, as the select launch did
     uint64_t* ekeys;           // [b, k']: exact key of candidate i, 0 = dropped by the f32 epilogue.  Handed from the
@@ -400,10 +401,11 @@ __global__ __launch_bounds__(1024) void rescore_certify_kernel(const TailParams 
     if (qi == 0u && blockIdx.x == 0u)
         for (uint32_t i = threadIdx.x; i < kWorkWords; i += 1024u) p.work[i] = 0u;
     // the approximate top k' + 1, sorted: what select_finish_kernel wrote to akeys / acounts when it was a launch of its own
-    const uint32_t n_tasks = p.tiers.total();
+    const GroupMap map{p.tiers, p.group_tasks};
+    const uint32_t n_groups = map.total();
     uint32_t found;
-    const uint64_t* akeys = select_body(p.scores + (size_t)qi * p.n_pad, p.gmax + (size_t)qi * n_tasks,
-                                        p.gaux ? p.gaux + (size_t)qi * n_tasks : nullptr, p.n_pad, p.tiers, p.kprime + 1u,
+    const uint64_t* akeys = select_body(p.scores + (size_t)qi * p.n_pad, p.gmax + (size_t)qi * n_groups,
+                                        p.gaux ? p.gaux + (size_t)qi * n_groups : nullptr, p.n_pad, map, p.kprime + 1u,
                                         p.row_base, p.bins, DBG ? dbg : nullptr, found);
     found = (uint32_t)__builtin_amdgcn_readfirstlane((int)found);   // (workgroup-uniform: a scalar from here on)
     const uint32_t ac = found < p.kprime + 1u ? found : p.kprime + 1u;
@@ -541,9 +543,9 @@ hipError_t launch_rescore_certify(const ScanArgs& a, uint32_t row_base, uint32_t
     const uint32_t b = a.b, dim = a.dim;
     if (b == 0) return hipSuccess;
     if (b > kShadowMaxQ || k == 0 || kprime < k || kprime >= kShadowKMax || a.k != kprime + 1u || dim % 8u != 0u ||
-        dim > kShadowMaxDim || bound > 2u)
+        dim > kShadowMaxDim || bound > 2u || (a.group_tasks != 1u && a.group_tasks != kMaxGroupTasks))
         return hipErrorInvalidValue;
-    const TailParams tp{a.rows, a.q, dim, k, kprime, a.mode, row_base, a.threshold, a.scores, a.gmax, a.gaux, a.n_pad, a.tiers,
+    const TailParams tp{a.rows, a.q, dim, k, kprime, a.mode, row_base, a.threshold, a.scores, a.gmax, a.gaux, a.n_pad, a.tiers, a.group_tasks,
                         a.range_bins ? 2u : (a.linear_bins ? 1u : 0u), a.work, ekeys, bq, tickets, bound, r_max, norm_max,
                         out_keys, out_counts, cert, counters, counters2, prefix ? 1u : 0u, prefix_counts, dbg};
     // One wave per slot (B_q + k' candidates) while the block's workgroups fit the device in one round; beyond that

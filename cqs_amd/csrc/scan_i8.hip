@@ -5,6 +5,8 @@
 //  scan_i8_kernel    HBM-streaming dot of every int8 row with 1..4 f32 queries, times the row's scale: a quarter of the
 //                    bytes of scan_gemv_kernel.  scan_bf16_kernel's tasks, score + gmax (+ gaux) layout and one-sided
 //                    epilogue, so the unchanged select, rescore and certify follow it; one wave per task at every size.
+//                    ScanArgs::group_tasks = 4: the four waves of a workgroup publish ONE (maximum, argmax, runner-up)
+//                    triple for their four consecutive tasks (group_map.h), a quarter of the maxima for the select to walk.
 //
 // Wave = 64 lanes.  gfx950 only.
 #include "scan_i8.h"
@@ -73,7 +75,12 @@ struct I8ScanParams {
     const float* bq;        // [nq] B_q of each query of the pass (device)
     uint32_t keep_stride;   // PQ: `keep` is a table of bitsets, this many words per row ...
     uint8_t slot[kMaxGemvQ];// ... and query b of the pass is filtered by row slot[b] (ScanArgs::keep_tab)
+    uint32_t group_tasks;   // 1: gmax / gaux hold one entry per task.  kI8BlockWaves: one per workgroup = group of that many
+    uint32_t n_groups;      // consecutive tasks (GroupMap{tiers, group_tasks}), and this is their per-query stride
 };
+
+constexpr uint32_t kI8BlockWaves = 4;   // waves = consecutive tasks of a workgroup (= kMaxGroupTasks: the grouped form's G)
+static_assert(kI8BlockWaves == kMaxGroupTasks, "a workgroup of the int8 scan is one group of the select's map");
 
 // NCH = ceil(dim / 1024): 1-KiB chunks per row; lane owns components [c*1024 + lane*16, +16) of chunk c (one 16-byte load).
 // A partial last chunk (FULL = false, 768-d: lanes 48..63) reads a clamped in-row address against a zero query fragment, as
@@ -83,12 +90,24 @@ struct I8ScanParams {
 // 1M rows and 2.11 against 1.24 at 10M - both about 14 ns per dequeued task, whatever the blocks per CU,
 // which points at the one returning atomic per task on an address every XCD shares; this scan needs a task every 8 ns.
 // PQ: one keep-bitset per query, as in scan_gemv_kernel.
+// group_tasks = 4 (a uniform branch on the kernarg; 1 keeps the per-task stores as they were): each wave leaves its triple
+// per query in LDS and adds one to an arrival counter (workgroup scope, acq_rel); the wave whose add completes the count -
+// min(4, n_tasks - 4 blockIdx.x): waves past the last task leave at entry - combines the slots (combine_triples) and stores
+// the group's gmax / gaux entry.  Nobody waits at the end; the counter is zeroed behind the one barrier at entry, which
+// stands before the early return.  The stores are plain: their reader is the next launch.
 template <int NCH, int BQ, int RI, bool NT, bool FULL, bool PQ>
 __global__ __launch_bounds__(256) void scan_i8_kernel(const I8ScanParams p) {
     constexpr int NV = RI * BQ;
     constexpr int LPV = 64 / NV;
+    __shared__ float s_gmx[kI8BlockWaves][BQ], s_gsec[kI8BlockWaves][BQ];
+    __shared__ uint32_t s_garg[kI8BlockWaves][BQ], s_goff[kI8BlockWaves], s_arrive;
     const int lane = threadIdx.x & 63;
     const uint32_t n = p.n, dim = p.dim;
+    const bool grouped = p.group_tasks > 1u;
+    if (grouped) {
+        if (threadIdx.x == 0) s_arrive = 0u;
+        __syncthreads();
+    }
 
     uint32_t coff[NCH];
     f4 qv[BQ][NCH][4];
@@ -112,6 +131,7 @@ __global__ __launch_bounds__(256) void scan_i8_kernel(const I8ScanParams p) {
     const uint32_t nwords = (n + 31u) / 32u;
     const uint32_t n_tasks = p.n_tasks;
     const uint32_t wpb = blockDim.x >> 6;
+    const uint32_t wib = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t cur = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * wpb + (threadIdx.x >> 6)));
     if (cur >= n_tasks) return;
 
@@ -181,12 +201,51 @@ __global__ __launch_bounds__(256) void scan_i8_kernel(const I8ScanParams p) {
             if ((uint32_t)b >= p.nq) continue;
             if ((uint32_t)lane < trows && row < p.n_pad) p.scores[(size_t)b * p.n_pad + row] = s;
             const float gm = wave_max64(s);
+            if (grouped) {   // this wave's triple of query b into its LDS slot (no gaux: the maximum alone matters)
+                uint32_t arg = 0u;
+                float sec = -INFINITY;
+                if (p.gaux) {
+                    arg = (uint32_t)__builtin_ctzll(__ballot(s == gm));
+                    sec = wave_max64(((uint32_t)lane == arg) ? -INFINITY : s);
+                }
+                if (lane == 0) { s_gmx[wib][b] = gm; s_garg[wib][b] = arg; s_gsec[wib][b] = sec; }
+                continue;
+            }
             if (lane == 0) p.gmax[(size_t)b * n_tasks + cur] = gm;
             if (p.gaux) {
                 const uint32_t arg = (uint32_t)__builtin_ctzll(__ballot(s == gm));
                 const float sec = wave_max64(((uint32_t)lane == arg) ? -INFINITY : s);
                 if (lane == 0) p.gaux[(size_t)b * n_tasks + cur] = ((uint64_t)arg << 32) | (uint64_t)__float_as_uint(sec);
             }
+        }
+        if (!grouped) return;
+        // the hand-off: lane 0 has stored this wave's slots; its acq_rel add releases them and, for the wave that completes
+        // the count, acquires every other wave's
+        const uint32_t g = blockIdx.x;   // (= cur / kI8BlockWaves: the launch puts consecutive tasks into a workgroup)
+        uint32_t gr;
+        const uint32_t gbase = p.tiers.locate(g * kI8BlockWaves, gr);
+        uint32_t t = 0u;
+        if (lane == 0) {
+            s_goff[wib] = base - gbase;
+            t = __hip_atomic_fetch_add(&s_arrive, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP);
+        }
+        t = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
+        const uint32_t left = n_tasks - g * kI8BlockWaves;
+        const uint32_t expect = left < kI8BlockWaves ? left : kI8BlockWaves;
+        if (t + 1u != expect) return;
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");   // (every lane that reads the slots below)
+        if ((uint32_t)lane < p.nq) {   // lane b combines query b
+            MaxTriple w[kI8BlockWaves];
+            uint32_t off[kI8BlockWaves];
+#pragma unroll
+            for (uint32_t i = 0; i < kI8BlockWaves; ++i) {   // (a missing wave: -inf, which never wins and never raises the runner-up)
+                const bool there = i < expect;
+                w[i] = MaxTriple{there ? s_gmx[i][lane] : -INFINITY, there ? s_garg[i][lane] : 0u, there ? s_gsec[i][lane] : -INFINITY};
+                off[i] = there ? s_goff[i] : 0u;
+            }
+            const MaxTriple m = combine_triples(w, off, kI8BlockWaves);
+            p.gmax[(size_t)lane * p.n_groups + g] = m.max;
+            if (p.gaux) p.gaux[(size_t)lane * p.n_groups + g] = ((uint64_t)m.arg << 32) | (uint64_t)__float_as_uint(m.sec);
         }
     };
     auto task_mask = [&](uint32_t base, uint32_t trows) -> uint64_t {
@@ -253,7 +312,13 @@ static hipError_t launch_i8(const ScanArgs& a, const int8_t* codes, const float*
     fill_gemv_pass(p, a, q0, nq, PQ);
     p.rows = codes; p.scales = scales;
     p.bq = bq + q0;
-    const uint32_t wpb = 4u;
+    p.group_tasks = a.group_tasks;
+    p.n_groups = (p.n_tasks + a.group_tasks - 1u) / a.group_tasks;
+    if (a.group_tasks != 1u) {   // one entry per workgroup: the rows of gmax / gaux are that much shorter
+        p.gmax = a.gmax + (size_t)q0 * p.n_groups;
+        p.gaux = a.gaux ? a.gaux + (size_t)q0 * p.n_groups : nullptr;
+    }
+    const uint32_t wpb = kI8BlockWaves;
     const dim3 grid((p.n_tasks + wpb - 1u) / wpb), block(64u * wpb);
     const bool full = (a.dim == (uint32_t)NCH * 1024u);
     for_nt_full(a.nontemporal, full, [&](auto nt_c, auto full_c) {
@@ -280,7 +345,7 @@ static hipError_t launch_i8_groups(const ScanArgs& a, const int8_t* codes, const
 
 hipError_t launch_scan_i8(const ScanArgs& a, const int8_t* codes, const float* scales, const float* bq, hipStream_t st) {
     if (a.b == 0 || a.n == 0) return hipSuccess;
-    if (a.b > kShadowMaxQ || !i8_dim_ok(a.dim)) return hipErrorInvalidValue;
+    if (a.b > kShadowMaxQ || !i8_dim_ok(a.dim) || (a.group_tasks != 1u && a.group_tasks != kI8BlockWaves)) return hipErrorInvalidValue;
     if (a.keep_tab && !keep_tab_ok(a)) return hipErrorInvalidValue;
     switch ((a.dim + 1023u) / 1024u) {
         case 1: return a.keep_tab ? launch_i8_groups<1, true>(a, codes, scales, bq, st) : launch_i8_groups<1, false>(a, codes, scales, bq, st);

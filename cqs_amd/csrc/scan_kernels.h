@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "group_map.h"
 #include "wave_ops.h"   // wave_dpp, wave_max16, wave_max64: the scans' maxima
 
 namespace cqs {
@@ -20,20 +21,7 @@ constexpr uint32_t kDbgWaves = 4096;      // per-wave start/end stamps kept by t
 constexpr uint32_t kWorkWords = 64;       // work-queue heads (one per scan launch of a search); zero on entry,
                                           // re-zeroed by select_finish (a shadow search: by its tail kernel)
 
-// Work-queue tasks in row order: nA tasks of 64 rows, then nB of 32, then nC of 16 (64 nA + 32 nB +
-// 16 nC = n_pad).  One task = one wave's unit of work = one group of the select's maxima index.
-struct TaskTiers {
-    uint32_t nA, nB, nC;
-    __host__ __device__ uint32_t total() const { return nA + nB + nC; }
-    // first row and row count of task t
-    __host__ __device__ uint32_t locate(uint32_t t, uint32_t& rows) const {
-        if (t < nA) { rows = 64u; return t * 64u; }
-        if (t < nA + nB) { rows = 32u; return nA * 64u + (t - nA) * 32u; }
-        rows = 16u;
-        return nA * 64u + nB * 32u + (t - nA - nB) * 16u;
-    }
-};
-TaskTiers plan_tiers(uint32_t n_pad, uint32_t n_cu, bool uniform64);
+// TaskTiers (tasks in row order), plan_tiers and the GroupMap of the select's maxima index: group_map.h.
 
 struct ScanArgs {
     const float* rows;      // [n, dim] f32, row-major, HBM
@@ -59,6 +47,8 @@ struct ScanArgs {
                             // (written by the gemv scan and the sparse index; the matrix-core scan does not: its select
                             // launch ignores the field)
     TaskTiers tiers;        // plan_tiers(n_pad, n_cu, uniform_groups(b, dim))
+    uint32_t group_tasks = 1;   // tasks per entry of gmax / gaux (GroupMap::G): 1, or 4 for the int8 scan, whose workgroup
+                            // publishes one triple for its four tasks; gmax / gaux are then [b, ceil(tiers.total() / 4)]
     uint32_t* work;         // [kWorkWords] work-queue heads (zero on entry)
     uint32_t n_cu;          // compute units of the device
     bool gemv_only = false; // never the matrix-core kernel, whatever b: blocks of > 8 queries run as passes of <= 8

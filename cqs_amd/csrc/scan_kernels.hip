@@ -296,7 +296,7 @@ __global__ __launch_bounds__(1024) void select_finish_kernel(const float* __rest
     const uint32_t n_tasks = tiers.total();
     uint32_t count;
     const uint64_t* sorted = select_body(scores + (size_t)qi * n_pad, gmax + (size_t)qi * n_tasks,
-                                         gaux ? gaux + (size_t)qi * n_tasks : nullptr, n_pad, tiers, k, row_base, linear, dbg,
+                                         gaux ? gaux + (size_t)qi * n_tasks : nullptr, n_pad, GroupMap{tiers, 1u}, k, row_base, linear, dbg,
                                          count);
     const uint32_t outc = count < k ? count : k;
     for (uint32_t i = threadIdx.x; i < k; i += 1024u) out_keys[(size_t)qi * k + i] = (i < outc) ? sorted[i] : 0ull;
@@ -333,25 +333,7 @@ bool scan_dim_supported(uint32_t dim) { return dim >= 4 && dim % 4 == 0 && dim <
 #ifndef CQS_SCAN_BLOCKS_PER_CU
 #define CQS_SCAN_BLOCKS_PER_CU 2u   // persistent grid
 #endif
-#ifndef CQS_SCAN_TIER_B
-#define CQS_SCAN_TIER_B 2u   // 32-row tasks at the end of the corpus, in units of (n_cu * 4 / 2)
-#endif
 
-// Task sizes over the padded corpus (measured at 768-d, 1 query; MI355X, 256 CUs):
-//   < 8 64-row tasks per CU (<= 131k rows): 16-row tasks, so a 17.5k-row corpus still reaches every CU;
-//   otherwise 64-row tasks (8 batches of 8 rows: the double buffer's fill/drain is amortised), with the
-//   last two rounds' worth of 32-row tasks: the launch ends when its slowest wave does, and halving the
-//   final tasks halves that tail (-5 us of 460 at 1M rows).  16-row tail tasks cost more than they gain.
-TaskTiers plan_tiers(uint32_t n_pad, uint32_t n_cu, bool uniform64) {
-    TaskTiers t{0u, 0u, 0u};
-    const uint32_t n64 = n_pad / 64u, waves = n_cu * 4u;
-    if (uniform64) { t.nA = n64; return t; }  // matrix-core kernel: 64-row groups only
-    if (n64 < 8u * n_cu) { t.nC = n_pad / 16u; return t; }
-    const uint32_t nb = CQS_SCAN_TIER_B * (waves / 2u) & ~1u;
-    if (n64 >= 6u * waves && n64 > nb / 2u) { t.nA = n64 - nb / 2u; t.nB = nb; }
-    else t.nA = n64;
-    return t;
-}
 static uint32_t tier_slot_log2(const TaskTiers& t) { return t.nA ? 6u : (t.nB ? 5u : 4u); }
 
 template <int NCH, int BQ, int RI, bool PQ>
@@ -441,6 +423,7 @@ static hipError_t launch_gemv_groups(const ScanArgs& a, hipStream_t st) {
 
 hipError_t launch_scan(const ScanArgs& a, hipStream_t st) {
     if (a.b == 0 || a.n == 0) return hipSuccess;
+    if (a.group_tasks != 1u) return hipErrorInvalidValue;   // (one maximum per task: groups of tasks are the int8 scan's)
     if (a.gate && (a.b > 64u || (!a.gemv_only && use_mfma(a.b, a.dim)))) return hipErrorInvalidValue;   // gemv passes only
     if (!a.gemv_only && use_mfma(a.b, a.dim)) {
         if (a.keep_tab) return hipErrorInvalidValue;   // (per-query bitsets: gemv passes only)
@@ -492,7 +475,7 @@ hipError_t launch_scan(const ScanArgs& a, hipStream_t st) {
 hipError_t launch_select(const ScanArgs& a, uint32_t row_base, uint64_t* out_keys, uint32_t* out_counts,
                          hipStream_t st) {
     if (a.b == 0 || a.k == 0) return hipSuccess;
-    if (a.gate && a.b > 64u) return hipErrorInvalidValue;
+    if ((a.gate && a.b > 64u) || a.group_tasks != 1u) return hipErrorInvalidValue;
     hipLaunchKernelGGL(select_finish_kernel, dim3(a.b), dim3(1024), 0, st, a.scores, a.gmax,
                        (!a.gemv_only && use_mfma(a.b, a.dim)) ? nullptr : a.gaux, a.n_pad,
                        a.tiers, tier_slot_log2(a.tiers), a.k, row_base,

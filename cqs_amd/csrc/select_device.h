@@ -148,15 +148,86 @@ static __device__ uint32_t slow_select(const float* __restrict__ s, uint32_t n_p
 // are bandwidth- not latency-paced.
 constexpr uint32_t kGroupCap = 8192;
 constexpr int kGB = 16;  // independent loads in flight per thread
+constexpr int kGBShort = 4;  // ... where the maxima are one per group of several tasks (GroupMap::G > 1) and 4 096 slots hold them
+
+#define CQS_STAMP(i) do { if (dbg && threadIdx.x == 0 && blockIdx.x == 0) dbg[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
+
+// Phases 1 and 2 of select_body at GB slots per thread and trip: the histogram of the n_groups maxima gm[], the threshold
+// bin T (returned), and the list of the groups whose maximum reaches it (s_groups, their number in *s_ng).  Every slot is
+// a load, an LDS atomic, a ballot and an mbcnt whether or not a group stands behind it, so GB follows the number of groups
+// (select_body): 16 for a row of up to 16 384 task maxima, 4 where 4 096 groups cover it.
+template <int GB>
+__device__ __forceinline__ uint32_t select_front(const float* __restrict__ gm, uint32_t n_groups, uint32_t k, uint32_t linear,
+                                                 float r_lo, float r_scale, uint32_t* s_hist, uint32_t* s_part, uint32_t* s_res,
+                                                 uint32_t* s_ng, uint32_t* s_groups, unsigned long long* __restrict__ dbg) {
+    const int lane = threadIdx.x & 63;
+    // phase 1: histogram of the group maxima
+    float m[GB];
+    const bool one_pass = n_groups <= 1024u * GB;  // the maxima then stay in registers for phase 2
+    for (uint32_t t0 = 0; t0 < n_groups; t0 += 1024u * GB) {
+#pragma unroll
+        for (int u = 0; u < GB; ++u) {
+            const uint32_t t = t0 + (uint32_t)u * 1024u + threadIdx.x;
+            const float v = gm[t < n_groups ? t : n_groups - 1u];  // unconditional load, clamped
+            m[u] = t < n_groups ? v : -INFINITY;
+        }
+#pragma unroll
+        for (int u = 0; u < GB; ++u)
+            if (m[u] != -INFINITY) atomicAdd(&s_hist[bin_any(m[u], linear, r_lo, r_scale)], 1u);
+    }
+    __syncthreads();
+    CQS_STAMP(1);
+    block_decide<1024>(s_hist, k, s_part, s_res);
+    const uint32_t T = (s_res[3] < k) ? 0u : s_res[0];  // fewer groups than k: every valid score is a candidate
+    __syncthreads();
+    CQS_STAMP(2);
+
+    // phase 2: groups whose maximum reaches the threshold bin
+    for (uint32_t t0 = 0; t0 < n_groups; t0 += 1024u * GB) {
+        if (!one_pass) {
+#pragma unroll
+            for (int u = 0; u < GB; ++u) {
+                const uint32_t t = t0 + (uint32_t)u * 1024u + threadIdx.x;
+                const float v = gm[t < n_groups ? t : n_groups - 1u];
+                m[u] = t < n_groups ? v : -INFINITY;
+            }
+        }
+        // list positions by ballot + mbcnt, one LDS atomic per wave (round 5; until then a 6-step shuffle scan over 16 flags)
+        bool take[GB];
+        uint64_t mk[GB];
+        uint32_t pre[GB], tot = 0;
+#pragma unroll
+        for (int u = 0; u < GB; ++u) {
+            take[u] = (m[u] != -INFINITY) && (bin_any(m[u], linear, r_lo, r_scale) >= T);
+            mk[u] = __ballot(take[u]);
+            pre[u] = tot;
+            tot += (uint32_t)__popcll(mk[u]);
+        }
+        uint32_t base = 0;
+        if (tot) {                                       // wave-uniform
+            if (lane == 0) base = atomicAdd(s_ng, tot);
+            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
+        }
+#pragma unroll
+        for (int u = 0; u < GB; ++u) {
+            const uint32_t slot = base + pre[u] + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk[u] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk[u], 0u));
+            if (take[u] && slot < kGroupCap) s_groups[slot] = t0 + (uint32_t)u * 1024u + threadIdx.x;
+        }
+    }
+    __syncthreads();
+    CQS_STAMP(3);
+    return T;
+}
 
 // The select of one query by one workgroup of 1024 threads, up to the sorted candidates: s = the query's score row
-// [n_pad], gm / ga = its rows of the scan's gmax / gaux (ga nullable).  Returns the candidates sorted descending (LDS,
+// [n_pad], gm / ga = its rows of the scan's gmax / gaux (ga nullable), one entry per group of `map` (G = 1: per task; the
+// int8 scan's G = 4: per workgroup of four tasks).  Returns the candidates sorted descending (LDS,
 // valid until the workgroup's next use of this function) and their number in `count`, which may exceed k: the first
 // min(count, k) are the query's top k.  The LDS it needs is declared here, so every kernel that calls it carries it.
 // Every thread of the workgroup must call it (barriers inside); it writes nothing but LDS and the debug stamps.
 __device__ __forceinline__ const uint64_t* select_body(const float* __restrict__ s, const float* __restrict__ gm,
                                                        const uint64_t* __restrict__ ga, uint32_t n_pad,
-                                                       const TaskTiers& tiers, uint32_t k, uint32_t row_base,
+                                                       const GroupMap& map, uint32_t k, uint32_t row_base,
                                                        uint32_t linear, unsigned long long* __restrict__ dbg,
                                                        uint32_t& count_out) {
     __shared__ uint64_t s_keys[kCandCap];
@@ -165,23 +236,24 @@ __device__ __forceinline__ const uint64_t* select_body(const float* __restrict__
     __shared__ uint32_t s_part[1024];
     __shared__ uint32_t s_res[4];
     __shared__ uint32_t s_cnt, s_ng, s_ng2;
-    const uint32_t n_tasks = tiers.total();
+    const TaskTiers& tiers = map.tiers;
+    const uint32_t G = map.G;
+    const uint32_t n_groups = map.total();
     const int lane = threadIdx.x & 63;
     float r_lo = 0.f, r_scale = 0.f;                       // mode 2: the bins' range (see bin_of_range)
 
-#define CQS_STAMP(i) do { if (dbg && threadIdx.x == 0 && blockIdx.x == 0) dbg[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
     CQS_STAMP(0);
     for (uint32_t i = threadIdx.x; i < kHistBins; i += 1024u) s_hist[i] = 0u;
     if (threadIdx.x == 0) { s_cnt = 0; s_ng = 0; s_ng2 = 0; }
     __syncthreads();
     if (linear == 2u) {                                    // phase 0: smallest and largest finite group maximum
         float lo = INFINITY, hi = -INFINITY;
-        for (uint32_t t0 = 0; t0 < n_tasks; t0 += 1024u * kGB) {   // kGB unconditional loads in flight (a conditional one per trip waited for each)
+        for (uint32_t t0 = 0; t0 < n_groups; t0 += 1024u * kGB) {   // kGB unconditional loads in flight (a conditional one per trip waited for each)
             float v[kGB];
 #pragma unroll
             for (int u = 0; u < kGB; ++u) {
                 const uint32_t t = t0 + (uint32_t)u * 1024u + threadIdx.x;
-                v[u] = gm[t < n_tasks ? t : n_tasks - 1u];
+                v[u] = gm[t < n_groups ? t : n_groups - 1u];
             }
 #pragma unroll
             for (int u = 0; u < kGB; ++u)
@@ -203,61 +275,11 @@ __device__ __forceinline__ const uint64_t* select_body(const float* __restrict__
         if (!(r_scale < INFINITY)) r_scale = 0.f;          // a range narrower than 4096 ulps of a subnormal: one bin, the exact path sorts it out
     }
 
-    // phase 1: histogram of the group maxima
-    float m[kGB];
-    const bool one_pass = n_tasks <= 1024u * kGB;  // the maxima then stay in registers for phase 2
-    for (uint32_t t0 = 0; t0 < n_tasks; t0 += 1024u * kGB) {
-#pragma unroll
-        for (int u = 0; u < kGB; ++u) {
-            const uint32_t t = t0 + (uint32_t)u * 1024u + threadIdx.x;
-            const float v = gm[t < n_tasks ? t : n_tasks - 1u];  // unconditional load, clamped
-            m[u] = t < n_tasks ? v : -INFINITY;
-        }
-#pragma unroll
-        for (int u = 0; u < kGB; ++u)
-            if (m[u] != -INFINITY) atomicAdd(&s_hist[bin_any(m[u], linear, r_lo, r_scale)], 1u);
-    }
-    __syncthreads();
-    CQS_STAMP(1);
-    block_decide<1024>(s_hist, k, s_part, s_res);
-    const uint32_t T = (s_res[3] < k) ? 0u : s_res[0];  // fewer groups than k: every valid score is a candidate
-    __syncthreads();
-    CQS_STAMP(2);
-
-    // phase 2: groups whose maximum reaches the threshold bin
-    for (uint32_t t0 = 0; t0 < n_tasks; t0 += 1024u * kGB) {
-        if (!one_pass) {
-#pragma unroll
-            for (int u = 0; u < kGB; ++u) {
-                const uint32_t t = t0 + (uint32_t)u * 1024u + threadIdx.x;
-                const float v = gm[t < n_tasks ? t : n_tasks - 1u];
-                m[u] = t < n_tasks ? v : -INFINITY;
-            }
-        }
-        // list positions by ballot + mbcnt, one LDS atomic per wave (round 5; until then a 6-step shuffle scan over 16 flags)
-        bool take[kGB];
-        uint64_t mk[kGB];
-        uint32_t pre[kGB], tot = 0;
-#pragma unroll
-        for (int u = 0; u < kGB; ++u) {
-            take[u] = (m[u] != -INFINITY) && (bin_any(m[u], linear, r_lo, r_scale) >= T);
-            mk[u] = __ballot(take[u]);
-            pre[u] = tot;
-            tot += (uint32_t)__popcll(mk[u]);
-        }
-        uint32_t base = 0;
-        if (tot) {                                       // wave-uniform
-            if (lane == 0) base = atomicAdd(&s_ng, tot);
-            base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-        }
-#pragma unroll
-        for (int u = 0; u < kGB; ++u) {
-            const uint32_t slot = base + pre[u] + __builtin_amdgcn_mbcnt_hi((uint32_t)(mk[u] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mk[u], 0u));
-            if (take[u] && slot < kGroupCap) s_groups[slot] = t0 + (uint32_t)u * 1024u + threadIdx.x;
-        }
-    }
-    __syncthreads();
-    CQS_STAMP(3);
+    // phases 1 and 2: the threshold bin and the groups that reach it, at as many slots per thread as the groups need.  Only
+    // a map of G > 1 has few enough groups for the short form to pay; G = 1 callers keep the code they had.
+    const uint32_t T = (G > 1u && n_groups <= 1024u * kGBShort)
+                           ? select_front<kGBShort>(gm, n_groups, k, linear, r_lo, r_scale, s_hist, s_part, s_res, &s_ng, s_groups, dbg)
+                           : select_front<kGB>(gm, n_groups, k, linear, r_lo, r_scale, s_hist, s_part, s_res, &s_ng, s_groups, dbg);
     const uint32_t ng = s_ng;
     uint32_t count = kCandCap + 1u;
     if (ng <= kGroupCap) {
@@ -283,33 +305,49 @@ __device__ __forceinline__ const uint64_t* select_body(const float* __restrict__
                 const float sec = __uint_as_float((uint32_t)ax);
                 const bool need = valid && (sec != -INFINITY) && (bin_any(sec, linear, r_lo, r_scale) >= T);
                 const bool direct = valid && !need;
-                const uint64_t mn = __ballot(need), md = __ballot(direct);
+                // a group to gather appends its (up to G) tasks: task j of every such group by one ballot, one LDS atomic per wave
+                const uint32_t ntk = need ? map.tasks(t) : 0u;
+                const uint64_t md = __ballot(direct);
+                uint64_t mn[kMaxGroupTasks];
+                uint32_t pn[kMaxGroupTasks], totn = 0;
+#pragma unroll
+                for (uint32_t j = 0; j < kMaxGroupTasks; ++j) {
+                    mn[j] = (j < G) ? __ballot(need && (j == 0u || j < ntk)) : 0ull;
+                    pn[j] = totn;
+                    totn += (uint32_t)__popcll(mn[j]);
+                }
                 uint32_t bn = 0, bd = 0;
                 if (lane == 0) {
-                    if (mn) bn = atomicAdd(&s_ng2, (uint32_t)__popcll(mn));
+                    if (totn) bn = atomicAdd(&s_ng2, totn);
                     if (md) bd = atomicAdd(&s_cnt, (uint32_t)__popcll(md));
                 }
                 bn = (uint32_t)__builtin_amdgcn_readfirstlane((int)bn);
                 bd = (uint32_t)__builtin_amdgcn_readfirstlane((int)bd);
-                if (need) {
-                    const uint32_t slot = bn + __builtin_amdgcn_mbcnt_hi((uint32_t)(mn >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mn, 0u));
-                    if (slot < kHistBins) s_list2[slot] = t;
+#pragma unroll
+                for (uint32_t j = 0; j < kMaxGroupTasks; ++j) {
+                    if (j < G && need && (j == 0u || j < ntk)) {
+                        const uint32_t slot = bn + pn[j] + __builtin_amdgcn_mbcnt_hi((uint32_t)(mn[j] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mn[j], 0u));
+                        if (slot < kHistBins) s_list2[slot] = G * t + j;
+                    }
                 }
                 if (direct) {
                     const uint32_t slot = bd + __builtin_amdgcn_mbcnt_hi((uint32_t)(md >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)md, 0u));
-                    uint32_t grows;
-                    const uint32_t gbase = tiers.locate(t, grows);
-                    if (slot < kCandCap) s_keys[slot] = pack_key(okey(mx), row_base + gbase + (uint32_t)(ax >> 32));
+                    if (slot < kCandCap) s_keys[slot] = pack_key(okey(mx), row_base + map.base(t) + (uint32_t)(ax >> 32));
                 }
             }
             __syncthreads();
             if (s_ng2 <= kHistBins) { glist = s_list2; n2 = s_ng2; }
-            else {                                         // more groups to read than the second list holds: read them all
+            else {                                         // more tasks to read than the second list holds: read every listed group
                 __syncthreads();
                 if (threadIdx.x == 0) s_cnt = 0;
                 __syncthreads();
             }
         }
+        // one wave per TASK: 64 / 32 / 16 rows.  The second list holds tasks; the group list (no gaux, or the second list
+        // overflowed) holds groups, each standing for its G tasks (entry e: task e % G of group e / G; G is a power of two)
+        const bool by_group = glist == s_groups;
+        const uint32_t gsh = (uint32_t)__builtin_ctz(G), n_tasks = tiers.total();
+        if (by_group) n2 = ng << gsh;
         constexpr int kGU = 8;
         const uint32_t wv = threadIdx.x >> 6;
         for (uint32_t g0 = wv * kGU; g0 < n2; g0 += 16u * kGU) {
@@ -320,8 +358,16 @@ __device__ __forceinline__ const uint64_t* select_body(const float* __restrict__
             for (int u = 0; u < kGU; ++u) {
                 const uint32_t g = g0 + (uint32_t)u;
                 uint32_t grows;
-                const uint32_t gbase = tiers.locate((uint32_t)__builtin_amdgcn_readfirstlane((int)glist[g < n2 ? g : n2 - 1u]), grows);
-                in[u] = g < n2 && (uint32_t)lane < grows;
+                const uint32_t e = g < n2 ? g : n2 - 1u;
+                uint32_t task = (uint32_t)__builtin_amdgcn_readfirstlane((int)glist[by_group ? e >> gsh : e]);
+                bool there = true;
+                if (G > 1u && by_group) {                  // (a partial last group has fewer than G tasks)
+                    task = (task << gsh) + (e & (G - 1u));
+                    there = task < n_tasks;
+                    task = there ? task : n_tasks - 1u;
+                }
+                const uint32_t gbase = tiers.locate(task, grows);
+                in[u] = g < n2 && there && (uint32_t)lane < grows;
                 idx[u] = gbase + (in[u] ? (uint32_t)lane : 0u);
             }
 #pragma unroll

@@ -46,7 +46,8 @@ d = np.stack(got)
 us = lambda x, y: (d[:, x] - d[:, y]) * 0.01               # 100 MHz counter
 _, cert, fb = idx.bf16_stats()
 print(f"# tail stamps: {a.rows} x {a.dim}, k = {a.k}, b = 1, {a.searches} searches")
-print(f"# certified {cert}, fallbacks {fb} (warm-up included); candidates listed by the select: median {int(np.median(d[:, 9]))}")
+print(f"# certified {cert}, fallbacks {fb} (warm-up included); groups listed by the select: median {int(np.median(d[:, 8]))},"
+      f" candidates: median {int(np.median(d[:, 9]))} (CQS_HIP_I8_GROUPS={os.environ.get('CQS_HIP_I8_GROUPS', '1')})")
 vh = lib.cqs_hip_debug_tail_verdicts
 vh.restype = C.c_int32
 vh.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]
@@ -61,6 +62,11 @@ def line(name, v):
 
 
 s = us
+line("  histogram of the maxima (link 1) 0 -> 1", s(1, 0))
+line("  decide the threshold bin (2)    1 -> 2", s(2, 1))
+line("  group list (link 3)             2 -> 3", s(3, 2))
+line("  candidates (link 4)             3 -> 4", s(4, 3))
+line("  sort (link 5)                   4 -> 5", s(5, 4))
 line("select (links 1-5)                0 -> 5", s(5, 0))
 line("first row loads issued            5 -> 6", s(6, 5))
 line("first row reduced (link 6)        6 -> 7", s(7, 6))
