@@ -22,8 +22,19 @@ __device__ __forceinline__ void f32_row_fragments(const float* rp, uint32_t dim,
     }
 }
 
-// The lane's fragments of the row at rp and of the query at qp (zero past the row's end), chunk by chunk.  (A kernel that
-// scores many rows against one query keeps the query's fragments, in this layout with these zeros, where it likes.)
+// The lane's fragments of the query at qp: zero past the row's end.  (A kernel that scores many rows against one query
+// keeps them, in this layout with these zeros, where it likes.)
+template <int NCH>
+__device__ __forceinline__ void f32_query_fragments(const float* qp, uint32_t dim, uint32_t lane, f4 (&qv)[NCH]) {
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        const uint32_t idx = (uint32_t)c * 256u + lane * 4u;
+        const f4 v = *(const f4*)(qp + (idx < dim ? idx : dim - 4u));
+        qv[c] = idx < dim ? v : (f4)(0.f);
+    }
+}
+
+// The lane's fragments of the row at rp and of the query at qp (zero past the row's end), chunk by chunk.
 template <int NCH>
 __device__ __forceinline__ void f32_fragments(const float* rp, const float* qp, uint32_t dim, uint32_t lane, f4 (&x)[NCH],
                                               f4 (&qv)[NCH]) {
@@ -36,6 +47,19 @@ __device__ __forceinline__ void f32_fragments(const float* rp, const float* qp, 
         const f4 v = *(const f4*)(qp + off);
         qv[c] = in ? v : (f4)(0.f);
     }
+}
+
+// The same words with every load of both issued before the first is waited for: the barrier keeps the zeroing behind the
+// loads, so a row costs one round trip, not one per chunk.  For a kernel in which the compiler, left to itself, puts each
+// chunk's zeroing right behind its load (the tiered tail kernel, scan_bf16.hip: seen in its code, 0.5 us per launch).
+template <int NCH>
+__device__ __forceinline__ void f32_fragments_batched(const float* rp, const float* qp, uint32_t dim, uint32_t lane, f4 (&x)[NCH],
+                                                      f4 (&qv)[NCH]) {
+    f32_row_fragments<NCH>(rp, dim, lane, x);
+    f32_row_fragments<NCH>(qp, dim, lane, qv);   // (the same clamped offsets)
+    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) qv[c] = (uint32_t)c * 256u + lane * 4u < dim ? qv[c] : (f4)(0.f);
 }
 
 // The dot product of the two, in every lane: an (even, odd) packed-FMA chain over the chunks in order, even + odd, then the xor

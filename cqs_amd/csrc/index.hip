@@ -248,7 +248,7 @@ int32_t create_common(uint64_t n, uint32_t dim, uint32_t metric, int32_t device,
     }
     read_combine_env(x);
     if (getenv("CQS_HIP_DEBUG_STAMPS")) {
-        const size_t bytes = (16 + 2 * cqs::kDbgWaves) * sizeof(unsigned long long);
+        const size_t bytes = (cqs::kDbgTailSlow + cqs::kDbgTailSlowWords) * sizeof(unsigned long long);
         if (hipMalloc(&x->d_dbg, bytes) == hipSuccess) (void)hipMemset(x->d_dbg, 0, bytes);
     }
     hipDeviceProp_t prop;

@@ -9,6 +9,7 @@
 #include "scan_bf16.h"
 #include "scan_fallback.h"
 #include "scan_i8.h"
+#include "tail_plan.h"
 
 namespace cqs_idx {
 
@@ -52,6 +53,9 @@ struct Shadow {
                                           // f32 fallback is always the gated scan + select pair
     bool tail_prefix = true;              // CQS_HIP_TAIL_PREFIX, read when the shadow is built: 0 = the tail kernel's finisher always
                                           // sorts every candidate at once (the A/B arm and the tests' reference; same answers)
+    uint8_t tail_first = 2;               // CQS_HIP_TAIL_PREFIX_FIRST, read when the shadow is built: 0 = every tail workgroup selects and the
+                                          // query's waves rescore all k' candidates (the A/B arm and the tests' reference); 1 = the prefix
+                                          // first wherever a proper one exists; unset = where that pays (tail_prefix_first_default).  Same answers
     uint8_t i8_groups = 2;                // CQS_HIP_I8_GROUPS, read when the shadow is built: 0 = the int8 scan publishes one maximum per
                                           // task, as the other scans do (the A/B arm and the tests' reference); 1 = one per workgroup of
                                           // four tasks in every int8 block; unset = where that pays (shadow_group_tasks).  Same answers
@@ -267,6 +271,8 @@ static int32_t shadow_enable(cqs_hip_index* x, const char* what) {
     s->fb_one_launch = !(fb_env && fb_env[0] == '0');
     const char* tp_env = getenv("CQS_HIP_TAIL_PREFIX");
     s->tail_prefix = !(tp_env && tp_env[0] == '0');
+    const char* tf_env = getenv("CQS_HIP_TAIL_PREFIX_FIRST");
+    s->tail_first = tf_env && tf_env[0] == '0' ? 0 : (tf_env && tf_env[0] == '1' ? 1 : 2);
     const char* ig_env = getenv("CQS_HIP_I8_GROUPS");
     s->i8_groups = ig_env && ig_env[0] == '0' ? 0 : (ig_env && ig_env[0] == '1' ? 1 : 2);
     if ((e = hipMalloc(&s->d_fb_lists, cqs::f32_topk_fallback_words(x->n_cu) * sizeof(uint64_t))) != hipSuccess) return oom(e);
@@ -417,6 +423,7 @@ int32_t shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k,
                                                s->d_bq, s->d_tickets, s->d_ekeys, out_keys, out_counts, cert,
                                                device_gate ? s->d_stats + kStatCounts : nullptr,
                                                device_gate && i8 ? s->d_stats + kStatI8Counts : nullptr, s->tail_prefix,
+                                               s->tail_first == 2 ? cqs::tail_prefix_first_default(pad_rows(x->n), k) : s->tail_first == 1,
                                                s->d_stats + kStatPrefix, x->d_dbg, st));
     return rc;
 }
@@ -597,8 +604,8 @@ int32_t cqs_hip_debug_tail_verdicts(cqs_hip_index* x, uint32_t b, uint32_t* out,
 } CQS_ABI_CATCH(x)
 
 // Diagnostic hook (CQS_HIP_DEBUG_STAMPS=1 handles; tools/tail_stamps.py): out[0, 16) = the phase stamps query 0 of the last
-// shadow search left (select_body's and the tail kernel's, 10 ns ticks), once every search has completed; the words are
-// zeroed for the next search.  INVALID on a handle without the stamp buffer.
+// shadow search left (select_body's and the tail kernel's, 10 ns ticks), out[16, 19) = those of its finisher's slow path (0:
+// not taken), once every search has completed; the words are zeroed for the next search.  INVALID on a handle without the stamp buffer.
 int32_t cqs_hip_debug_tail_stamps(cqs_hip_index* x, uint64_t* out) CQS_ABI_TRY {
     if (!x || x->sh || !out) return CQS_HIP_ERR_INVALID;
     std::lock_guard<std::mutex> g(x->mu);
@@ -606,7 +613,9 @@ int32_t cqs_hip_debug_tail_stamps(cqs_hip_index* x, uint64_t* out) CQS_ABI_TRY {
     HIP_TRY(x, hipSetDevice(x->device));
     HIP_TRY(x, quiesce(x));
     HIP_TRY(x, hipMemcpyAsync(out, x->d_dbg, 16 * sizeof(uint64_t), hipMemcpyDeviceToHost, x->stream));
+    HIP_TRY(x, hipMemcpyAsync(out + 16, x->d_dbg + cqs::kDbgTailSlow, cqs::kDbgTailSlowWords * sizeof(uint64_t), hipMemcpyDeviceToHost, x->stream));
     HIP_TRY(x, hipMemsetAsync(x->d_dbg, 0, 16 * sizeof(uint64_t), x->stream));
+    HIP_TRY(x, hipMemsetAsync(x->d_dbg + cqs::kDbgTailSlow, 0, cqs::kDbgTailSlowWords * sizeof(uint64_t), x->stream));
     HIP_TRY(x, hipStreamSynchronize(x->stream));
     return CQS_HIP_OK;
 } CQS_ABI_CATCH(x)

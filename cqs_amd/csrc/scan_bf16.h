@@ -105,12 +105,17 @@ hipError_t launch_scan_bf16(const ScanArgs& a, const uint16_t* shadow, const flo
 // whose outcome the host never sees; the second pair counts what the int8 copy served).
 // prefix: the finisher sorts the first tail_prefix_first candidates' keys and certifies on them where it can (tail_prefix.h);
 // false: it sorts all at once.  Same outputs either way.  prefix_counts: nullable device [2], += queries certified on the prefix,
-// += queries whose prefix failed and that went on.  dbg: nullable device [16] (CQS_HIP_DEBUG_STAMPS), phase stamps of query 0's tail.
+// += queries whose prefix failed and that went on.  prefix_first: where the copy's k' leaves room for a proper prefix, the query's
+// workgroups select and rescore that prefix alone, and the finisher does the rest by itself if the prefix does not certify
+// (tail_plan.h); same outputs, verdicts and counts either way.  dbg: nullable device [16 + 2 * kDbgWaves + 3]
+// (CQS_HIP_DEBUG_STAMPS), phase stamps of query 0's tail.
+constexpr uint32_t kDbgTailSlow = 16u + 2u * kDbgWaves;   // the slow path's stamps: behind the f32 scan's per-wave ones (scan_kernels.h)
+constexpr uint32_t kDbgTailSlowWords = 3u;
 hipError_t launch_rescore_certify(const ScanArgs& a, uint32_t row_base, uint32_t k, uint32_t kprime, uint32_t bound,
                                   double r_max, double norm_max, float* bq, uint32_t* tickets, uint64_t* ekeys,
                                   uint64_t* out_keys, uint32_t* out_counts, uint32_t* cert, unsigned long long* counters,
-                                  unsigned long long* counters2, bool prefix, unsigned long long* prefix_counts, unsigned long long* dbg,
-                                  hipStream_t st);
+                                  unsigned long long* counters2, bool prefix, bool prefix_first, unsigned long long* prefix_counts,
+                                  unsigned long long* dbg, hipStream_t st);
 #endif
 
 }  // namespace cqs

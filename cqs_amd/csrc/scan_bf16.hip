@@ -21,6 +21,7 @@
 #include "scan_gemv_device.h"
 #include "select_device.h"
 #include "shadow_build_device.h"
+#include "tail_plan.h"
 #include "tail_prefix.h"
 
 namespace cqs {
@@ -352,19 +353,19 @@ struct TailParams {
     unsigned long long* counters2;  // nullable [2]: the same again (the int8 copy's own counts)
     uint32_t prefix;           // 1: the finisher sorts a prefix first (tail_prefix.h), 0: all candidates at once
     unsigned long long* prefix_counts;   // nullable [2]: queries certified on the prefix, queries that went on to sort all
-    unsigned long long* dbg;   // CQS_HIP_DEBUG_STAMPS (DBG instantiations only): [0, 16) phase stamps of query 0's tail
+    unsigned long long* dbg;   // CQS_HIP_DEBUG_STAMPS (DBG instantiations only): [0, 16) phase stamps of query 0's tail, and
+                               // kDbgTailSlow words further on the slow path's three
+    uint32_t first;            // tail_plan_first: tier 1's candidates (implies prefix), 0: no tiers
 };
 
-constexpr uint32_t kTailWaves = 16;   // 1024 threads: the block shape select_body and rank_sort_keys are written for
-
 // One launch for a block's tail.  blockIdx.y = query; the query's waves are numbered w = blockIdx.x * 16 + wave and take
-// the slots w, w + #waves, ... of 0 .. min(count, k').
-//  every workgroup  the select of its query for the top k' + 1 approximate keys (select_body on the scan's scores / gmax /
+// the slots w, w + #waves, ... of 0 .. min(count, lim), lim = k' candidates, or tier 1's j1 (tail_plan.h).
+//  every workgroup  the select of its query for the top lim + 1 approximate keys (select_body on the scan's scores / gmax /
 //                   gaux, as select_finish_kernel runs it): nobody can wait for a select workgroup, so each does the
 //                   select itself.  All of them read the same words an earlier launch wrote and run the same code, so all
 //                   hold the same sorted list and nothing is handed between workgroups before the ticket below.
 //  slot 0           B_q of the query into bq (bound != 0), beside the rescoring waves, off their path.
-//  slot i + 1       candidate i < min(count, k'): its exact f32 score, scan_gemv_kernel's for this (row, query): lane owns
+//  slot i + 1       candidate i < min(count, lim): its exact f32 score, scan_gemv_kernel's for this (row, query): lane owns
 //                   floats [c*256 + lane*4, +4) of chunk c (clamped address and zero query fragment past a partial last
 //                   chunk), an (even, odd) packed-FMA chain over the chunks in order, even + odd, then the xor butterfly at
 //                   distances 32 -> 1 - the tree treduce builds for every RI x BQ (each node adds the same two partial
@@ -375,14 +376,24 @@ constexpr uint32_t kTailWaves = 16;   // 1024 threads: the block shape select_bo
 //                   them is an earlier launch).
 // Nobody waits for anybody: a workgroup adds one to the query's ticket when its waves have stored, and the one whose add
 // returns gridDim.x - 1 knows that every other has.  It puts the ticket back to 0 for the next search.
+// Prefix first (p.first = j1 != 0): the select is exact and its keys totally ordered, so the first min(count, j1 + 1) keys of a
+// select at j1 + 1 are those of the select at k' + 1.  With j1 + 1 keys returned the finisher holds what the prefix
+// certificate reads - candidates 0 .. j1 - 1 rescored and key j1 - and a query it certifies is done at half the slots and a
+// select of 161 keys, not 351 (k = 20).  Where it does not certify, the finisher alone goes round again: the select at
+// k' + 1, its 16 waves rescore candidates j1 .. nc - 1 into LDS behind the prefix's keys, then one sort and the rules on all
+// of them - the verdict the tail without tiers reaches, and still nobody waits.  Fewer than j1 + 1 keys returned: every valid row was a
+// candidate and was rescored, rule (a).
 // Visibility (per-XCD L2s are not coherent, a CU's L1 is never refreshed): every word handed over (ekeys, bq) is stored
 // write-through by an agent-scope atomic store, each wave drains its stores before the workgroup's barrier, one lane then
 // adds to the ticket, and the finisher reads those words by agent-scope atomic loads only, after the add has returned and a
 // barrier that the adding wave joins.  scores / gmax / gaux come from an earlier launch and are read plainly.
-// DBG: phase stamps of query 0's tail (s_memrealtime) into p.dbg: [0, 6) select_body's, 6 / 7 first rows issued / reduced
-// (lane 0 of workgroup 0's wave 1), 10 workgroup 0's ticket returned, 14 the finisher's, 11 / 12 / 13 the finisher's keys
-// listed / sorted / outputs stored.
-template <int NCH, bool DBG>
+// DBG: phase stamps of query 0's tail (s_memrealtime) into p.dbg: [0, 6) the first select_body's, 6 / 7 first rows issued /
+// reduced (lane 0 of workgroup 0's wave 1), 10 workgroup 0's ticket returned, 14 the finisher's, 11 / 12 / 13 the finisher's
+// keys listed / sorted (the last sort) / outputs stored; kDbgTailSlow + 0 / 1 / 2 the finisher's prefix refused / second select
+// done / remaining rows' keys in LDS.
+// TIER is a property of the instantiation, not a branch: without it (p.first == 0: the bf16 copy, CQS_HIP_TAIL_PREFIX=0, the tier
+// switched off or ruled out) the kernel holds one select, no slow path, and is the code it was before there were tiers.
+template <int NCH, bool DBG, bool TIER>
 __global__ __launch_bounds__(1024) void rescore_certify_kernel(const TailParams p) {
     __shared__ uint64_t s_keys[kShadowKMax];
     __shared__ uint64_t s_sorted[kShadowKMax];
@@ -400,20 +411,26 @@ __global__ __launch_bounds__(1024) void rescore_certify_kernel(const TailParams 
     if (threadIdx.x == 0) s_cnt = 0u;
     if (qi == 0u && blockIdx.x == 0u)
         for (uint32_t i = threadIdx.x; i < kWorkWords; i += 1024u) p.work[i] = 0u;
-    // the approximate top k' + 1, sorted: what select_finish_kernel wrote to akeys / acounts when it was a launch of its own
     const GroupMap map{p.tiers, p.group_tasks};
     const uint32_t n_groups = map.total();
-    uint32_t found;
-    const uint64_t* akeys = select_body(p.scores + (size_t)qi * p.n_pad, p.gmax + (size_t)qi * n_groups,
-                                        p.gaux ? p.gaux + (size_t)qi * n_groups : nullptr, p.n_pad, map, p.kprime + 1u,
-                                        p.row_base, p.bins, DBG ? dbg : nullptr, found);
-    found = (uint32_t)__builtin_amdgcn_readfirstlane((int)found);   // (workgroup-uniform: a scalar from here on)
-    const uint32_t ac = found < p.kprime + 1u ? found : p.kprime + 1u;
-    const uint32_t nc = ac < p.kprime ? ac : p.kprime;
-    const uint64_t key_next = ac > p.kprime ? akeys[p.kprime] : 0ull;   // the (k' + 1)-th approximate key (the finisher's)
+    const uint32_t first = TIER ? p.first : 0u;
+    uint32_t lim = TIER ? first : p.kprime;   // candidates of this select; it returns one key more where there is one
+    uint32_t found, ac, nc;
+    uint64_t key_next;
+    const uint64_t* akeys;
+    // the approximate top lim + 1, sorted: what select_finish_kernel wrote to akeys / acounts when it was a launch of its own
+    auto run_select = [&](unsigned long long* stamps) {
+        akeys = select_body(p.scores + (size_t)qi * p.n_pad, p.gmax + (size_t)qi * n_groups,
+                            p.gaux ? p.gaux + (size_t)qi * n_groups : nullptr, p.n_pad, map, lim + 1u, p.row_base, p.bins,
+                            stamps, found);
+        found = (uint32_t)__builtin_amdgcn_readfirstlane((int)found);   // (workgroup-uniform: a scalar from here on)
+        ac = found < lim + 1u ? found : lim + 1u;
+        nc = ac < lim ? ac : lim;
+        key_next = ac > lim ? akeys[lim] : 0ull;   // the (lim + 1)-th approximate key (the finisher's)
+    };
+    run_select(DBG ? dbg : nullptr);
 
-    // top k of the m kept exact keys in s_keys, the outputs, the verdict: what the last workgroup to arrive does, and
-    // workgroup 0 on the path of its own
+    // top k of the m kept exact keys in s_keys, the outputs, the verdict: what the last workgroup to arrive does
     auto write_out = [&](uint32_t m, bool ok) {
         const uint32_t k = p.k;
         const uint32_t outc = m < k ? m : k;
@@ -425,7 +442,8 @@ __global__ __launch_bounds__(1024) void rescore_certify_kernel(const TailParams 
             if (p.counters2) atomicAdd(&p.counters2[ok ? 0 : 1], 1ull);
         }
     };
-    // today's rules on all min(count, k') candidates, m of them kept
+    // the rules on all min(count, k') candidates, m of them kept (ac, key_next: of a select that was asked for k' + 1 keys,
+    // or of tier 1's where it returned no more than j1 <= k')
     auto full_verdict = [&](uint32_t m, float bq) {
         bool ok = false;
         if (__builtin_fabsf(bq) <= 3.4028234664e38f) {
@@ -455,7 +473,8 @@ __global__ __launch_bounds__(1024) void rescore_certify_kernel(const TailParams 
         const float* rp = p.rows + (size_t)(grow - p.row_base) * dim;
         // the exact score and scan_gemv_kernel's epilogue: f32_score.h, shared with the one-launch f32 fallback
         f4 x[NCH], qv[NCH];
-        f32_fragments<NCH>(rp, qp, dim, lane, x, qv);
+        if constexpr (TIER) f32_fragments_batched<NCH>(rp, qp, dim, lane, x, qv);
+        else f32_fragments<NCH>(rp, qp, dim, lane, x, qv);
         CQS_TAIL_STAMP(6, slot == 1u && threadIdx.x == 64u);
         float s = f32_dot_chain<NCH>(x, qv);
         const bool keep = f32_emit(s, p.mode, p.thr);
@@ -480,8 +499,10 @@ __global__ __launch_bounds__(1024) void rescore_certify_kernel(const TailParams 
 
     // the finisher: every other workgroup of the query has stored, drained and signalled.  The certificate holds for any
     // prefix of the candidates (tail_prefix_first), and the rank sort is quadratic in what it sorts: first the prefix alone;
-    // the rest only if the prefix does not certify, and then today's rules on all of them.
+    // the rest only if the prefix does not certify, and then the rules on all of them.  Tier 1 rescored the prefix alone:
+    // it is a proper one whenever the select returned a key past it.
     const uint32_t j1 = p.prefix ? tail_prefix_first(p.k, nc) : nc;
+    const bool proper = TIER ? found > first : j1 < nc;   // (workgroup-uniform) candidate j1 is the first row outside the prefix
     if (threadIdx.x < j1) {
         const uint64_t key = __hip_atomic_load(p.ekeys + (size_t)qi * p.kprime + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (key != 0ull) s_keys[atomicAdd(&s_cnt, 1u)] = key;
@@ -492,9 +513,9 @@ __global__ __launch_bounds__(1024) void rescore_certify_kernel(const TailParams 
     float bq = 0.f;   // (asked for ahead of the sort: the prefix's verdict stands between the sort and the outputs)
     if (threadIdx.x == 0) bq = __uint_as_float(__hip_atomic_load((uint32_t*)p.bq + qi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
     // a proper prefix is short (6k + 40 keys): all 1024 threads rank it; every candidate at once is the sort it always was
-    if (j1 < nc) rank_sort_keys_wide(s_keys, m, s_sorted, s_ok, &s_flag);
+    if (proper) rank_sort_keys_wide(s_keys, m, s_sorted, s_ok, &s_flag);
     else rank_sort_keys(s_keys, m, s_sorted, s_ok, &s_flag);
-    if (j1 < nc) {   // (workgroup-uniform) a proper prefix: candidate j1 is the first row outside it
+    if (proper) {
         if (threadIdx.x == 0) {
             bool ok = false;
             if (__builtin_fabsf(bq) <= 3.4028234664e38f && m >= p.k)
@@ -509,11 +530,42 @@ __global__ __launch_bounds__(1024) void rescore_certify_kernel(const TailParams 
             CQS_TAIL_STAMP(13, threadIdx.x == 0u);
             return;
         }
-        if (threadIdx.x >= j1 && threadIdx.x < nc) {
-            const uint64_t key = __hip_atomic_load(p.ekeys + (size_t)qi * p.kprime + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (key != 0ull) s_keys[atomicAdd(&s_cnt, 1u)] = key;
+        if constexpr (!TIER) {   // the other workgroups rescored the rest too
+            if (threadIdx.x >= j1 && threadIdx.x < nc) {
+                const uint64_t key = __hip_atomic_load(p.ekeys + (size_t)qi * p.kprime + threadIdx.x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (key != 0ull) s_keys[atomicAdd(&s_cnt, 1u)] = key;
+            }
+        } else {
+            // the slow path, this workgroup alone: the whole select, then candidates first .. nc - 1, a wave taking kRU
+            // neighbours at a time with their loads in flight together (kRU * NCH + NCH f4 registers per lane; only NCH = 3 was
+            // timed).  The kept keys go behind the prefix's in s_keys, which the sort left as they were.
+            CQS_TAIL_STAMP(kDbgTailSlow + 0u, threadIdx.x == 0u);
+            lim = p.kprime;
+            run_select(nullptr);
+            CQS_TAIL_STAMP(kDbgTailSlow + 1u, threadIdx.x == 0u);
+            constexpr int kRU = NCH <= 3 ? 4 : (NCH <= 4 ? 3 : (NCH <= 6 ? 2 : 1));
+            f4 qv[NCH];
+            f32_query_fragments<NCH>(qp, dim, lane, qv);
+            for (uint32_t i0 = first + wib * (uint32_t)kRU; i0 < nc; i0 += kTailWaves * (uint32_t)kRU) {
+                f4 x[kRU][NCH];
+                uint32_t grow[kRU];
+#pragma unroll
+                for (int u = 0; u < kRU; ++u) {
+                    const uint32_t i = i0 + (uint32_t)u < nc ? i0 + (uint32_t)u : nc - 1u;
+                    grow[u] = 0xFFFFFFFFu - (uint32_t)akeys[i];
+                    f32_row_fragments<NCH>(p.rows + (size_t)(grow[u] - p.row_base) * dim, dim, lane, x[u]);
+                }
+                __builtin_amdgcn_sched_barrier(0);   // (the kRU rows' loads are issued before the first is waited for)
+#pragma unroll
+                for (int u = 0; u < kRU; ++u) {
+                    float s = f32_dot_chain<NCH>(x[u], qv);
+                    const bool keep = f32_emit(s, p.mode, p.thr);
+                    if (lane == 0u && i0 + (uint32_t)u < nc && keep) s_keys[atomicAdd(&s_cnt, 1u)] = pack_key(okey(s), grow[u]);
+                }
+            }
         }
         __syncthreads();
+        if constexpr (TIER) CQS_TAIL_STAMP(kDbgTailSlow + 2u, threadIdx.x == 0u);
         m = s_cnt;
         rank_sort_keys(s_keys, m, s_sorted, s_ok, &s_flag);
     }
@@ -531,30 +583,34 @@ __global__ __launch_bounds__(1024) void rescore_certify_kernel(const TailParams 
 
 template <int NCH>
 static void launch_tail(dim3 grid, dim3 block, hipStream_t st, const TailParams& tp) {
-    if (tp.dbg) hipLaunchKernelGGL((rescore_certify_kernel<NCH, true>), grid, block, 0, st, tp);
-    else hipLaunchKernelGGL((rescore_certify_kernel<NCH, false>), grid, block, 0, st, tp);
+    if (tp.first != 0u) {
+        if (tp.dbg) hipLaunchKernelGGL((rescore_certify_kernel<NCH, true, true>), grid, block, 0, st, tp);
+        else hipLaunchKernelGGL((rescore_certify_kernel<NCH, false, true>), grid, block, 0, st, tp);
+    } else {
+        if (tp.dbg) hipLaunchKernelGGL((rescore_certify_kernel<NCH, true, false>), grid, block, 0, st, tp);
+        else hipLaunchKernelGGL((rescore_certify_kernel<NCH, false, false>), grid, block, 0, st, tp);
+    }
 }
 
 hipError_t launch_rescore_certify(const ScanArgs& a, uint32_t row_base, uint32_t k, uint32_t kprime, uint32_t bound,
                                   double r_max, double norm_max, float* bq, uint32_t* tickets, uint64_t* ekeys,
                                   uint64_t* out_keys, uint32_t* out_counts, uint32_t* cert, unsigned long long* counters,
-                                  unsigned long long* counters2, bool prefix, unsigned long long* prefix_counts, unsigned long long* dbg,
-                                  hipStream_t st) {
+                                  unsigned long long* counters2, bool prefix, bool prefix_first, unsigned long long* prefix_counts,
+                                  unsigned long long* dbg, hipStream_t st) {
     const uint32_t b = a.b, dim = a.dim;
     if (b == 0) return hipSuccess;
     if (b > kShadowMaxQ || k == 0 || kprime < k || kprime >= kShadowKMax || a.k != kprime + 1u || dim % 8u != 0u ||
         dim > kShadowMaxDim || bound > 2u || (a.group_tasks != 1u && a.group_tasks != kMaxGroupTasks))
         return hipErrorInvalidValue;
+    const uint32_t first = tail_plan_first(k, kprime, prefix, prefix_first);
     const TailParams tp{a.rows, a.q, dim, k, kprime, a.mode, row_base, a.threshold, a.scores, a.gmax, a.gaux, a.n_pad, a.tiers, a.group_tasks,
                         a.range_bins ? 2u : (a.linear_bins ? 1u : 0u), a.work, ekeys, bq, tickets, bound, r_max, norm_max,
-                        out_keys, out_counts, cert, counters, counters2, prefix ? 1u : 0u, prefix_counts, dbg};
-    // One wave per slot (B_q + k' candidates) while the block's workgroups fit the device in one round; beyond that
-    // (b * ceil((k' + 1) / 16) > CUs: from b = 4 at k = 500) fewer workgroups whose waves take several slots each, because
-    // every workgroup repeats the select's front end and a second round would repeat it behind the first.
-    const uint32_t want = (kprime + 1u + kTailWaves - 1u) / kTailWaves;
-    uint32_t cap = a.n_cu * CQS_TAIL_MAX_BLOCKS_PER_CU / b;
-    if (cap < 1u) cap = 1u;
-    const dim3 grid(want < cap ? want : cap, b), block(64u * kTailWaves);
+                        out_keys, out_counts, cert, counters, counters2, prefix ? 1u : 0u, prefix_counts, dbg, first};
+    // One wave per slot (B_q + the candidates of the first select: tier 1's, or k') while the block's workgroups fit the
+    // device in one round; beyond that (b * ceil((k' + 1) / 16) > CUs: from b = 4 at k = 500) fewer workgroups whose waves
+    // take several slots each, because every workgroup repeats the select's front end and a second round would repeat it
+    // behind the first.
+    const dim3 grid(tail_plan_workgroups(tail_plan_slots(kprime, first), b, a.n_cu, CQS_TAIL_MAX_BLOCKS_PER_CU), b), block(64u * kTailWaves);
     switch ((dim + 255u) / 256u) {
         case 1: launch_tail<1>(grid, block, st, tp); break;
         case 2: launch_tail<2>(grid, block, st, tp); break;
