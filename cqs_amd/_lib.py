@@ -89,6 +89,19 @@ SIGNATURES = [
     ("cqs_hip_index_neighbors", C.c_int32, [_c_idx, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, _pp(C.c_uint32)]),
     ("cqs_hip_index_knn_graph", C.c_int32,
      [_c_idx, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("cqs_hip_layout_params_default", None, [C.c_void_p]),
+    ("cqs_hip_layout_create", C.c_int32,
+     [C.c_int32, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _pp(_c_idx)]),
+    ("cqs_hip_layout_len", C.c_uint64, [_c_idx]),
+    ("cqs_hip_layout_edges", C.c_uint64, [_c_idx]),
+    ("cqs_hip_layout_epochs", C.c_uint32, [_c_idx]),
+    ("cqs_hip_layout_graph", C.c_int32, [_c_idx, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, _pp(C.c_float)]),
+    ("cqs_hip_layout_set_coords", C.c_int32, [_c_idx, C.c_void_p]),
+    ("cqs_hip_layout_coords", C.c_int32, [_c_idx, C.c_void_p]),
+    ("cqs_hip_layout_run", C.c_int32, [_c_idx, C.c_uint32, _pp(C.c_uint32)]),
+    ("cqs_hip_layout_last_error", C.c_size_t, [_c_idx, C.c_char_p, C.c_size_t]),
+    ("cqs_hip_layout_destroy", None, [_c_idx]),
+    ("cqs_hip_index_umap_project", C.c_int32, [_c_idx, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p]),
     ("cqs_hip_index_diff", C.c_int32,
      [_c_idx, C.c_void_p, _c_idx, C.c_void_p, C.c_uint64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("cqs_hip_index_pairwise", C.c_int32, [_c_idx, C.c_void_p, C.c_uint32, C.c_void_p]),
@@ -189,6 +202,12 @@ class BertConfig(C.Structure):
                 ("intermediate", C.c_uint32), ("max_pos", C.c_uint32), ("type_vocab", C.c_uint32),
                 ("num_labels", C.c_uint32), ("head", C.c_uint32), ("ln_eps", C.c_float)]
 
+
+
+class LayoutParams(C.Structure):
+    """`cqs_hip_layout_params` (include/cqs_hip.h)."""
+    _fields_ = [("a", C.c_float), ("b", C.c_float), ("learning_rate", C.c_float), ("repulsion", C.c_float),
+                ("negative_samples", C.c_uint32), ("n_epochs", C.c_uint32), ("seed", C.c_uint64)]
 
 
 class EmbedConfig(C.Structure):

@@ -795,6 +795,32 @@ class HipIndex(VectorIndex):
         return [[IndexResult(self._id(int(rows[i, j])), float(scores[i, j])) for j in range(int(counts[i]))]
                 for i in range(rows.shape[0])]
 
+    def umap_project(self, n_neighbors: int = 15, n_epochs: Optional[int] = None, seed: int = 42,
+                     rows_per_call: int = 4096) -> np.ndarray:
+        """`cqs index --umap` on the resident corpus (src/cli/commands/index/umap.rs): the exact graph of
+        `knn_graph_rows(n_neighbors - 1)` - umap-learn counts a point among its own neighbours - in calls of
+        `rows_per_call` targets cut at multiples of 256, then a `HipLayout` (cqs_amd/umap.py) on this index's device run to
+        its end.  Returns coordinates f32 [n, 2] in row order; fewer than 2 rows give the origin.  Raises what
+        `knn_graph_rows` raises on a row-sharded handle."""
+        from .umap import HipLayout
+        n = len(self)
+        if n < 2:
+            return np.zeros((n, 2), dtype=np.float32)
+        if int(self._lib.cqs_hip_index_row_base(self._h)) != 0:
+            raise ValueError("umap_project: the handle's row_base is not 0")
+        rows, scores, counts = self.knn_graph_rows(int(n_neighbors) - 1, rows_per_call=rows_per_call)
+        with HipLayout(rows, scores, counts, device=int(self._lib.cqs_hip_index_device(self._h)),
+                       n_epochs=0 if n_epochs is None else int(n_epochs), seed=int(seed)) as lay:
+            lay.run()
+            return lay.coords()
+
+    def umap_project_by_id(self, n_neighbors: int = 15, n_epochs: Optional[int] = None, seed: int = 42,
+                           rows_per_call: int = 4096) -> List[Tuple[str, float, float]]:
+        """`umap_project` by chunk id, in row order: (id, x, y) - the triples the reference's script answers with."""
+        xy = self.umap_project(n_neighbors, n_epochs, seed, rows_per_call)
+        base = int(self._lib.cqs_hip_index_row_base(self._h))
+        return [(self._id(base + i), float(xy[i, 0]), float(xy[i, 1])) for i in range(xy.shape[0])]
+
     # ---- semantic diff of two resident indexes (src/diff.rs:99-246, src/drift.rs:51-120) ------------
     def diff_rows(self, other: "HipIndex", rows_a, rows_b, threshold: float, want_sims: bool = False):
         """`cqs_hip_index_diff`: pair i is (stored row `rows_a[i]` of this index, stored row `rows_b[i]` of `other`), global

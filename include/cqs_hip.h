@@ -283,6 +283,104 @@ int32_t cqs_hip_index_neighbors(cqs_hip_index* idx, uint64_t target_row, uint32_
 int32_t cqs_hip_index_knn_graph(cqs_hip_index* idx, uint64_t first_row, uint64_t m, uint32_t limit,
                                 uint64_t* out_rows, float* out_scores, uint32_t* out_counts);
 
+/* ---- UMAP layout of a kNN graph ---------------------------------------------------
+ * `cqs index --umap` (src/cli/commands/index/umap.rs) streams every embedding to a Python child that runs umap-learn with
+ * n_neighbors = 15, min_dist = 0.1, metric = "cosine" and stores 2-D coordinates for the cluster view of `cqs serve`.
+ * cqs_hip_index_knn_graph is the first half of that work; this is the second: the fuzzy-simplicial-set weights of the
+ * graph and the epochs of force-directed layout, on the device.  The layout is its own handle: it takes a graph, not an
+ * index, and never holds an index's mutex.  The rules below are umap-learn's published algorithm with the stated
+ * departures; they are the specification.
+ * Input: exactly what cqs_hip_index_knn_graph writes for the whole corpus of a handle with row_base 0.  Vertex i owns
+ * knn_rows[i*stride .. i*stride + knn_counts[i]) and the same range of knn_scores (host; raw dots of unit rows; the target
+ * itself excluded; a list names a vertex at most once).  The arrays are read during `create` only.
+ * Distances: d = max(0, 1 - score) in f32.
+ * Smooth-kNN, per vertex with c = its count:  rho = the smallest d > 0 of its list, 0 if there is none.  sigma by
+ *   umap-learn's bisection in f32: lo = 0, hi = inf, mid = 1, at most 64 rounds of
+ *     psum = sum over the list of (d - rho > 0 ? expf(-(d - rho) / mid) : 1);  stop when |psum - target| < 1e-5;
+ *     psum > target: hi = mid, mid = (lo + hi) / 2;  else lo = mid, mid = hi infinite ? 2 mid : (lo + hi) / 2
+ *   with target = log2f(c + 1) - umap-learn counts the point itself among its n_neighbors, so a graph of limit 14 is its
+ *   n_neighbors = 15 - and sigma = the last mid.  Then sigma = max(sigma, 1e-3 * mean(d of the list)); stated departure:
+ *   umap-learn uses the global mean where rho == 0.  c == 0: rho = sigma = 0, no forward edges.
+ *   w(i->j) = 1 where d - rho <= 0 or sigma == 0, else expf(-(d - rho) / sigma).
+ * Fuzzy union: s(i,j) = w(i->j) + w(j->i) - w(i->j) * w(j->i), 0 for an absent direction, the sum, the product and the
+ *   difference each rounded.  The adjacency of i is its forward list in list order, then the vertices that list i and are
+ *   not in i's list, in ascending id: every undirected edge is stored at both ends with the same weight bits.  w_max is
+ *   the maximum over all entries.  This order is part of the contract: it is what cqs_hip_layout_graph returns and what
+ *   "adjacency slot" means below.
+ * Epoch e = 1 .. E (E = n_epochs, or 500 for n <= 10000 and 200 above where that is 0), on a snapshot - stated departure:
+ *   umap-learn updates in place, edge by edge; here every vertex reads the previous epoch's coordinates and writes the
+ *   next, so the result is a pure function of its inputs, without atomics or races.
+ *     alpha = learning_rate * (1 - (e - 1) / E)
+ *     an adjacency entry is active iff floorf(e * p) != floorf((e - 1) * p) with p = s / w_max: f32 operations, each
+ *     rounded once
+ *     for vertex i, the sum over its active entries (other end j, slot t) of
+ *       2 * clip(ca * (y_i - y_j)),  ca = -2ab d2^(b-1) / (a d2^b + 1), d2 = |y_i - y_j|^2; 0 where d2 == 0  (twice:
+ *         umap-learn lists the edge in both directions and each copy moves both ends)
+ *       + for each draw k < negative_samples, of vertex q:  clip(cr * (y_i - y_q)),
+ *         cr = 2 repulsion b / ((0.001 + d2) (a d2^b + 1)); 0 where q == i or d2 == 0
+ *     clip is to [-4, 4] per coordinate;  y_i_new = y_i + alpha * sum.
+ * Random draws: counter-based, from murmur3's 32-bit finaliser
+ *     fmix(h): h ^= h >> 16; h *= 0x85EBCA6B; h ^= h >> 13; h *= 0xC2B2AE35; h ^= h >> 16
+ *     hash(seed, epoch, vertex, slot, draw) = fmix(fmix(fmix(fmix(fmix(fmix(lo32(seed) ^ 0x9E3779B9) ^ hi32(seed)) ^ epoch)
+ *                                             ^ vertex) ^ slot) ^ draw)
+ *     q = (uint64(hash) * n) >> 32
+ *   with slot = the entry's position in its vertex's adjacency.  Initial coordinates, unless cqs_hip_layout_set_coords
+ *   replaces them, are uniform in [-10, 10): coordinate c of vertex i = float(hash(seed, 0, i, 0, c) >> 8) * (20 / 2^24)
+ *   - 10 in f32, the product and the difference each rounded.  There is no device RNG state and nothing depends on the
+ *   launch grid.
+ * Determinism: the coordinates after epoch e are a function of the graph arrays, the parameters and the initial
+ *   coordinates only.  run(50) and run(20); run(30) give the same bytes; two handles made from the same inputs give the
+ *   same bytes.  A wave adds its terms in a fixed order that is not the sequential one: lane l of 64 adds the entries
+ *   l, l + 64, ... in that order (attraction, then the draws 0, 1, ...), then the lanes add as v += v[lane ^ 32], ^ 16,
+ *   ^ 8, ^ 4, ^ 2, ^ 1.
+ * Degenerate sizes: n < 2 is valid: the coordinates are the origin, edges is 0 and `run` launches nothing.
+ * create    refuses with CQS_HIP_ERR_INVALID, nothing left allocated, *out NULL, in this order: a NULL out, params or
+ *           array; n > 2^31; stride == 0 or stride > CQS_HIP_NEIGHBORS_MAX; a count greater than stride; a neighbour id
+ *           >= n or equal to its own vertex (the text names the vertex); a non-finite a, b, learning_rate or repulsion or
+ *           a non-positive a or b; n_epochs > 10000.  The reason is this thread's create text: cqs_hip_layout_last_error
+ *           with a NULL handle.  The adjacency is built on the host (the graph arrives from host memory anyway), the
+ *           weights on the device.  Device memory: two coordinate buffers (16 n bytes) and the adjacency, 8 bytes per
+ *           entry, at most 2 n stride entries, plus 20 n bytes of offsets, rho and sigma.
+ * graph     the structure above, each output nullable: offsets [n + 1] u64, nbrs / weights [edges], rho / sigma [n],
+ *           *w_max (0 where edges == 0).
+ * set_coords / coords   xy [n * 2] f32, host: x then y of each vertex.  set_coords replaces the current coordinates and
+ *           leaves the epoch counter alone.
+ * run       the next `epochs` epochs, clamped at n_epochs; *epoch_after (nullable) = epochs done so far.  One launch per
+ *           epoch on the layout's own stream, one wait per call.
+ * A device failure poisons the layout handle only (CQS_HIP_ERR_POISONED afterwards).  Calls on one handle serialise. */
+typedef struct cqs_hip_layout cqs_hip_layout;
+typedef struct cqs_hip_layout_params {
+    float a;                   /* 1.5769434603 with b = 0.8950608779: umap-learn's fit for min_dist 0.1, spread 1 */
+    float b;
+    float learning_rate;       /* 1.0 */
+    float repulsion;           /* 1.0 */
+    uint32_t negative_samples; /* 5 */
+    uint32_t n_epochs;         /* 0: 500 for n <= 10000, 200 above */
+    uint64_t seed;             /* 42 */
+} cqs_hip_layout_params;
+void cqs_hip_layout_params_default(cqs_hip_layout_params* params);
+int32_t cqs_hip_layout_create(int32_t device, uint64_t n, uint32_t stride, const uint64_t* knn_rows,
+                              const float* knn_scores, const uint32_t* knn_counts, const cqs_hip_layout_params* params,
+                              cqs_hip_layout** out);
+uint64_t cqs_hip_layout_len(const cqs_hip_layout* layout);
+uint64_t cqs_hip_layout_edges(const cqs_hip_layout* layout);
+uint32_t cqs_hip_layout_epochs(const cqs_hip_layout* layout);
+int32_t cqs_hip_layout_graph(cqs_hip_layout* layout, uint64_t* offsets, uint32_t* nbrs, float* weights, float* rho,
+                             float* sigma, float* w_max);
+int32_t cqs_hip_layout_set_coords(cqs_hip_layout* layout, const float* xy);
+int32_t cqs_hip_layout_coords(cqs_hip_layout* layout, float* xy);
+int32_t cqs_hip_layout_run(cqs_hip_layout* layout, uint32_t epochs, uint32_t* epoch_after);
+size_t cqs_hip_layout_last_error(const cqs_hip_layout* layout, char* buf, size_t cap);
+void cqs_hip_layout_destroy(cqs_hip_layout* layout);
+/* The two halves in one call, for a caller that has the index and wants the coordinates: cqs_hip_index_knn_graph at
+ * limit n_neighbors - 1 (clamped to [1, CQS_HIP_NEIGHBORS_MAX]) over the whole corpus in calls of 4096 targets - the
+ * index is held per call, not for the whole length - then a layout with the default parameters but n_epochs and seed,
+ * run to its end on the index's device.  out_xy [len * 2] f32, host.  Fewer than 2 rows give the origin.  Refuses what
+ * cqs_hip_index_knn_graph refuses (a row-sharded handle among it) and a handle whose row_base is not 0; the reason is in
+ * the index's last_error. */
+int32_t cqs_hip_index_umap_project(cqs_hip_index* idx, uint32_t n_neighbors, uint32_t n_epochs, uint64_t seed,
+                                   float* out_xy);
+
 /* ---- semantic diff of two resident indexes --------------------------------------
  * The arithmetic of `semantic_diff` (src/diff.rs:99-246; `detect_drift`, src/drift.rs:51-120, sits on it): for every
  * chunk present in both stores the reference fetches both embeddings from SQLite in batches of 1000, computes

@@ -70,6 +70,9 @@ extern "C" {
                                out_scores: *mut f32, out_count: *mut u32) -> i32;
     fn cqs_hip_index_knn_graph(idx: *mut CqsHipIndex, first_row: u64, m: u64, limit: u32, out_rows: *mut u64,
                                out_scores: *mut f32, out_counts: *mut u32) -> i32;
+    // `cqs index --umap` on the resident corpus: the kNN graph, then the layout handle (its own opaque type on the C side;
+    // this one call is all the shim needs of it), run to its end
+    fn cqs_hip_index_umap_project(idx: *mut CqsHipIndex, n_neighbors: u32, n_epochs: u32, seed: u64, out_xy: *mut f32) -> i32;
     // semantic diff of two resident indexes (src/diff.rs:172-215: full_cosine_similarity of matched pairs, the threshold)
     fn cqs_hip_index_diff(a: *mut CqsHipIndex, rows_a: *const u64, b: *mut CqsHipIndex, rows_b: *const u64, m: u64,
                           threshold: f32, out_sims: *mut f32, out_mod_pairs: *mut u64, out_mod_sims: *mut f32,
@@ -636,6 +639,26 @@ impl HipIndex {
             first += m;
         }
         Some(graph)
+    }
+
+    /// `cqs index --umap` without the Python child (src/cli/commands/index/umap.rs): 2-D coordinates of every resident chunk,
+    /// (id, x, y) in `id_map` order - what the script's stdout is parsed into before `update_umap_coords_batch`.  The exact
+    /// kNN graph at `n_neighbors - 1` and umap-learn's layout rules (min_dist 0.1, the stated departures of cqs_hip.h) run
+    /// on the device; the index is held per graph call, not during the layout.  `n_epochs == 0` = 500 up to 10 000 chunks,
+    /// 200 above.  Fewer than 2 chunks give the origin, as the script does.  `None` = the device failed or the handle is
+    /// row-sharded: the caller keeps the script.
+    pub fn umap_project(&self, n_neighbors: usize, n_epochs: usize, seed: u64) -> Option<Vec<(String, f32, f32)>> {
+        let n = self.id_map.len();
+        let mut xy = vec![0f32; 2 * n.max(1)];
+        let rc = unsafe {
+            cqs_hip_index_umap_project(self.handle, n_neighbors.min(u32::MAX as usize) as u32,
+                                       n_epochs.min(u32::MAX as usize) as u32, seed, xy.as_mut_ptr())
+        };
+        if rc != CQS_HIP_OK {
+            tracing::warn!(error = %self.last_error(), rc, "HIP UMAP projection failed");
+            return None;
+        }
+        Some((0..n).map(|i| (self.id_map[i].to_string(), xy[2 * i], xy[2 * i + 1])).collect())
     }
 
     /// The embedding loop of `semantic_diff` (src/diff.rs:172-215) for matched pairs of two resident indexes: pair i is
