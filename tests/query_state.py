@@ -1,4 +1,4 @@
-"""Shared by tests/test_query_state_gpu.py and tests/test_query_state_sensitivity_cpu.py (test infrastructure, like
+"""Shared by tests/test_query_state_gpu.py, tests/test_query_state_sensitivity_cpu.py and tests/batch_state.py (test infrastructure, like
 shadow_emul.py): the per-token measures, their committed bounds, the oracle-side recording through
 `gemma3_ref.forward(tap=...)`, the planted errors, and a bf16-operand emulation of a correct device.
 
@@ -74,10 +74,15 @@ def record(cfg, w, ids, mask, plant=None):
     return rec
 
 
-def attn_from_qkv(cfg, w, layer, qkv, window_delta=0, late_from=None, mask_last_key_for=None, rnd=lambda a: a):
+def attn_from_qkv(cfg, w, layer, qkv, window_delta=0, late_from=None, mask_last_key_for=None, rnd=lambda a: a, leak=None):
     """The attention of `layer` restated from its (tapped) qkv rows [T, (nh + 2 nkv) D] -> [T, nh D], in float64, with
     switches for the errors a kernel can make: the window compare off by `window_delta`; keys at positions >= late_from
-    rotated one position late; the last key masked for the queries >= mask_last_key_for.  rnd rounds the MFMA operands."""
+    rotated one position late; the last key masked for the queries >= mask_last_key_for; leak = (qkv row of another
+    sequence, its position there, n): that row attended as one more key by the queries < n (a packed batch's neighbour
+    read past a sequence's end).  rnd rounds the MFMA operands."""
+    n_own = qkv.shape[0]
+    if leak is not None:
+        qkv = np.concatenate([qkv, np.asarray(leak[0], qkv.dtype)[None]], 0)     # (the row rides along as token T; dropped below)
     T = qkv.shape[0]
     D, nh, nkv = cfg.head_dim, cfg.heads, cfg.kv_heads
     p = f"layers.{layer}."
@@ -97,6 +102,8 @@ def attn_from_qkv(cfg, w, layer, qkv, window_delta=0, late_from=None, mask_last_
         return t * c + rot * s
 
     pos = np.arange(T, dtype=np.float64)
+    if leak is not None:
+        pos[-1] = float(leak[1])
     kpos = pos.copy()
     if late_from is not None:
         kpos[late_from:] -= 1.0
@@ -107,14 +114,20 @@ def attn_from_qkv(cfg, w, layer, qkv, window_delta=0, late_from=None, mask_last_
     allow = np.ones((T, T), bool) if full else dist < cfg.window + window_delta
     if mask_last_key_for is not None:
         allow = allow.copy()
-        allow[mask_last_key_for:, T - 1] = False               # (the last token loses itself too; it keeps its other keys)
+        allow[mask_last_key_for:, n_own - 1] = False           # (the last token loses itself too; it keeps its other keys)
+    if leak is not None:
+        allow = allow.copy()
+        allow[:, -1] = False
+        allow[-1, :] = False
+        allow[: leak[2], -1] = True
+        allow[-1, -1] = True
     out = np.zeros((T, nh, D))
     for h in range(nh):
         s = q[:, h] @ k[:, h // (nh // nkv)].T
         s = np.where(allow, s, -np.inf)
         e = rnd(np.exp(s - s.max(-1, keepdims=True)))
         out[:, h] = (e @ v[:, h // (nh // nkv)]) / e.sum(-1, keepdims=True)
-    return out.reshape(T, nh * D)
+    return out.reshape(T, nh * D)[:n_own]
 
 
 def forward_emulated(cfg, w, ids, rnd=G.round_bf16):
