@@ -248,16 +248,17 @@ class Tally:
     the worst figures were reported, so that one run shows all of them (CQS_BATCH_STATE_REPORT=<file> appends them as JSON
     lines: how the MEASURED table above was taken)."""
 
-    def __init__(self, name):
+    def __init__(self, name, bounds=None, tag="BSTATE", report_env="CQS_BATCH_STATE_REPORT"):
         self.name, self.worst, self.failed = name, {}, []
+        self.bounds, self.tag, self.report_env = BOUNDS if bounds is None else bounds, tag, report_env     # (bert_state.py brings its own table)
 
     def add(self, place, key, got, ref, what):
         m = Q.measures(got, ref)
         w0 = self.worst.setdefault((key, place), [0.0, 0.0, 0.0])
         for i in range(3):
             w0[i] = max(w0[i], m[i])
-        b = BOUNDS[key][place]
-        print("BSTATE-ROW %s %s %s 1-cos=%.3e elem=%.4f col=%.4f (bounds %.3e %.4f %.4f)" % (what, "/".join(key), place, *m, *b))
+        b = self.bounds[key][place]
+        print("%s-ROW %s %s %s 1-cos=%.3e elem=%.4f col=%.4f (bounds %.3e %.4f %.4f)" % (self.tag, what, "/".join(key), place, *m, *b))
         if not (m[0] < b[0] and m[1] < b[1] and m[2] < b[2]):
             self.failed.append((what, place, key, m, b))
         return m
@@ -266,9 +267,9 @@ class Tally:
         self.failed.append(what)
 
     def finish(self):
-        path = os.environ.get("CQS_BATCH_STATE_REPORT")
+        path = os.environ.get(self.report_env)
         for (key, place), m in sorted(self.worst.items()):
-            print("BSTATE %s %s %s 1-cos=%.3e elem=%.4f col=%.4f" % (self.name, "/".join(key), place, m[0], m[1], m[2]))
+            print("%s %s %s %s 1-cos=%.3e elem=%.4f col=%.4f" % (self.tag, self.name, "/".join(key), place, m[0], m[1], m[2]))
             if path:
                 with open(path, "a") as f:
                     f.write(json.dumps({"test": self.name, "key": list(key), "place": place, "one_minus_cos": m[0], "elem": m[1], "col": m[2]}) + "\n")
