@@ -27,6 +27,7 @@ MODE_PIPELINE = 1
 MAX_K = 1024
 NEIGHBORS_MAX = 100
 KNN_MAX_TARGETS = 65536
+TRANSFORM_ALL = 0xFFFFFFFF
 MMR_MAX = 1024
 
 _c_idx = C.c_void_p
@@ -102,6 +103,14 @@ SIGNATURES = [
     ("cqs_hip_layout_last_error", C.c_size_t, [_c_idx, C.c_char_p, C.c_size_t]),
     ("cqs_hip_layout_destroy", None, [_c_idx]),
     ("cqs_hip_index_umap_project", C.c_int32, [_c_idx, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p]),
+    ("cqs_hip_umap_transform", C.c_int32,
+     [C.c_int32, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
+      C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("cqs_hip_layout_transform", C.c_int32,
+     [_c_idx, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p,
+      C.c_void_p, C.c_void_p]),
+    ("cqs_hip_index_umap_transform", C.c_int32,
+     [_c_idx, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p]),
     ("cqs_hip_index_diff", C.c_int32,
      [_c_idx, C.c_void_p, _c_idx, C.c_void_p, C.c_uint64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("cqs_hip_index_pairwise", C.c_int32, [_c_idx, C.c_void_p, C.c_uint32, C.c_void_p]),

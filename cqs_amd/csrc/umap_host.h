@@ -81,7 +81,7 @@ struct Adjacency {
     std::vector<float> dist;      // [edges]
 };
 
-inline float distance_of(float score) {
+CQS_UMAP_HD inline float distance_of(float score) {
     const float d = 1.0f - score;
     return d > 0.f ? d : 0.f;     // (a NaN score gives 0)
 }

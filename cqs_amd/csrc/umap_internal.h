@@ -12,6 +12,7 @@
 struct cqs_hip_layout {
     mutable std::mutex mu;
     std::atomic<bool> poisoned{false};
+    std::atomic<int> inject_fail{0};   // test hook: the next transform fails as a device error would
     std::string last_error;
     int device = 0;
     hipStream_t stream = nullptr;
@@ -37,5 +38,10 @@ namespace cqs_umap {
 // Enqueues on st and waits; *w_max is the grid maximum (0 where edges == 0).
 hipError_t graph_weights(hipStream_t st, uint64_t n, uint64_t edges, const uint64_t* d_off, const uint32_t* d_cnt,
                          const uint32_t* d_nbr, const float* d_dist, float* d_rho, float* d_sigma, float* d_w, float* w_max);
+
+// What umap_transform.hip asks of umap_layout.hip: a handle's failure (text, and poison on a device error; caller holds
+// mu), and this thread's handle-less text, the one cqs_hip_layout_last_error(NULL, ..) returns.
+int32_t lfail(cqs_hip_layout* x, int32_t code, const char* what, hipError_t e = hipSuccess);
+void set_handleless_error(const char* text);
 
 }  // namespace cqs_umap

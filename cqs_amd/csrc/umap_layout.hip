@@ -83,7 +83,9 @@ __global__ __launch_bounds__(64 * kEpochWaves) void layout_epoch_kernel(const Ep
 // ---- the handle ----------------------------------------------------------------------------------------------------------
 static thread_local std::string t_create_error;   // why this thread's last `create` was refused
 
-static int32_t lfail(cqs_hip_layout* x, int32_t code, const char* what, hipError_t e = hipSuccess) {
+void set_handleless_error(const char* text) { t_create_error = text; }
+
+int32_t lfail(cqs_hip_layout* x, int32_t code, const char* what, hipError_t e) {
     char buf[512];
     if (e != hipSuccess) snprintf(buf, sizeof buf, "%s: %s (%s)", what, hipGetErrorString(e), hipGetErrorName(e));
     else snprintf(buf, sizeof buf, "%s", what);

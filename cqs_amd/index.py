@@ -814,6 +814,27 @@ class HipIndex(VectorIndex):
             lay.run()
             return lay.coords()
 
+    def umap_transform(self, xy, vectors, n_neighbors: int = 15, n_epochs: Optional[int] = None, seed: int = 42) -> np.ndarray:
+        """`cqs_hip_index_umap_transform`: coordinates f32 [m, 2] for the new `vectors` [m, dim] in the layout `xy`
+        [n_anchors, 2] of this index's first n_anchors rows, which do not move: each vector's `n_neighbors` nearest of
+        those rows (the rows appended since, by `extend`, are masked out), then umap-learn's transform rules in one launch
+        (include/cqs_hip.h "UMAP transform of new rows").  Call it after `extend` of new chunks - or before - and store the
+        pairs beside the old ones.  Raises HipError on a row-sharded handle, a row_base other than 0 or more anchors than
+        rows."""
+        a = np.ascontiguousarray(xy, dtype=np.float32)
+        v = np.ascontiguousarray(vectors, dtype=np.float32)
+        if a.ndim != 2 or a.shape[1] != 2:
+            raise ValueError("umap_transform: xy is [n_anchors, 2]")
+        if v.ndim != 2 or v.shape[1] != self.dim():
+            raise ValueError("umap_transform: vectors must be [m, dim]")
+        m = v.shape[0]
+        out = np.zeros((m, 2), dtype=np.float32)
+        rc = self._lib.cqs_hip_index_umap_transform(self._h, a.shape[0], _ptr(a), _ptr(v), m, max(0, min(int(n_neighbors), 2**32 - 1)),
+                                                    0 if n_epochs is None else int(n_epochs), int(seed), _ptr(out))
+        if rc != _lib.OK:
+            raise HipError(rc, self.last_error())
+        return out
+
     def umap_project_by_id(self, n_neighbors: int = 15, n_epochs: Optional[int] = None, seed: int = 42,
                            rows_per_call: int = 4096) -> List[Tuple[str, float, float]]:
         """`umap_project` by chunk id, in row order: (id, x, y) - the triples the reference's script answers with."""

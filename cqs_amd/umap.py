@@ -2,7 +2,11 @@
 
 The second half of `cqs index --umap` (src/cli/commands/index/umap.rs): the fuzzy-simplicial-set weights of the graph that
 `HipIndex.knn_graph_rows` returns, and the epochs of force-directed layout.  The layout is its own handle: it takes the
-graph, not the index, and holds no index while it runs.  `HipIndex.umap_project` is the two halves in one call."""
+graph, not the index, and holds no index while it runs.  `HipIndex.umap_project` is the two halves in one call.
+
+`transform` / `HipLayout.transform` place new rows among coordinates that exist and do not move (include/cqs_hip.h, "UMAP
+transform of new rows"): weights, initial position and all epochs in one launch.  `HipIndex.umap_transform` is the
+neighbour search and that in one call."""
 from __future__ import annotations
 
 import ctypes as C
@@ -112,6 +116,75 @@ class HipLayout:
         todo = self.n_epochs if epochs is None else max(0, min(int(epochs), 2**32 - 1))
         self._check(self._lib.cqs_hip_layout_run(self._h, todo, C.byref(after)))
         return int(after.value)
+
+
+    def transform(self, rows, scores, counts, id_base: Optional[int] = None, epochs: Optional[int] = None,
+                  n_epochs: int = 0, want_weights: bool = False):
+        """`cqs_hip_layout_transform`: coordinates f32 [m, 2] of m new vertices among this layout's current coordinates,
+        which stay where they are (and on the device).  `rows` / `scores` [m, stride] and `counts` [m] are what
+        `search_batch` of the new vectors at k = n_neighbors over the anchored rows returns; `id_base` (default: `len`) is
+        the first new vertex's future row number; `epochs` runs only that many of the `n_epochs` epochs (0: the default
+        for m).  With `want_weights` returns (xy, sigma f32 [m], weights f32 [m, stride])."""
+        r, s, c = _lists(rows, scores, counts, "HipLayout.transform")
+        first = len(self) if id_base is None else int(id_base)
+        call = lambda at, stop, E, xy, sg, w: self._check(self._lib.cqs_hip_layout_transform(
+            self._h, stop - at, r.shape[1], _ptr(r[at:stop]), _ptr(s[at:stop]), _ptr(c[at:stop]), E, first + at, _todo(epochs),
+            _ptr(xy[at:stop]), None if sg is None else _ptr(sg[at:stop]), None if w is None else _ptr(w[at:stop])))
+        return _in_calls(call, r, int(n_epochs), want_weights)
+
+
+def _lists(rows, scores, counts, who):
+    r = np.ascontiguousarray(rows, dtype=np.uint64)
+    s = np.ascontiguousarray(scores, dtype=np.float32)
+    c = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+    if r.ndim != 2 or s.shape != r.shape or c.shape[0] != r.shape[0]:
+        raise ValueError(f"{who}: rows and scores are [m, stride], counts is [m]")
+    return r, s, c
+
+
+def _todo(epochs: Optional[int]) -> int:
+    return _lib.TRANSFORM_ALL if epochs is None else max(0, min(int(epochs), _lib.TRANSFORM_ALL))
+
+
+def _in_calls(call, r, n_epochs: int, want_weights: bool):
+    """m new vertices in calls of at most 65536 with matching ids.  A vertex's answer does not depend on the cut; the
+    default epoch count does depend on m, so it is fixed here for the whole of it."""
+    m = r.shape[0]
+    E = n_epochs if n_epochs or m == 0 else (100 if m <= 10000 else 30)
+    xy = np.zeros((m, 2), dtype=np.float32)
+    sigma = np.zeros((m,), dtype=np.float32) if want_weights else None
+    weights = np.zeros(r.shape, dtype=np.float32) if want_weights else None
+    for at in range(0, m, _lib.KNN_MAX_TARGETS):
+        call(at, min(m, at + _lib.KNN_MAX_TARGETS), E, xy, sigma, weights)
+    return (xy, sigma, weights) if want_weights else xy
+
+
+def transform(anchors_xy, rows, scores, counts, id_base: Optional[int] = None, epochs: Optional[int] = None,
+              device: int = 0, want_weights: bool = False, **params):
+    """`cqs_hip_umap_transform`, the handle-less transform: coordinates f32 [m, 2] of m new vertices among the fixed
+    `anchors_xy` [n, 2] (uploaded per call).  Lists, `id_base` (default: n) and `epochs` as `HipLayout.transform` takes
+    them; keyword arguments override the fields of `default_params()`.  Raises `HipError` with the refusal's text."""
+    lib = _lib.load()
+    a = np.ascontiguousarray(anchors_xy, dtype=np.float32)
+    if a.ndim != 2 or a.shape[1] != 2:
+        raise ValueError("transform: anchors_xy is [n, 2]")
+    r, s, c = _lists(rows, scores, counts, "transform")
+    p = default_params()
+    for k, v in params.items():
+        if not hasattr(p, k):
+            raise TypeError(f"transform: no parameter {k!r}")
+        setattr(p, k, v)
+    first = a.shape[0] if id_base is None else int(id_base)
+
+    def call(at, stop, E, xy, sg, w):
+        p.n_epochs = E
+        rc = lib.cqs_hip_umap_transform(int(device), a.shape[0], _ptr(a), stop - at, r.shape[1], _ptr(r[at:stop]), _ptr(s[at:stop]),
+                                        _ptr(c[at:stop]), C.byref(p), first + at, _todo(epochs), _ptr(xy[at:stop]),
+                                        None if sg is None else _ptr(sg[at:stop]), None if w is None else _ptr(w[at:stop]))
+        if rc != _lib.OK:
+            raise HipError(rc, _create_error(lib))
+
+    return _in_calls(call, r, int(p.n_epochs), want_weights)
 
 
 def _create_error(lib) -> str:

@@ -381,6 +381,71 @@ void cqs_hip_layout_destroy(cqs_hip_layout* layout);
 int32_t cqs_hip_index_umap_project(cqs_hip_index* idx, uint32_t n_neighbors, uint32_t n_epochs, uint64_t seed,
                                    float* out_xy);
 
+/* ---- UMAP transform of new rows ----------------------------------------------------
+ * The watch loop appends a few hundred chunks; this gives them coordinates in a layout that exists, without projecting the
+ * corpus again: umap-learn's `transform`, restated in the conventions of the layout section above, departures stated.
+ * The old coordinates - the anchors - do not move, so no new vertex depends on another: weights, initial position and all
+ * epochs of a vertex are the private loop of one wave, and the whole call is ONE launch.
+ * Input: n anchor coordinates Y [n * 2] f32 (x then y), fixed; for each of m new vertices a list of at most `stride` anchor
+ *   ids (< n) with raw dot scores and a count: vertex i owns nbr_rows[i*stride .. i*stride + nbr_counts[i]) and the same
+ *   range of nbr_scores (host) - what `search` of the new vectors at k = n_neighbors over the anchored rows returns.  There
+ *   is no self entry: a new row is not an anchor.  Vertex i of the call has the id id_base + i, its future row number; the
+ *   id is used only in the hash.  Anchor coordinates are NOT checked for finiteness: a non-finite anchor gives non-finite
+ *   answers to the vertices that list or draw it.
+ * Weights, per vertex with c = its count:  d = max(0, 1 - score);  rho = 0 (umap-learn's transform runs with
+ *   local_connectivity - 1 = 0);  sigma from the layout's bisection with target = log2f(c) - c, not c + 1: the list holds
+ *   all n_neighbors entries - then sigma = max(sigma, 1e-3 * mean(d));  w_t = 1 where d_t <= 0, else expf(-d_t / sigma).
+ *   c == 0: the vertex is written as (0, 0) and never moves; so is one whose weights all underflow to 0 (scores far below
+ *   -1: not unit rows).
+ * Initial position: W = sum of w_t, q_t = w_t / W, y = sum of q_t * Y[j_t], each quotient and each product rounded once,
+ *   the sums in the wave order below.
+ * Epoch e = 1 .. E (E = n_epochs, or where that is 0, 100 for m <= 10000 and 30 above: umap-learn's transform defaults):
+ *     alpha = (learning_rate / 4) * (1 - (e - 1) / E)
+ *     entry t is active iff floorf(e * p) != floorf((e - 1) * p) with p = w_t / (the vertex's own largest w) - stated
+ *       departure: umap-learn divides by the maximum over the whole batch; the per-vertex maximum makes a vertex's answer a
+ *       function of the anchors, its own list and its id only, not of how the caller batches
+ *     for each active entry, slot t and anchor j: clip(ca * (y - Y_j)) ONCE (the edge exists in one direction and only its
+ *       head moves), then for each draw k < negative_samples, q = draw_vertex(hash(seed, e, id, t, k), n):
+ *       clip(cr * (y - Y_q)).  ca, cr, clip and the hash are the layout's; a term is 0 where d2 == 0.
+ *     y_new = y + alpha * sum, the sum taken at the epoch's starting y - stated departure, as in the layout: umap-learn
+ *       re-reads y after every edge.
+ * Order of addition (part of the contract): lane l of 64 holds the slots l and l + 64; it adds slot l's attraction, then
+ *   slot l's draws 0, 1, .., then slot l + 64 likewise; the lanes then add as v += v[lane ^ 32], ^ 16, ^ 8, ^ 4, ^ 2, ^ 1.
+ * Determinism: a vertex's answer is a function of the anchors, its list, its id and the parameters.  One call of m and two
+ *   calls cut anywhere with matching id_base give the same bytes.
+ * `epochs` is how many of the E epochs to run, clamped at E: CQS_HIP_TRANSFORM_ALL runs all of them, 0 returns the initial
+ *   positions.  out_xy [m * 2]; out_sigma [m] and out_weights [m * stride] (slots past a count written as 0) are nullable.
+ * Refused with CQS_HIP_ERR_INVALID, the outputs untouched, in this order: NULL params, or out_xy, an array or the anchors
+ *   NULL while m > 0; (m == 0 returns CQS_HIP_OK here;) n == 0; n > 2^31; m > CQS_HIP_KNN_MAX_TARGETS; id_base + m > 2^32;
+ *   stride == 0 or stride > CQS_HIP_NEIGHBORS_MAX; a count greater than stride; a neighbour id >= n (the text names the
+ *   vertex); the layout's parameter checks, n_epochs > 10000 among them.
+ * cqs_hip_umap_transform          the handle-less call, for a daemon that keeps its coordinates in SQLite: uploads 8 n bytes
+ *           per call; refusals and failures are in this thread's handle-less text, cqs_hip_layout_last_error(NULL, ..).
+ * cqs_hip_layout_transform        the anchors are the handle's current coordinates where they lie on the device: nothing is
+ *           uploaded but the lists.  n is the handle's length; the parameters are the handle's, except n_epochs (0: the
+ *           default for m).  The handle's coordinates and epoch counter do not change; the new vertices do not join the
+ *           layout.  The reason of a refusal is the handle's last_error; a device failure poisons the layout only.
+ * cqs_hip_index_umap_transform    `search` of `vectors` [m * dim] at k = clamp(n_neighbors, 1, CQS_HIP_NEIGHBORS_MAX) over
+ *           the rows [0, n_anchors) - the plain search where n_anchors == len, else the filtered one with a keep-bitset of
+ *           the first n_anchors rows, so it also works after `extend` - in blocks of at most 256 queries, the index held per
+ *           block; then the transform on the index's device with id_base = n_anchors and the default parameters but
+ *           n_epochs and seed.  anchors_xy [n_anchors * 2], out_xy [m * 2], host.  A vector of the wrong kind (non-finite)
+ *           finds no neighbours and lands on (0, 0).  Refuses a row-sharded handle, a row_base other than 0 and
+ *           n_anchors > len, as umap_project does, and m > CQS_HIP_KNN_MAX_TARGETS; the reason is in the index's
+ *           last_error and the index is not poisoned by a transform's failure. */
+#define CQS_HIP_TRANSFORM_ALL 0xFFFFFFFFu
+int32_t cqs_hip_umap_transform(int32_t device, uint64_t n, const float* anchors_xy, uint64_t m, uint32_t stride,
+                               const uint64_t* nbr_rows, const float* nbr_scores, const uint32_t* nbr_counts,
+                               const cqs_hip_layout_params* params, uint64_t id_base, uint32_t epochs,
+                               float* out_xy /*[m*2]*/, float* out_sigma /*[m], nullable*/,
+                               float* out_weights /*[m*stride], nullable*/);
+int32_t cqs_hip_layout_transform(cqs_hip_layout* layout, uint64_t m, uint32_t stride, const uint64_t* nbr_rows,
+                                 const float* nbr_scores, const uint32_t* nbr_counts, uint32_t n_epochs, uint64_t id_base,
+                                 uint32_t epochs, float* out_xy, float* out_sigma, float* out_weights);
+int32_t cqs_hip_index_umap_transform(cqs_hip_index* idx, uint64_t n_anchors, const float* anchors_xy,
+                                     const float* vectors, uint64_t m, uint32_t n_neighbors, uint32_t n_epochs, uint64_t seed,
+                                     float* out_xy);
+
 /* ---- semantic diff of two resident indexes --------------------------------------
  * The arithmetic of `semantic_diff` (src/diff.rs:99-246; `detect_drift`, src/drift.rs:51-120, sits on it): for every
  * chunk present in both stores the reference fetches both embeddings from SQLite in batches of 1000, computes

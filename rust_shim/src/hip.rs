@@ -73,6 +73,9 @@ extern "C" {
     // `cqs index --umap` on the resident corpus: the kNN graph, then the layout handle (its own opaque type on the C side;
     // this one call is all the shim needs of it), run to its end
     fn cqs_hip_index_umap_project(idx: *mut CqsHipIndex, n_neighbors: u32, n_epochs: u32, seed: u64, out_xy: *mut f32) -> i32;
+    // ... and coordinates for rows appended since, among the stored ones, which stay where they are
+    fn cqs_hip_index_umap_transform(idx: *mut CqsHipIndex, n_anchors: u64, anchors_xy: *const f32, vectors: *const f32, m: u64,
+                                    n_neighbors: u32, n_epochs: u32, seed: u64, out_xy: *mut f32) -> i32;
     // semantic diff of two resident indexes (src/diff.rs:172-215: full_cosine_similarity of matched pairs, the threshold)
     fn cqs_hip_index_diff(a: *mut CqsHipIndex, rows_a: *const u64, b: *mut CqsHipIndex, rows_b: *const u64, m: u64,
                           threshold: f32, out_sims: *mut f32, out_mod_pairs: *mut u64, out_mod_sims: *mut f32,
@@ -659,6 +662,34 @@ impl HipIndex {
             return None;
         }
         Some((0..n).map(|i| (self.id_map[i].to_string(), xy[2 * i], xy[2 * i + 1])).collect())
+    }
+
+    /// Coordinates for new chunks in a projection that exists, without projecting the corpus again: `anchors_xy` holds the
+    /// stored (x, y) of the first `anchors_xy.len()` resident chunks in `id_map` order - what `umap_project` returned and
+    /// `update_umap_coords_batch` wrote - and `vectors` the new embeddings, `dim` floats each, before or after they were
+    /// appended with `extend`.  Each new row's `n_neighbors` nearest anchors are searched on the device (rows past the
+    /// anchors are masked out) and umap-learn's `transform` rules place it among them in one launch; the anchors do not
+    /// move.  `n_epochs == 0` = 100 up to 10 000 new rows, 30 above.  Returns one (x, y) per new row, in order.  `None` =
+    /// the device failed, the handle is row-sharded, or there are more anchors than resident chunks: the caller projects
+    /// again.
+    pub fn umap_transform(&self, anchors_xy: &[(f32, f32)], vectors: &[f32], n_neighbors: usize, n_epochs: usize, seed: u64)
+                          -> Option<Vec<(f32, f32)>> {
+        if self.dim == 0 || vectors.len() % self.dim != 0 {
+            return None;
+        }
+        let m = vectors.len() / self.dim;
+        let flat: Vec<f32> = anchors_xy.iter().flat_map(|&(x, y)| [x, y]).collect();
+        let mut xy = vec![0f32; 2 * m.max(1)];
+        let rc = unsafe {
+            cqs_hip_index_umap_transform(self.handle, anchors_xy.len() as u64, flat.as_ptr(), vectors.as_ptr(), m as u64,
+                                         n_neighbors.min(u32::MAX as usize) as u32, n_epochs.min(u32::MAX as usize) as u32,
+                                         seed, xy.as_mut_ptr())
+        };
+        if rc != CQS_HIP_OK {
+            tracing::warn!(error = %self.last_error(), rc, "HIP UMAP transform failed");
+            return None;
+        }
+        Some((0..m).map(|i| (xy[2 * i], xy[2 * i + 1])).collect())
     }
 
     /// The embedding loop of `semantic_diff` (src/diff.rs:172-215) for matched pairs of two resident indexes: pair i is
