@@ -186,7 +186,7 @@ SIGNATURES = [
     ("cqs_hip_sparse_index_last_error", C.c_size_t, [_c_idx, C.c_char_p, C.c_size_t]),
 ]
 
-# Test hooks the library exports beside the header's symbols (embedder.hip, index_remove.hip, index_update.hip, index_diff.hip, index_tags.hip, index_combine.hip; not part of
+# Test hooks the library exports beside the header's symbols (embedder_debug.hip, index_remove.hip, index_update.hip, index_diff.hip, index_tags.hip, index_combine.hip; not part of
 # include/cqs_hip.h).
 DEBUG_SIGNATURES = [
     ("cqs_hip_debug_index_tag_keep", C.c_int32, [_c_idx, C.c_void_p, C.c_void_p]),

@@ -6,6 +6,7 @@
 #include "../../include/cqs_hip.h"
 #include "abi_guard.h"
 #include "roctx.h"
+#include "batch_tables.h"
 #include "bert_kernels.h"
 #include "onnx_reader.h"
 #include "safetensors_reader.h"
@@ -64,7 +65,7 @@ struct cqs_hip_bert {
 
     // Execution contexts (a HIP stream + the activation scratch of one batch each; weights shared): consecutive tickets
     // alternate, so batch i + 1's kernel chain fills the CUs batch i's leaves idle and its H2D / host packing overlap
-    // batch i's compute - the submit / collect scheme of the EmbeddingGemma engine (embedder.hip), which the reference's
+    // batch i's compute - the submit / collect scheme of the EmbeddingGemma engine (embedder_run.hip), which the reference's
     // index pipeline needs from the SPLADE encoder just as well (src/splade/mod.rs:774-1075 is called per batch from it).
     struct Ctx {
         hipStream_t stream = nullptr;
@@ -74,7 +75,8 @@ struct cqs_hip_bert {
         uint32_t *sp_ids = nullptr, *sp_cnt = nullptr;  // device-side threshold filter: [sp_rows * sp_cap] ids / weights, [sp_rows] counts
         float* sp_w = nullptr;
         size_t sp_rows = 0, sp_cap = 0;
-        int32_t* d_meta = nullptr;
+        int32_t* d_meta = nullptr;                // the batch's integer tables (batch_tables.h, BERT kind), sized for the capacities,
+        cqs::BatchTables<const int32_t> tb;       // and that block carved for the batch it holds (run_encoder)
     };
     static constexpr int kCtx = 2;
     Ctx ctx[kCtx];
@@ -83,8 +85,8 @@ struct cqs_hip_bert {
         uint64_t ticket = 0;         // 0 = free
         int kind = 0;                // 1 = sparse SPLADE vectors, 2 = pooled embeddings
         int ctx = 0;
-        uint32_t B = 0, M = 0, cap = 0, nblk = 0;
-        int32_t* meta = nullptr;     // pinned: [tok M][pos M][tt M][seq_start B][seq_len B][blk 2 nblk][row_seq M]
+        uint32_t B = 0, cap = 0;
+        int32_t* meta = nullptr;     // pinned twin of d_meta
         size_t meta_cap = 0;         // int32 elements
         void* out = nullptr;         // pinned results: kind 1: ids [B cap] u32 | weights [B cap] f32 | counts [B] u32; kind 2: [B, H] f32
         size_t out_cap = 0;          // bytes
@@ -158,6 +160,7 @@ void free_scratch(BCtx& c) {
     for (void** p : all) { (void)hipFree(*p); *p = nullptr; }
     (void)hipFree(c.sp_ids); (void)hipFree(c.sp_w); (void)hipFree(c.sp_cnt);
     c.sp_ids = c.sp_cnt = nullptr; c.sp_w = nullptr; c.sp_rows = c.sp_cap = 0;
+    c.tb = {};
     c.tok_cap = c.seq_cap = c.blk_cap = 0;
 }
 
@@ -182,31 +185,32 @@ int32_t ensure_scratch(cqs_hip_bert* e, BCtx& c, uint32_t M, uint32_t B, uint32_
         B_TRY(e, hipMalloc((void**)&c.pooled, (size_t)Bc * H * 2));
         B_TRY(e, hipMalloc((void**)&c.cls, (size_t)Bc * 16 * 4));
     }
-    B_TRY(e, hipMalloc((void**)&c.d_meta, ((size_t)4 * Mc + (size_t)2 * Bc + (size_t)2 * bc) * 4));
+    B_TRY(e, hipMalloc((void**)&c.d_meta, cqs::table_words(cqs::BATCH_BERT, {Bc, Mc, bc, 0}) * sizeof(int32_t)));
     c.tok_cap = Mc; c.seq_cap = Bc; c.blk_cap = bc;
     return CQS_HIP_OK;
 }
 
 // Validate + pack a ragged batch into the slot's pinned tables, upload them, run the encoder on context `c`; leaves the
-// final hidden states in c.x.
+// final hidden states in c.x and the batch's device tables in c.tb.
 int32_t run_encoder(cqs_hip_bert* e, BCtx& c, BSlot& sl, const int32_t* tokens, const int32_t* type_ids, const uint32_t* lens, uint32_t B,
                     uint32_t* M_out) {
     const cqs_hip_bert_config& cf = e->cfg;
-    uint64_t M64 = 0, nblk64 = 0;
-    uint32_t max_len = 0;
-    for (uint32_t b = 0; b < B; ++b) {
-        if (lens[b] > cf.max_pos) return bfail(e, CQS_HIP_ERR_INVALID, "bert: sequence longer than max_position_embeddings");
-        M64 += lens[b];
-        nblk64 += (lens[b] + 63u) / 64u;
-        max_len = std::max(max_len, lens[b]);
-    }
-    if (M64 > 0x7FFFFFFFull) return bfail(e, CQS_HIP_ERR_INVALID, "bert: batch holds too many tokens");
-    const uint32_t M = (uint32_t)M64, nblk = (uint32_t)nblk64;
+    constexpr cqs::BatchKind kKind = cqs::BATCH_BERT;
+    auto refuse = [&](cqs::BatchCode code) {      // batch_tables.h's refusals as this engine's errors
+        const char* what = code == cqs::BATCH_TOO_LONG          ? "bert: sequence longer than max_position_embeddings"
+                           : code == cqs::BATCH_TOO_MANY_TOKENS ? "bert: batch holds too many tokens"
+                           : code == cqs::BATCH_BAD_TYPE        ? "bert: token type id out of range"
+                                                                : "bert: token id out of range";
+        return code == cqs::BATCH_OK ? CQS_HIP_OK : bfail(e, CQS_HIP_ERR_INVALID, what);
+    };
+    cqs::BatchShape s;
+    int32_t rc = refuse(cqs::batch_shape(kKind, lens, B, cf.max_pos, &s));
+    if (rc != CQS_HIP_OK) return rc;
+    const uint32_t M = s.M, nblk = s.nblk, max_len = B ? *std::max_element(lens, lens + B) : 0u;
     *M_out = M;
-    sl.B = B; sl.M = M; sl.nblk = nblk;
+    sl.B = B;
     if (M == 0) return CQS_HIP_OK;
-    // tables: [tok M][pos M][tt M][seq_start B][seq_len B][blk 2 nblk][row_seq M]
-    const size_t words = (size_t)4 * M + (size_t)2 * B + (size_t)2 * nblk;
+    const size_t words = cqs::table_words(kKind, s);
     if (words > sl.meta_cap) {
         if (sl.meta) (void)hipHostFree(sl.meta);
         sl.meta = nullptr; sl.meta_cap = 0;
@@ -214,30 +218,17 @@ int32_t run_encoder(cqs_hip_bert* e, BCtx& c, BSlot& sl, const int32_t* tokens, 
         B_TRY(e, hipHostMalloc((void**)&sl.meta, cap * sizeof(int32_t), hipHostMallocDefault));
         sl.meta_cap = cap;
     }
-    int32_t *tok = sl.meta, *pos = tok + M, *tt = pos + M, *seq_start = tt + M, *seq_len = seq_start + B, *blk = seq_len + B;
-    int32_t* row_seq = blk + (size_t)2 * nblk;
-    uint32_t m = 0, nb = 0;
-    for (uint32_t b = 0; b < B; ++b) {
-        seq_start[b] = (int32_t)m;
-        seq_len[b] = (int32_t)lens[b];
-        for (uint32_t j = 0; j < lens[b]; ++j) {
-            const int32_t id = tokens[m + j];
-            if (id < 0 || (uint32_t)id >= cf.vocab_size) return bfail(e, CQS_HIP_ERR_INVALID, "bert: token id out of range");
-            const int32_t ty = type_ids ? type_ids[m + j] : 0;
-            if (ty < 0 || (uint32_t)ty >= cf.type_vocab) return bfail(e, CQS_HIP_ERR_INVALID, "bert: token type id out of range");
-            tok[m + j] = id; pos[m + j] = (int32_t)j; tt[m + j] = ty; row_seq[m + j] = (int32_t)b;
-        }
-        for (uint32_t q = 0; q * 64u < lens[b]; ++q) { blk[2 * nb] = (int32_t)b; blk[2 * nb + 1] = (int32_t)q; ++nb; }
-        m += lens[b];
-    }
-    int32_t rc = ensure_scratch(e, c, M, B, nblk);
+    rc = refuse(cqs::fill_tables(kKind, cqs::carve(kKind, sl.meta, s), s, lens,
+                                 [&](uint32_t, uint32_t, uint32_t row) { return (int64_t)tokens[row]; },
+                                 [&](uint32_t, uint32_t, uint32_t row) { return (int64_t)(type_ids ? type_ids[row] : 0); },
+                                 (int64_t)cf.vocab_size, (int64_t)cf.type_vocab));
+    if (rc == CQS_HIP_OK) rc = ensure_scratch(e, c, M, B, nblk);
     if (rc != CQS_HIP_OK) return rc;
     hipStream_t st = c.stream;
-    B_TRY(e, hipMemcpyAsync(c.d_meta, sl.meta, words * 4, hipMemcpyHostToDevice, st));
-    const int32_t *d_tok = c.d_meta, *d_pos = d_tok + M, *d_tt = d_pos + M, *d_start = d_tt + M, *d_len = d_start + B,
-                  *d_blk = d_len + B;
+    B_TRY(e, hipMemcpyAsync(c.d_meta, sl.meta, words * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    c.tb = cqs::carve<const int32_t>(kKind, c.d_meta, s);
     const uint32_t H = cf.hidden, I = cf.intermediate;
-    B_TRY(e, cqs::launch_bert_embed_ln(d_tok, d_pos, d_tt, e->word, e->posw, e->typew, e->emb_g, e->emb_b, cf.ln_eps, c.x, M, H, st));
+    B_TRY(e, cqs::launch_bert_embed_ln(c.tb.tok, c.tb.pos, c.tb.tt, e->word, e->posw, e->typew, e->emb_g, e->emb_b, cf.ln_eps, c.x, M, H, st));
     // Up to 64 tokens (a search-time query): 5 launches per layer instead of 7 - each residual add + LayerNorm runs in the
     // prologue of the projection that consumes it (launch_gemm_small_rows_addln: every workgroup normalises the rows it
     // multiplies; the stream alternates between two buffers because everybody reads the old one)
@@ -257,7 +248,7 @@ int32_t run_encoder(cqs_hip_bert* e, BCtx& c, BSlot& sl, const int32_t* tokens, 
                                                                3u * H, cqs::GEMM_OUT_BF16, st));
                     std::swap(cur, oth);
                 }
-                B_TRY(e, cqs::launch_bert_attention(c.qkv, c.att, d_blk, nblk, d_start, d_len, B, max_len, cf.heads, H / cf.heads, st));
+                B_TRY(e, cqs::launch_bert_attention(c.qkv, c.att, c.tb.blk, nblk, c.tb.seq_start, c.tb.seq_len, B, max_len, cf.heads, H / cf.heads, st));
                 B_TRY(e, cqs::launch_gemm_bias(c.att, w.wo, w.bo, c.y, M, H, H, H, cqs::GEMM_OUT_BF16, st));
                 B_TRY(e, cqs::launch_gemm_small_rows_addln(cur, c.y, w.ln1_g, w.ln1_b, cf.ln_eps, oth, w.w1, w.b1, c.h, M, I, H, I,
                                                            cqs::GEMM_OUT_BF16_GELU, st));
@@ -272,7 +263,7 @@ int32_t run_encoder(cqs_hip_bert* e, BCtx& c, BSlot& sl, const int32_t* tokens, 
     for (uint32_t l = 0; l < cf.layers; ++l) {
         const BertLayer& w = e->L[l];
         B_TRY(e, cqs::launch_gemm_bias(c.x, w.wqkv, w.bqkv, c.qkv, M, 3u * H, H, 3u * H, cqs::GEMM_OUT_BF16, st));
-        B_TRY(e, cqs::launch_bert_attention(c.qkv, c.att, d_blk, nblk, d_start, d_len, B, max_len, cf.heads, H / cf.heads, st));
+        B_TRY(e, cqs::launch_bert_attention(c.qkv, c.att, c.tb.blk, nblk, c.tb.seq_start, c.tb.seq_len, B, max_len, cf.heads, H / cf.heads, st));
         B_TRY(e, cqs::launch_gemm_bias(c.att, w.wo, w.bo, c.y, M, H, H, H, cqs::GEMM_OUT_BF16, st));
         B_TRY(e, cqs::launch_bert_add_ln(c.x, c.y, w.ln1_g, w.ln1_b, cf.ln_eps, c.x, M, H, st));
         B_TRY(e, cqs::launch_gemm_bias(c.x, w.w1, w.b1, c.h, M, I, H, I, cqs::GEMM_OUT_BF16_GELU, st));
@@ -301,12 +292,11 @@ int32_t take_slot(cqs_hip_bert* e, BSlot** sl, BCtx** c, bool reserved = false) 
         for (int i = 0; i < cqs_hip_bert::kSlots; ++i)
             if (e->slot[i].ticket == 0) { *sl = &e->slot[i]; break; }
     if (!*sl) return bfail(e, CQS_HIP_ERR_INVALID, "bert: every submission slot is in flight (collect a ticket first)");
-    // the context with fewer tickets in flight; ties alternate, an idle engine takes context 0 (one blocking call at a time
-    // keeps re-using ONE set of activation scratch instead of two taking turns in L2 / the Infinity Cache)
+    // the context with fewer tickets in flight; ties alternate, an idle engine takes context 0 (batch_tables.h)
     int load[cqs_hip_bert::kCtx] = {0, 0};
     for (const BSlot& s2 : e->slot)
         if (s2.ticket != 0) load[s2.ctx]++;
-    const int ci = load[0] == load[1] ? (load[0] == 0 ? 0 : 1 - e->last_ctx) : (load[0] < load[1] ? 0 : 1);
+    const int ci = cqs::pick_context(load[0], load[1], e->last_ctx);
     e->last_ctx = ci;
     (*sl)->ctx = ci;
     *c = &e->ctx[ci];
@@ -490,15 +480,13 @@ int32_t splade_forward(cqs_hip_bert* e, BCtx& c, BSlot& sl, const int32_t* token
     const size_t V = cf.vocab_size;
     hipStream_t st = c.stream;
     const uint32_t H = cf.hidden;
-    const int32_t* d_len = c.d_meta + (size_t)3 * M + batch;
     // BertLMPredictionHead: LayerNorm(gelu(x Wt^T + bt)) E^T + b, decoder tied to the (zero-padded) word embeddings.
     // The [tokens, vocab] logits are never stored: the decoder GEMM's epilogue keeps, per sequence and vocabulary
     // entry, the maximum of max(0, logit) (atomic max on the float bits), then one small pass takes ln(1 + .).
-    const int32_t* d_rowseq = d_len + batch + (size_t)2 * sl.nblk;
     B_TRY(e, cqs::launch_gemm_bias(c.x, e->wt, e->bt, c.y, M, H, H, H, cqs::GEMM_OUT_BF16_GELU, st));
     B_TRY(e, cqs::launch_bert_add_ln(c.y, nullptr, e->lnt_g, e->lnt_b, cf.ln_eps, c.y, M, H, st));
     B_TRY(e, hipMemsetAsync(c.dense, 0, (size_t)batch * V * 4, st));
-    B_TRY(e, cqs::launch_gemm_rowmax(c.y, e->word, e->bdec, (uint32_t*)c.dense, M, e->vpad, H, (uint32_t)V, d_rowseq, (uint32_t)V, st));
+    B_TRY(e, cqs::launch_gemm_rowmax(c.y, e->word, e->bdec, (uint32_t*)c.dense, M, e->vpad, H, (uint32_t)V, c.tb.row_seq, (uint32_t)V, st));
     B_TRY(e, cqs::launch_splade_activate(c.dense, (size_t)batch * V, st));
     return CQS_HIP_OK;
 }
@@ -655,8 +643,7 @@ int32_t cqs_hip_rerank_logits(cqs_hip_bert* e, const int32_t* tokens, const int3
     const uint32_t H = cf.hidden;
     // BertPooler on every sequence's first token (row seq_start[b] of the packed hidden states: the skinny GEMM reads its
     // rows through that table), dense + tanh, then the classifier (labels padded to 16).
-    const int32_t* d_start = c->d_meta + (size_t)3 * M;
-    B_TRY(e, cqs::launch_gemm_rows(c->x, H, e->wp, e->bp, 1, c->att, batch, H, H, H, cqs::GEMM_OUT_BF16, st, d_start));
+    B_TRY(e, cqs::launch_gemm_rows(c->x, H, e->wp, e->bp, 1, c->att, batch, H, H, H, cqs::GEMM_OUT_BF16, st, c->tb.seq_start));
     B_TRY(e, cqs::launch_gemm_rows(c->att, H, e->wc, e->bc, 0, c->cls, batch, 16, H, 16, cqs::GEMM_OUT_F32, st));
     std::vector<float> tmp((size_t)batch * 16);
     B_TRY(e, hipMemcpyAsync(tmp.data(), c->cls, tmp.size() * 4, hipMemcpyDeviceToHost, st));
@@ -699,8 +686,7 @@ int32_t cqs_hip_bert_embed_submit(cqs_hip_bert* e, const int32_t* tokens, const 
     if (M == 0) {
         memset(sl->out, 0, (size_t)batch * H * 4);                                   // every sequence empty: zero vectors
     } else {
-        const int32_t *d_start = c->d_meta + (size_t)3 * M, *d_len = d_start + batch;
-        B_TRY(e, cqs::launch_bert_pool(c->x, d_start, d_len, c->dense, batch, H, (int)pooling, st));
+        B_TRY(e, cqs::launch_bert_pool(c->x, c->tb.seq_start, c->tb.seq_len, c->dense, batch, H, (int)pooling, st));
         B_TRY(e, hipMemcpyAsync(sl->out, c->dense, (size_t)batch * H * 4, hipMemcpyDeviceToHost, st));
     }
     B_TRY(e, hipEventRecord(sl->done, st));

@@ -3,7 +3,7 @@
 // The reference embeds the query text on every search (`Embedder::embed_query`, src/embedder/core.rs:768-856, called at
 // src/cli/commands/search/query.rs:595; README.md:1079-1082 quotes ~3 ms on its CUDA EP).  At one sequence of 8-32 tokens
 // the forward is not a throughput problem: 2 x 101.5 M parameters are 212 MB of bf16 weights streamed once (~30 us at
-// HBM / Infinity-Cache rates) and ~10 MFLOP per token of matrix work.  The batch chain (embedder.hip: run_layers) serves
+// HBM / Infinity-Cache rates) and ~10 MFLOP per token of matrix work.  The batch chain (embedder_run.hip: run_layers) serves
 // that shape with 9-10 launches per layer, each a tile kernel built for 16 384 tokens: 230 dependent launches of 4-8 us,
 // 1.3 ms.  What bounds a kernel here is LATENCY: a launch boundary (~1.3 us, MI355X_MICROARCH.md price list
 // "boundary"), one round trip to L2 / MALL for the activations the previous kernel wrote, one for the weights.  So:

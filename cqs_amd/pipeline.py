@@ -113,7 +113,7 @@ class EmbedPipeline:
                 self._stats["chunks"] += len(sel)
                 self._stats["tokens"] += int(lens[sel].sum())
         except BaseException:
-            # A submission slot is freed only when its ticket is collected (embedder.hip: submit_locked / collect), and a
+            # A submission slot is freed only when its ticket is collected (embedder_run.hip: submit_locked / collect), and a
             # non-device failure (a token id out of range in ONE batch) does not poison the engine: without this drain
             # the tickets still in flight would strand their slots and every later call would fail with "every
             # submission slot is in flight" on an engine that still looks healthy.

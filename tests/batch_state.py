@@ -1,5 +1,5 @@
 """Shared by tests/test_batch_state_gpu.py and tests/test_batch_state_sensitivity_cpu.py (test infrastructure, next to
-query_state.py whose oracle-side helpers it reuses): the batch chain (`run_layers` in cqs_amd/csrc/embedder.hip) token by
+query_state.py whose oracle-side helpers it reuses): the batch chain (`run_layers` in cqs_amd/csrc/embedder_run.hip) token by
 token.  `HipEmbedEngine.run_hidden` returns the f32 final-norm row of every token of a packed ragged batch; the oracle
 side is built one sequence at a time.
 

@@ -1,4 +1,4 @@
-"""The batch chain (`run_layers` in cqs_amd/csrc/embedder.hip with embed_attention.hip, embed_gemm.hip, gemm_kernels.hip,
+"""The batch chain (`run_layers` in cqs_amd/csrc/embedder_run.hip with embed_attention.hip, embed_gemm.hip, gemm_kernels.hip,
 gemm_rowfuse.hip and embed_rows.hip) token by token, in every kernel form.  tests/test_embed_gpu.py holds it to the POOLED
 sentence vector (a mean over T tokens divides a one-row error by T) and ties its fused forms only to the unfused chain;
 here `HipEmbedEngine.run_hidden` - which runs `run_layers` and returns the f32 final-norm row of every token - is compared
