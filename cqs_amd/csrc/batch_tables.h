@@ -1,5 +1,5 @@
 // batch_tables.h — the packed int32 tables a batch travels to the device in, and the rule that picks a ticket's execution
-// context, for both transformer engines (embedder_run.hip, bert_engine.hip).  Header-only and device-free, so the engines and
+// context, for both transformer engines (embedder_run.hip, bert_run.hip).  Header-only and device-free, so the engines and
 // a CPU test (tests/batch_tables_driver.cpp) run the same functions.  One block per batch, pinned on the host and copied as it
 // is to the device:
 //   Gemma kind: [tok M][pos M][seq_start B][seq_len B][vt_start B][blk 2 nblk]                 (attention blocks of 128 rows)

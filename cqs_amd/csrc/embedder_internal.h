@@ -3,7 +3,8 @@
 // embedder_debug.hip (the cqs_hip_debug_* hooks).  Plays the role of the ORT `Session` inside the reference's `Embedder`
 // (src/embedder/core.rs:34-226, `session.run` at :1097): one engine per device, inference serialised behind a mutex
 // exactly like `Mutex<Option<Session>>` (core.rs:35-39), errors reported as status codes (-> `EmbedderError::InferenceFailed`,
-// src/embedder/mod.rs:36-60).
+// src/embedder/mod.rs:36-60).  Shared with the BERT-family engine (bert_internal.h): the ticket bookkeeping (ticket_pool.h)
+// and the failure rule, allocation helpers and bf16 rounding (engine_common.h).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -18,6 +19,8 @@
 #include "abi_guard.h"
 #include "batch_tables.h"
 #include "embed_kernels.h"
+#include "engine_common.h"
+#include "ticket_pool.h"
 
 namespace cqs_emb {
 
@@ -111,26 +114,23 @@ struct cqs_hip_embedder {
     uint64_t q_captured = 0, q_capture_failures = 0, q_replays = 0, q_eager = 0;
 
     // Submission slots (pinned host staging + events): batch i+1 is packed and enqueued while batch i computes;
-    // results come back through the slot's pinned `out` (cqs_hip_embed_submit / _collect).
+    // results come back through the slot's pinned `out` (cqs_hip_embed_submit / _collect).  Ticket, context and the
+    // collector of slot i: pool.slot[i] (ticket_pool.h).
     struct Slot {
         int32_t* meta = nullptr;   // pinned twin of d_meta, carved at `shape`
-        size_t meta_cap = 0;
+        size_t meta_cap = 0;       // bytes
         float* out = nullptr;      // pinned [B, hidden]
-        size_t out_cap = 0;        // floats
+        size_t out_cap = 0;        // bytes
         cqs::BatchShape shape;
         hipEvent_t ev0 = nullptr, ev1 = nullptr;   // forward start / end (timing), ev_done after the D2H
         hipEvent_t done = nullptr;
-        uint64_t ticket = 0;       // 0 = free
-        int ctx = 0;               // execution context the ticket runs on
         bool direct = false;       // the result is in the context's q_out_pin, not in `out`
-        bool collecting = false;   // a collect is waiting on this ticket: a second collector of the same ticket is refused
         bool batch_chain = false;  // the ticket ran the batch path (whose fused projections exchange row sums across workgroups)
         bool rerun = false;        // a pair exchange timed out while this ticket was in flight: recompute it at its collect
     };
     static constexpr int kSlots = 3;
     Slot slot[kSlots];
-    uint64_t next_ticket = 1;
-    int last_ctx = 1;              // context of the previous ticket (ties alternate)
+    cqs::TicketPool<kSlots, 0> pool;
 
     mutable std::mutex mu;
     std::atomic<bool> poisoned{false};
@@ -142,32 +142,11 @@ namespace cqs_emb {
 using Ctx = cqs_hip_embedder::Ctx;
 using Slot = cqs_hip_embedder::Slot;
 
-inline int32_t efail(cqs_hip_embedder* e, int32_t code, const std::string& what, hipError_t he = hipSuccess) {
-    std::string msg = what;
-    if (he != hipSuccess) msg += std::string(": ") + hipGetErrorString(he);
-    if (e) {
-        e->last_error = msg;
-        if (code == CQS_HIP_ERR_DEVICE) e->poisoned.store(true, std::memory_order_release);
-    }
-    return code;
-}
-#define E_TRY(e, expr)                                                                                  \
-    do {                                                                                                \
-        hipError_t _h = (expr);                                                                         \
-        if (_h != hipSuccess) return efail((e), _h == hipErrorOutOfMemory ? CQS_HIP_ERR_NOMEM : CQS_HIP_ERR_DEVICE, #expr, _h); \
-    } while (0)
-
-template <class T>
-hipError_t dmalloc(T** p, size_t count) { return hipMalloc((void**)p, count * sizeof(T)); }
+using cqs::dmalloc;
+using cqs::efail;
+using cqs::f32_to_bf16_bits;
 
 inline uint32_t nqkv(const cqs::EmbedGeom& g) { return (g.heads + 2u * g.kv_heads) * g.head_dim; }
-
-inline uint16_t f32_to_bf16_bits(float f) {
-    uint32_t u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7F800000u) == 0x7F800000u && (u & 0x007FFFFFu)) return (uint16_t)((u >> 16) | 0x0040u);  // keep NaN a NaN
-    return (uint16_t)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
-}
 
 // embedder_run.hip (cqs_hip_embedder_destroy gives a context's scratch back through them)
 void free_scratch(Ctx& c);

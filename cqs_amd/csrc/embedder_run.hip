@@ -1,6 +1,6 @@
 // embedder_run.hip — the EmbeddingGemma forward behind the C ABI (include/cqs_hip.h, embed section): a context's scratch, batch
-// packing (batch_tables.h), the batch chain, the search-time chain with its graph capture, and the submit / collect tickets.
-// The handle: embedder_internal.h; the weights: embedder.hip.
+// packing (batch_tables.h), the batch chain, the search-time chain with its graph capture, and the submit / collect tickets
+// (ticket_pool.h).  The handle: embedder_internal.h; the weights: embedder.hip.
 #include "embedder_internal.h"
 
 #include <algorithm>
@@ -69,21 +69,8 @@ int32_t ensure_scratch(cqs_hip_embedder* e, Ctx& c, const cqs::BatchShape& s) {
 
 // ---- batch packing into a submission slot ------------------------------------------------------------------
 int32_t slot_reserve(cqs_hip_embedder* e, Slot& sl, const cqs::BatchShape& s) {
-    const size_t need = cqs::table_words(kKind, s);
-    if (need > sl.meta_cap) {
-        if (sl.meta) (void)hipHostFree(sl.meta);
-        sl.meta = nullptr; sl.meta_cap = 0;
-        const size_t cap = need + need / 4 + 64;
-        E_TRY(e, hipHostMalloc((void**)&sl.meta, cap * sizeof(int32_t), hipHostMallocDefault));
-        sl.meta_cap = cap;
-    }
-    const size_t out_need = (size_t)s.B * e->g.hidden;
-    if (out_need > sl.out_cap) {
-        if (sl.out) (void)hipHostFree(sl.out);
-        sl.out = nullptr; sl.out_cap = 0;
-        E_TRY(e, hipHostMalloc((void**)&sl.out, (out_need + out_need / 4 + 64) * sizeof(float), hipHostMallocDefault));
-        sl.out_cap = out_need + out_need / 4 + 64;
-    }
+    E_TRY(e, cqs::grow_pinned(&sl.meta, &sl.meta_cap, cqs::table_words(kKind, s) * sizeof(int32_t)));
+    E_TRY(e, cqs::grow_pinned(&sl.out, &sl.out_cap, (size_t)s.B * e->g.hidden * sizeof(float)));
     if (!sl.ev0) {
         E_TRY(e, hipEventCreate(&sl.ev0));
         E_TRY(e, hipEventCreate(&sl.ev1));
@@ -310,12 +297,11 @@ int32_t enqueue_batch_chain(cqs_hip_embedder* e, Ctx& c, Slot& sl) {
     return CQS_HIP_OK;
 }
 
-// A slot with no ticket in flight; NULL (and last_error set) when there is none.
-Slot* free_slot(cqs_hip_embedder* e) {
-    for (Slot& s : e->slot)
-        if (s.ticket == 0) return &s;
-    (void)efail(e, CQS_HIP_ERR_INVALID, "embed: every submission slot is in flight (collect a ticket first)");
-    return nullptr;
+// The number of a slot with no ticket in flight; kNone (and last_error set) when there is none.
+int free_slot(cqs_hip_embedder* e) {
+    const int si = e->pool.take();
+    if (si == e->pool.kNone) (void)efail(e, CQS_HIP_ERR_INVALID, "embed: every submission slot is in flight (collect a ticket first)");
+    return si;
 }
 
 int32_t submit_locked(cqs_hip_embedder* e, uint32_t B, const std::function<int32_t(Slot&)>& pack, uint64_t* ticket) {
@@ -324,22 +310,17 @@ int32_t submit_locked(cqs_hip_embedder* e, uint32_t B, const std::function<int32
     if (!ticket) return efail(e, CQS_HIP_ERR_INVALID, "embed: null ticket");
     *ticket = 0;
     if (B == 0) return efail(e, CQS_HIP_ERR_INVALID, "embed: empty batch");
-    Slot* sl = free_slot(e);
-    if (!sl) return CQS_HIP_ERR_INVALID;
+    const int si = free_slot(e);
+    if (si == e->pool.kNone) return CQS_HIP_ERR_INVALID;
+    Slot* sl = &e->slot[si];
     E_TRY(e, hipSetDevice(e->device));
     int32_t rc = pack(*sl);
     if (rc != CQS_HIP_OK) return rc;
-    sl->batch_chain = false;
-    sl->rerun = false;
-    // the context with fewer tickets in flight, unless the batch fills the CUs on its own (batch_tables.h: both rules)
-    int load[cqs_hip_embedder::kCtx] = {0, 0};
-    for (const Slot& s2 : e->slot)
-        if (s2.ticket != 0) load[s2.ctx]++;
-    int ci = cqs::pick_context(load[0], load[1], e->last_ctx);
-    if (cqs::exact_rounds(sl->shape.M, e->n_cu)) ci = 0;
-    if (e->single_ctx) ci = 0;            // CQS_HIP_EMBED_CONTEXTS=1: every ticket on one stream (tickets still overlap host packing / copies)
-    e->last_ctx = ci;
-    sl->ctx = ci;
+    sl->direct = sl->batch_chain = sl->rerun = false;
+    // the context with fewer tickets in flight, unless the batch fills the CUs on its own (batch_tables.h: both rules) or
+    // CQS_HIP_EMBED_CONTEXTS=1 puts every ticket on one stream (tickets still overlap host packing / copies)
+    const auto chosen = e->pool.choose_context(si, cqs::exact_rounds(sl->shape.M, e->n_cu) || e->single_ctx);
+    const int ci = chosen.ctx;
     Ctx& c = e->ctx[ci];
     hipStream_t st = c.stream;
     const uint32_t H = e->g.hidden;
@@ -350,9 +331,9 @@ int32_t submit_locked(cqs_hip_embedder* e, uint32_t B, const std::function<int32
         E_TRY(e, hipEventRecord(sl->ev1, st));
         E_TRY(e, hipEventRecord(sl->done, st));
     } else if (slot_takes_query_path(e, *sl)) {
-        sl->direct = e->query_direct && load[ci] == 0;          // nothing else in flight on this context
+        sl->direct = e->query_direct && chosen.load[ci] == 0;   // nothing else in flight on this context
         rc = run_query(e, c, *sl, sl->direct);
-        if (rc != CQS_HIP_OK) { sl->direct = false; return rc; }
+        if (rc != CQS_HIP_OK) return rc;
         E_TRY(e, hipEventRecord(sl->ev1, st));
         if (!sl->direct) E_TRY(e, hipMemcpyAsync(sl->out, c.q_out, (size_t)H * sizeof(float), hipMemcpyDeviceToHost, st));
         E_TRY(e, hipEventRecord(sl->done, st));
@@ -361,8 +342,7 @@ int32_t submit_locked(cqs_hip_embedder* e, uint32_t B, const std::function<int32
         if (rc != CQS_HIP_OK) return rc;
         sl->batch_chain = true;
     }
-    sl->ticket = e->next_ticket++;
-    *ticket = sl->ticket;
+    *ticket = e->pool.publish(si, 0);
     return CQS_HIP_OK;
 }
 
@@ -391,22 +371,22 @@ int32_t cqs_hip_embed_submit_ragged(cqs_hip_embedder* e, const int32_t* tokens, 
 int32_t cqs_hip_embed_collect(cqs_hip_embedder* e, uint64_t ticket, float* out) CQS_ABI_TRY {
     CQS_ROCTX_RANGE("cqs_hip_embed_collect");
     if (!e) return CQS_HIP_ERR_INVALID;
-    Slot* sl = nullptr;
+    int si = 0;
     {
         std::lock_guard<std::mutex> lk(e->mu);
         if (ticket == 0) return efail(e, CQS_HIP_ERR_INVALID, "collect: null ticket");
-        for (Slot& c : e->slot)
-            if (c.ticket == ticket) { sl = &c; break; }
-        if (!sl) return efail(e, CQS_HIP_ERR_INVALID, "collect: unknown ticket");
-        if (sl->collecting) return efail(e, CQS_HIP_ERR_INVALID, "collect: this ticket is already being collected");
-        sl->collecting = true;
+        const cqs::CollectCode cc = e->pool.begin_collect(ticket, 0, &si);
+        if (cc == cqs::COLLECT_UNKNOWN) return efail(e, CQS_HIP_ERR_INVALID, "collect: unknown ticket");
+        if (cc == cqs::COLLECT_BUSY) return efail(e, CQS_HIP_ERR_INVALID, "collect: this ticket is already being collected");
     }
-    // wait outside the lock: other threads may submit meanwhile; the slot stays ours until its ticket is cleared
+    Slot* sl = &e->slot[si];
+    // wait outside the lock: other threads may submit meanwhile; the slot stays ours until the guard below lets it go
     (void)hipSetDevice(e->device);
     const hipError_t he = hipEventSynchronize(sl->done);
     std::lock_guard<std::mutex> lk(e->mu);
-    sl->collecting = false;
-    if (he != hipSuccess) { sl->ticket = 0; return efail(e, CQS_HIP_ERR_DEVICE, "collect: device failure", he); }
+    decltype(e->pool)::Collecting release{e->pool, si};
+    Ctx& c = e->ctx[e->pool.slot[si].ctx];
+    if (he != hipSuccess) return efail(e, CQS_HIP_ERR_DEVICE, "collect: device failure", he);
     if (e->fuse_err && *(volatile unsigned*)e->fuse_err != 0u) {
         // A pair of the fused projection kernel never met (gemm_rowfuse.hip: workgroup b waits for granules of workgroup
         // b ^ 8 of the same launch, which needs both resident - true on an otherwise idle device, not promised by HIP):
@@ -417,26 +397,23 @@ int32_t cqs_hip_embed_collect(cqs_hip_embedder* e, uint64_t ticket, float* out) 
         *(volatile unsigned*)e->fuse_err = 0u;
         e->fuse_norm = 0;
         e->fuse_fallbacks++;
-        for (Slot& c2 : e->slot)
-            if (c2.ticket != 0 && c2.batch_chain) c2.rerun = true;
+        e->pool.for_each_in_flight([&](int i) { if (e->slot[i].batch_chain) e->slot[i].rerun = true; });
     }
     if (sl->rerun) {
         sl->rerun = false;
-        int32_t rc = enqueue_batch_chain(e, e->ctx[sl->ctx], *sl);
+        int32_t rc = enqueue_batch_chain(e, c, *sl);
         if (rc == CQS_HIP_OK && hipEventSynchronize(sl->done) != hipSuccess) rc = efail(e, CQS_HIP_ERR_DEVICE, "collect: device failure in the recomputed batch");
-        if (rc != CQS_HIP_OK) { sl->ticket = 0; return rc; }
+        if (rc != CQS_HIP_OK) return rc;
     }
     const uint32_t H = e->g.hidden, B = sl->shape.B;
     if (out) {                         // out == NULL: abandon the ticket (wait, release the slot, drop the rows)
-        memcpy(out, sl->direct ? e->ctx[sl->ctx].q_out_pin : sl->out, (size_t)B * H * sizeof(float));
+        memcpy(out, sl->direct ? c.q_out_pin : sl->out, (size_t)B * H * sizeof(float));
         const int32_t* seq_len = cqs::carve<const int32_t>(kKind, sl->meta, sl->shape).seq_len;
         for (uint32_t b = 0; b < B; ++b)   // empty rows: exact zeros, like the reference's zero-mask pooling
             if (seq_len[b] == 0) memset(out + (size_t)b * H, 0, (size_t)H * sizeof(float));
     }
     float ms = -1.f;
     if (hipEventElapsedTime(&ms, sl->ev0, sl->ev1) == hipSuccess) e->last_ms = ms;
-    sl->ticket = 0;
-    sl->direct = false;
     return CQS_HIP_OK;
 } CQS_ABI_CATCH(e)
 
@@ -463,14 +440,13 @@ int32_t cqs_hip_embedder_warm(cqs_hip_embedder* e, uint32_t max_tokens) CQS_ABI_
     if (e->poisoned.load(std::memory_order_acquire)) return CQS_HIP_ERR_POISONED;
     if (!e->finalized) return efail(e, CQS_HIP_ERR_INVALID, "warm: weights not finalized");
     if (!e->query_path || max_tokens == 0) return CQS_HIP_OK;
-    for (const Slot& s2 : e->slot)
-        if (s2.ticket != 0) return efail(e, CQS_HIP_ERR_INVALID, "warm: tickets are in flight (collect them first)");
-    Slot& sl = e->slot[0];
+    if (e->pool.in_flight() != 0) return efail(e, CQS_HIP_ERR_INVALID, "warm: tickets are in flight (collect them first)");
+    Slot& sl = e->slot[e->pool.take()];
     E_TRY(e, hipSetDevice(e->device));
     const uint32_t Tmax = std::min(max_tokens, std::min(e->query_max_tokens, e->g.max_seq));
     int32_t rc = slot_reserve(e, sl, {1, Tmax, 1, 0});
     if (rc != CQS_HIP_OK) return rc;
-    memset(sl.meta, 0, sl.meta_cap * sizeof(int32_t));          // token id 0 at every position, wherever a shape puts `tok`
+    memset(sl.meta, 0, sl.meta_cap);                            // token id 0 at every position, wherever a shape puts `tok`
     const int n_ctx = e->single_ctx ? 1 : cqs_hip_embedder::kCtx;
     for (uint32_t T = 1; T <= Tmax; ++T) {
         sl.shape = {1, T, 1, 0};
@@ -512,8 +488,9 @@ int32_t cqs_hip_embed_hidden(cqs_hip_embedder* e, const int64_t* ids, const int6
     if (!e->finalized) return efail(e, CQS_HIP_ERR_INVALID, "embed: weights not finalized");
     if (B == 0) return CQS_HIP_OK;
     if (!ids || !mask || !out || L == 0) return efail(e, CQS_HIP_ERR_INVALID, "embed: null buffer / empty sequence");
-    Slot* sl = free_slot(e);
-    if (!sl) return CQS_HIP_ERR_INVALID;
+    const int si = free_slot(e);
+    if (si == e->pool.kNone) return CQS_HIP_ERR_INVALID;
+    Slot* sl = &e->slot[si];
     E_TRY(e, hipSetDevice(e->device));
     int32_t rc = pack_padded(e, *sl, ids, mask, B, L);
     if (rc != CQS_HIP_OK) return rc;

@@ -1,5 +1,5 @@
 """Shared by tests/test_bert_state_gpu.py and tests/test_bert_state_sensitivity_cpu.py (test infrastructure, next to
-query_state.py / batch_state.py whose `measures` and `Tally` it reuses): the three BERT-family engines (bert_engine.hip,
+query_state.py / batch_state.py whose `measures` and `Tally` it reuses): the three BERT-family engines (bert_run.hip,
 bert_kernels.hip, the bias / GELU / ROWMAX epilogues of gemm_kernels.hip and embed_gemm.hip, query_gemm.hip's small-rows
 forms) token row by token row.  `HipBertEngine.hidden` returns the final hidden row of every live token of a packed
 ragged batch (bf16 on the device, widened); the oracle side is oracle/bert_ref.encode (fp32).
@@ -262,7 +262,7 @@ def thresholds_in_source():
     small = int(re.search(r"if \(M <= (\d+)u\) \{", body).group(1))
     few = re.search(r"CQS_HIP_GEMM_BIAS_FEWROWS_MH\"\); return f \? \(uint64_t\)atoll\(f\) : (\d+)ull \* (\d+)ull;", body)
     bf = int(re.search(r"N % 128u == 0 && M <= (\d+)u\) return launch_gemm_bf16", body).group(1))
-    eng = open(os.path.join(here, "bert_engine.hip")).read()
+    eng = open(os.path.join(here, "bert_run.hip")).read()
     fused = re.search(r"const bool fused = M <= (\d+)u && .*?\(H == (\d+)u \|\| H == (\d+)u \|\| H == (\d+)u\)", eng)
     return small, int(few.group(1)) * int(few.group(2)), bf, int(fused.group(1)), tuple(int(fused.group(i)) for i in (2, 3, 4))
 

@@ -1,4 +1,4 @@
-"""The three BERT-family engines (bert_engine.hip, bert_kernels.hip, the bias / GELU / ROWMAX epilogues of gemm_kernels.hip
+"""The three BERT-family engines (bert_run.hip, bert_kernels.hip, the bias / GELU / ROWMAX epilogues of gemm_kernels.hip
 and embed_gemm.hip, query_gemm.hip's small-rows forms) token row by token row, through the entry points that exist:
 `HipBertEngine.hidden`, `embed`, `rerank_logits`, `splade_dense`.  tests/test_bert_gpu.py holds them to sequence-wide
 cosines; here every row is compared with the fp32 oracle (oracle/bert_ref.py) within 3 x the distance of an EMULATED

@@ -313,3 +313,37 @@ def test_bert_engine_from_two_threads(hip):
 
     _run_threads(work, 2)
     eng.close()
+
+
+def test_bert_blocking_calls_share_the_reserved_slot_beside_three_open_tickets(hip):
+    """The reserved slot's wait and wake-up with real calls (cqs_amd/csrc/ticket_pool.h; the protocol alone runs under the
+    sanitizers in tests/test_ticket_pool_cpu.py): a blocking `embed` is a submit + a collect on the reserved slot with the
+    handle's mutex free in between, so of two threads that call it one waits for the other's collect.  All three ticket
+    slots are held open meanwhile.  The smallest engine `create` accepts; a thread that is still alive after the join's
+    timeout fails the test instead of hanging the run."""
+    from oracle import bert_ref as R
+    from test_bert_gpu import _engine, _seqs
+    cfg = R.BertConfig(vocab_size=64, hidden=256, layers=1, heads=4, intermediate=256, max_pos=16)
+    eng, _ = _engine(cfg, "none", seed=98)
+    calls = [[_seqs(cfg, [1 + r, 8 - r], seed=100 + 8 * t + r) for r in range(8)] for t in range(2)]
+    want = [[eng.embed(s, None, "mean").copy() for s in calls[t]] for t in range(2)]       # each call alone, beforehand
+    held = [_seqs(cfg, lens, seed=120 + i) for i, lens in enumerate(([8, 3], [1, 7], [5, 5]))]
+    want_held = [eng.embed(s, None, "mean").copy() for s in held]
+    tickets = [eng.embed_submit(s, None, "mean") for s in held]
+    errs = []
+
+    def work(t):
+        try:
+            for r, s in enumerate(calls[t]):
+                assert np.array_equal(eng.embed(s, None, "mean"), want[t][r]), (t, r)
+        except BaseException as e:  # noqa: BLE001 - surfaced below
+            errs.append((t, repr(e)))
+
+    th = [threading.Thread(target=work, args=(t,), daemon=True) for t in range(2)]
+    [x.start() for x in th]
+    [x.join(timeout=60) for x in th]
+    assert not any(x.is_alive() for x in th), "a blocking call never got the reserved slot"
+    assert not errs, errs
+    for j in (1, 2, 0):
+        assert np.array_equal(eng.embed_collect(tickets[j]), want_held[j]), j
+    eng.close()
