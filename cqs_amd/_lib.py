@@ -28,6 +28,9 @@ MAX_K = 1024
 NEIGHBORS_MAX = 100
 KNN_MAX_TARGETS = 65536
 TRANSFORM_ALL = 0xFFFFFFFF
+PCA_MAX_COMPONENTS = 4
+UMAP_INIT_RANDOM = 0
+UMAP_INIT_PCA = 1
 MMR_MAX = 1024
 
 _c_idx = C.c_void_p
@@ -103,6 +106,11 @@ SIGNATURES = [
     ("cqs_hip_layout_last_error", C.c_size_t, [_c_idx, C.c_char_p, C.c_size_t]),
     ("cqs_hip_layout_destroy", None, [_c_idx]),
     ("cqs_hip_index_umap_project", C.c_int32, [_c_idx, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p]),
+    ("cqs_hip_index_pca", C.c_int32,
+     [_c_idx, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("cqs_hip_index_pca_project", C.c_int32,
+     [_c_idx, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p]),
+    ("cqs_hip_index_umap_project_init", C.c_int32, [_c_idx, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint32, C.c_void_p]),
     ("cqs_hip_umap_transform", C.c_int32,
      [C.c_int32, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
       C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]),

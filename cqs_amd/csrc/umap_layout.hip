@@ -10,6 +10,7 @@
 
 #include "abi_guard.h"
 #include "index_internal.h"
+#include "pca_host.h"
 #include "roctx.h"
 #include "search_host.h"
 #include "umap_host.h"
@@ -301,8 +302,9 @@ void cqs_hip_layout_destroy(cqs_hip_layout* x) CQS_ABI_TRY {
 } CQS_ABI_CATCH_VOID
 
 // cqs_hip_index_knn_graph over the whole corpus, then a layout run to its end: the index is held per graph call only.
-int32_t cqs_hip_index_umap_project(cqs_hip_index* idx, uint32_t n_neighbors, uint32_t n_epochs, uint64_t seed,
-                                   float* out_xy) CQS_ABI_TRY {
+// init == CQS_HIP_UMAP_INIT_PCA: the layout starts from the scaled PCA projection of the rows (pca_host.h) where there is one.
+int32_t cqs_hip_index_umap_project_init(cqs_hip_index* idx, uint32_t n_neighbors, uint32_t n_epochs, uint64_t seed,
+                                        uint32_t init, float* out_xy) CQS_ABI_TRY {
     CQS_ROCTX_RANGE("cqs_hip_index_umap_project");
     if (!idx) return CQS_HIP_ERR_INVALID;
     const auto refuse = [&](int32_t code, const char* what) {   // (a layout's failure does not poison the index)
@@ -313,6 +315,20 @@ int32_t cqs_hip_index_umap_project(cqs_hip_index* idx, uint32_t n_neighbors, uin
     const uint64_t n = cqs_hip_index_len(idx);
     if (cqs_hip_index_row_base(idx) != 0) return refuse(CQS_HIP_ERR_INVALID, "umap_project: the handle's row_base is not 0");
     if (n && !out_xy) return refuse(CQS_HIP_ERR_INVALID, "umap_project: null output buffer");
+    if (init != CQS_HIP_UMAP_INIT_RANDOM && init != CQS_HIP_UMAP_INIT_PCA) return refuse(CQS_HIP_ERR_INVALID, "umap_project: unknown init");
+    std::vector<float> start;                                   // the PCA initial coordinates; empty: the hashed ones stay
+    if (init == CQS_HIP_UMAP_INIT_PCA && n >= 2) {
+        // what the layout would refuse anyway, before the index is held for the passes
+        if (n_epochs > cqs_umap::kMaxEpochs) return refuse(CQS_HIP_ERR_INVALID, "layout: more than 10000 epochs");
+        const uint32_t dim = cqs_hip_index_dim(idx), nc = dim < 2 ? 1u : 2u;
+        std::vector<float> mean(dim), axes((size_t)nc * dim), proj((size_t)n * nc);
+        float variance[2], total;
+        int32_t rc = cqs_hip_index_pca(idx, nc, 0, seed, mean.data(), axes.data(), variance, &total);
+        if (rc == CQS_HIP_OK) rc = cqs_hip_index_pca_project(idx, mean.data(), axes.data(), nc, 0, n, proj.data());
+        if (rc != CQS_HIP_OK) return rc;                        // (the reason is in the index's last_error)
+        start.resize((size_t)n * 2);
+        if (!cqs_pca::noisy_scale_coords(proj.data(), n, nc, seed, start.data())) start.clear();
+    }
     uint32_t limit = n_neighbors > 1 ? n_neighbors - 1u : 1u;
     if (limit > CQS_HIP_NEIGHBORS_MAX) limit = CQS_HIP_NEIGHBORS_MAX;
     std::vector<uint64_t> rows((size_t)n * limit);
@@ -335,7 +351,8 @@ int32_t cqs_hip_index_umap_project(cqs_hip_index* idx, uint32_t n_neighbors, uin
         cqs_hip_layout_last_error(nullptr, why, sizeof why);
         return refuse(rc, why);
     }
-    rc = cqs_hip_layout_run(lay, cqs_hip_layout_epochs(lay), nullptr);
+    if (!start.empty()) rc = cqs_hip_layout_set_coords(lay, start.data());
+    if (rc == CQS_HIP_OK) rc = cqs_hip_layout_run(lay, cqs_hip_layout_epochs(lay), nullptr);
     if (rc == CQS_HIP_OK) rc = cqs_hip_layout_coords(lay, out_xy);
     if (rc != CQS_HIP_OK) {
         cqs_hip_layout_last_error(lay, why, sizeof why);
@@ -344,6 +361,11 @@ int32_t cqs_hip_index_umap_project(cqs_hip_index* idx, uint32_t n_neighbors, uin
     }
     cqs_hip_layout_destroy(lay);
     return CQS_HIP_OK;
+} CQS_ABI_CATCH(idx)
+
+int32_t cqs_hip_index_umap_project(cqs_hip_index* idx, uint32_t n_neighbors, uint32_t n_epochs, uint64_t seed,
+                                   float* out_xy) CQS_ABI_TRY {
+    return cqs_hip_index_umap_project_init(idx, n_neighbors, n_epochs, seed, CQS_HIP_UMAP_INIT_RANDOM, out_xy);
 } CQS_ABI_CATCH(idx)
 
 }  // extern "C"

@@ -795,22 +795,70 @@ class HipIndex(VectorIndex):
         return [[IndexResult(self._id(int(rows[i, j])), float(scores[i, j])) for j in range(int(counts[i]))]
                 for i in range(rows.shape[0])]
 
+    def pca(self, n_components: int = 2, n_passes: Optional[int] = None, seed: int = 42):
+        """`cqs_hip_index_pca`: the top principal axes of the stored rows by block subspace iteration on the device
+        (include/cqs_hip.h "PCA of the stored rows").  Returns (mean f32 [dim], axes f32 [n_components, dim] orthonormal,
+        largest variance first, variance f32 [n_components] as sklearn's explained_variance_, total_variance float: the
+        trace of the covariance).  `n_passes` None: the default 16.  Raises HipError (INVALID: n_components not in
+        [1, min(4, dim)], more than 64 passes, a row-sharded handle, fewer than 2 rows, non-finite rows)."""
+        dim = self.dim()
+        nc = max(0, min(int(n_components), _lib.PCA_MAX_COMPONENTS + 1))    # (one past the limit: the library refuses it)
+        mean = np.zeros((dim,), dtype=np.float32)
+        axes = np.zeros((max(nc, 1), dim), dtype=np.float32)
+        var = np.zeros((max(nc, 1),), dtype=np.float32)
+        total = C.c_float()
+        rc = self._lib.cqs_hip_index_pca(self._h, nc, 0 if n_passes is None else max(0, min(int(n_passes), 2**32 - 1)),
+                                         int(seed), _ptr(mean), _ptr(axes), _ptr(var), C.byref(total))
+        if rc != _lib.OK:
+            raise HipError(rc, self.last_error())
+        return mean, axes[:nc], var[:nc], float(total.value)
+
+    def pca_project(self, mean, axes, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """`cqs_hip_index_pca_project`: (x - mean) . axes_k for the `count` stored rows from the index's `first`-th on
+        (default: to the end), f32 [count, n_components].  `mean` [dim] and `axes` [n_components, dim] are what `pca`
+        returns - of this index or of another of the same dimension."""
+        mu = np.ascontiguousarray(mean, dtype=np.float32).reshape(-1)
+        ax = np.ascontiguousarray(axes, dtype=np.float32)
+        if ax.ndim != 2 or ax.shape[1] != self.dim() or mu.shape[0] != self.dim():
+            raise ValueError("pca_project: mean is [dim], axes is [n_components, dim]")
+        n = len(self)
+        first = int(first)
+        count = n - first if count is None else int(count)
+        if first < 0 or count < 0 or first + count > n:
+            raise ValueError("pca_project: range not in this index")
+        out = np.zeros((count if ax.shape[0] <= _lib.PCA_MAX_COMPONENTS else 0, ax.shape[0]), dtype=np.float32)   # (more: the library refuses)
+        base = int(self._lib.cqs_hip_index_row_base(self._h))
+        rc = self._lib.cqs_hip_index_pca_project(self._h, _ptr(mu), _ptr(ax), ax.shape[0], base + first, count, _ptr(out))
+        if rc != _lib.OK:
+            raise HipError(rc, self.last_error())
+        return out
+
     def umap_project(self, n_neighbors: int = 15, n_epochs: Optional[int] = None, seed: int = 42,
-                     rows_per_call: int = 4096) -> np.ndarray:
+                     rows_per_call: int = 4096, *, init: str = "random") -> np.ndarray:
         """`cqs index --umap` on the resident corpus (src/cli/commands/index/umap.rs): the exact graph of
         `knn_graph_rows(n_neighbors - 1)` - umap-learn counts a point among its own neighbours - in calls of
         `rows_per_call` targets cut at multiples of 256, then a `HipLayout` (cqs_amd/umap.py) on this index's device run to
         its end.  Returns coordinates f32 [n, 2] in row order; fewer than 2 rows give the origin.  Raises what
-        `knn_graph_rows` raises on a row-sharded handle."""
-        from .umap import HipLayout
+        `knn_graph_rows` raises on a row-sharded handle.  `init="pca"` starts the layout from the scaled PCA projection of
+        the rows (umap-learn's init="pca"; `cqs_hip_index_umap_project_init`, whose bytes this returns) instead of the
+        hashed uniform coordinates: where the clusters end up relative to each other then follows the corpus."""
+        from .umap import HipLayout, pca_initial_coords
+        if init not in ("random", "pca"):
+            raise ValueError("umap_project: init is 'random' or 'pca'")
         n = len(self)
         if n < 2:
             return np.zeros((n, 2), dtype=np.float32)
         if int(self._lib.cqs_hip_index_row_base(self._h)) != 0:
             raise ValueError("umap_project: the handle's row_base is not 0")
+        start = None
+        if init == "pca":
+            mean, axes, _, _ = self.pca(min(2, self.dim()), None, seed)
+            start = pca_initial_coords(self.pca_project(mean, axes), seed)
         rows, scores, counts = self.knn_graph_rows(int(n_neighbors) - 1, rows_per_call=rows_per_call)
         with HipLayout(rows, scores, counts, device=int(self._lib.cqs_hip_index_device(self._h)),
                        n_epochs=0 if n_epochs is None else int(n_epochs), seed=int(seed)) as lay:
+            if start is not None:
+                lay.set_coords(start)
             lay.run()
             return lay.coords()
 
@@ -836,9 +884,9 @@ class HipIndex(VectorIndex):
         return out
 
     def umap_project_by_id(self, n_neighbors: int = 15, n_epochs: Optional[int] = None, seed: int = 42,
-                           rows_per_call: int = 4096) -> List[Tuple[str, float, float]]:
+                           rows_per_call: int = 4096, *, init: str = "random") -> List[Tuple[str, float, float]]:
         """`umap_project` by chunk id, in row order: (id, x, y) - the triples the reference's script answers with."""
-        xy = self.umap_project(n_neighbors, n_epochs, seed, rows_per_call)
+        xy = self.umap_project(n_neighbors, n_epochs, seed, rows_per_call, init=init)
         base = int(self._lib.cqs_hip_index_row_base(self._h))
         return [(self._id(base + i), float(xy[i, 0]), float(xy[i, 1])) for i in range(xy.shape[0])]
 

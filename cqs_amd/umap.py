@@ -187,6 +187,52 @@ def transform(anchors_xy, rows, scores, counts, id_base: Optional[int] = None, e
     return _in_calls(call, r, int(p.n_epochs), want_weights)
 
 
+def _fmix32(h):
+    h = h ^ (h >> np.uint32(16))
+    h = h * np.uint32(0x85EBCA6B)
+    h = h ^ (h >> np.uint32(13))
+    h = h * np.uint32(0xC2B2AE35)
+    return h ^ (h >> np.uint32(16))
+
+
+def _hash5(seed: int, epoch: int, vertex, slot: int, draw: int):
+    """The header's hash(seed, epoch, vertex, slot, draw) over a u32 array of vertices."""
+    seed = int(seed) & (2 ** 64 - 1)
+    with np.errstate(over="ignore"):
+        h = _fmix32(np.asarray([(seed & 0xFFFFFFFF) ^ 0x9E3779B9], dtype=np.uint32))
+        h = _fmix32(h ^ np.uint32(seed >> 32))
+        h = _fmix32(h ^ np.uint32(epoch))
+        h = _fmix32(h ^ np.asarray(vertex, dtype=np.uint32))
+        h = _fmix32(h ^ np.uint32(slot))
+        return _fmix32(h ^ np.uint32(draw))
+
+
+def pca_initial_coords(proj, seed: int) -> Optional[np.ndarray]:
+    """umap-learn's `noisy_scale_coords` as include/cqs_hip.h states it for `cqs_hip_index_umap_project_init`: `proj`
+    [n, 1 or 2] f32 (what `HipIndex.pca_project` returns) -> xy [n, 2] f32 = proj * (10 / max|proj|) + jitter, every
+    operation in f32 and rounded once, so the bytes are the C entry point's.  None where max|proj| is 0 or a projection
+    is not finite: the layout keeps its hashed uniform coordinates."""
+    p = np.ascontiguousarray(proj, dtype=np.float32)
+    if p.ndim != 2 or p.shape[1] not in (1, 2):
+        raise ValueError("pca_initial_coords: proj is [n, 1] or [n, 2]")
+    n = p.shape[0]
+    mag = np.abs(p)
+    if n == 0 or not np.isfinite(mag).all() or not mag.max() > 0:
+        return None
+    with np.errstate(over="ignore"):
+        scale = np.float32(10.0) / mag.max()
+    if not np.isfinite(scale):                                 # a denormal maximum
+        return None
+    xy = np.zeros((n, 2), dtype=np.float32)
+    xy[:, :p.shape[1]] = p * scale
+    v = np.arange(n, dtype=np.uint32)
+    for c in (0, 1):
+        u = (_hash5(seed, 0, v, 1, c) >> np.uint32(8)).astype(np.float32)
+        jitter = (u * np.float32(1.0 / 16777216.0) - np.float32(0.5)) * np.float32(2e-4)
+        xy[:, c] = xy[:, c] + jitter
+    return xy
+
+
 def _create_error(lib) -> str:
     buf = C.create_string_buffer(512)
     lib.cqs_hip_layout_last_error(None, buf, 512)

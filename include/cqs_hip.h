@@ -381,6 +381,74 @@ void cqs_hip_layout_destroy(cqs_hip_layout* layout);
 int32_t cqs_hip_index_umap_project(cqs_hip_index* idx, uint32_t n_neighbors, uint32_t n_epochs, uint64_t seed,
                                    float* out_xy);
 
+/* ---- PCA of the stored rows ---------------------------------------------------------
+ * The top principal axes of the resident corpus in a few streaming passes: the global picture of a corpus on its own (and
+ * how anisotropic a model's embeddings are: variance / total_variance), and the initial coordinates of a UMAP layout that
+ * umap-learn calls init="pca" (below).  The rules here are the specification.
+ * Definition: X is the n stored f32 rows, mu their column mean, Z = X - 1 mu^T.  The axes are orthonormal eigenvectors of
+ *   Z^T Z, largest eigenvalue first; out_variance[k] is the Rayleigh quotient a_k^T Z^T Z a_k / (n - 1) (sklearn's
+ *   explained_variance_); out_total_variance = (sum |x_i|^2 - n |mu|^2) / (n - 1), the trace of the covariance.  Sign: the
+ *   component of largest magnitude of each axis is positive, the lowest index on ties.
+ * Shift: all sums are taken over x_i - x_0, x_0 the first stored row (the covariance does not change, the f32 sums lose
+ *   less, and a corpus of identical rows gives exactly mean = x_0, Z = 0).  mu = x_0 + (sum (x_i - x_0)) / n; that sum and the
+ *   squares of out_total_variance, evaluated as (sum |x_i - x_0|^2 - n |mu - x_0|^2) / (n - 1), are one pass in f64.
+ * Method: block subspace iteration with p = min(8, dim) columns.
+ *   Start: V0[d][j] = float(hash(seed, 0, d, 2, j) >> 8) * 2^-23 - 1 with the layout section's hash (slot 2: the initial
+ *     coordinates use slot 0, the jitter below slot 1), orthonormalised on the host in f64.
+ *   Gram-Schmidt (host, f64, column order): column j has its components along the columns before it subtracted one after
+ *     the other, twice, and is divided by its norm.  Breakdown rule: a column whose norm before is 0 or not finite, or whose
+ *     norm after is at most 1e-10 of the norm before, is replaced by the first unit basis vector e_d, d ascending, whose
+ *     residual against the earlier columns has a squared norm of at least 1 / (2 dim); that residual is normalised.
+ *   A pass (n_passes of them; 0 means 16; at most 64): V rounded to f32; on the device, per row, t = (x - x_0) V - c with
+ *     c = (mu - x_0)^T V, Y += (x - x_0) (x) t, S += t, products and sums in f32; the host forms Z^T Z V = Y - (mu - x_0)
+ *     (x) S in f64 and orthonormalises it into the next V.
+ *   After the last pass one more gives H = V^T (Z^T Z V) for the f32 V the device saw; H is symmetrised and eigen-solved
+ *     on the host (cyclic Jacobi, f64); the axes are V W's first n_components columns rounded to f32.
+ * Determinism: the corpus is cut into slabs of 1024 rows by local row number.  A slab's partial Y [dim x 8] and S [8] are
+ *   fmaf chains of the f32 matrix cores in an order fixed by the kernel (t: the columns in steps of 4, the steps dealt
+ *   round-robin to four chains that are added as ((0 + 1) + 2) + 3; Y: the slab's rows in ascending order); the slab
+ *   partials are added in ascending slab order in f64.  No float atomics.  The answer is a function of the stored rows,
+ *   seed and n_passes only: not of the grid, the device's CU count, or whether the rows came by `create` or by `create` +
+ *   `extend`; after `update` or `remove` it is that of a fresh index of the rows now stored.
+ * cqs_hip_index_pca      out_mean [dim], out_axes [n_components * dim] (axis k at k * dim), out_variance [n_components],
+ *   out_total_variance [1], host.  Holds the handle's mutex for the whole call, so that every pass sees the same rows:
+ *   searches on the handle wait (DESIGN.md §3.18b has the measured length).  Device memory for the call: 32 dim + 4
+ *   ceil(n / 1024) (8 dim + 8) bytes of partials, about 24 MB at 1M x 768; freed before it returns.
+ * cqs_hip_index_pca_project   out[i * n_components + k] = (x_{first_row + i} - mean) . axes_k in f32 for the m stored rows
+ *   from first_row (a GLOBAL row id) on: the subtraction first, then per lane an fmaf chain over the float4 columns lane,
+ *   lane + 64, ..., then the lanes added as v += v[lane ^ 32], ^ 16, ^ 8, ^ 4, ^ 2, ^ 1.  Any m: launches of at most
+ *   16 * CQS_HIP_KNN_MAX_TARGETS rows each, the handle held for the call.  mean / axes are the caller's (host), so rows
+ *   can be projected onto the axes of another index.
+ * Refused with CQS_HIP_ERR_INVALID, nothing written, the handle not poisoned and the reason in last_error, in this order -
+ *   pca: a NULL handle; a NULL output; n_components == 0, > CQS_HIP_PCA_MAX_COMPONENTS or > dim; n_passes > 64; a
+ *   row-sharded handle ("pca: not built for a row-sharded handle"); fewer than 2 rows; and, after the passes, a total variance,
+ *   an entry of H or one of the p Rayleigh values that is not finite as f32 ("pca: non-finite rows").  pca_project: a NULL handle; (m == 0 returns CQS_HIP_OK here and touches nothing;)
+ *   a NULL mean or axes; a NULL out; n_components as above; a row-sharded handle; any part of the range outside the index.
+ *   A poisoned handle -> CQS_HIP_ERR_POISONED; a device failure poisons the handle. */
+#define CQS_HIP_PCA_MAX_COMPONENTS 4
+int32_t cqs_hip_index_pca(cqs_hip_index* idx, uint32_t n_components, uint32_t n_passes, uint64_t seed,
+                          float* out_mean /*[dim]*/, float* out_axes /*[n_components * dim]*/,
+                          float* out_variance /*[n_components]*/, float* out_total_variance /*1*/);
+int32_t cqs_hip_index_pca_project(cqs_hip_index* idx, const float* mean, const float* axes, uint32_t n_components,
+                                  uint64_t first_row, uint64_t m, float* out /*[m * n_components]*/);
+/* cqs_hip_index_umap_project with a choice of initial coordinates.  init == CQS_HIP_UMAP_INIT_RANDOM: exactly the bytes of
+ * cqs_hip_index_umap_project.  init == CQS_HIP_UMAP_INIT_PCA (umap-learn's init="pca"; where the clusters end up relative
+ * to each other then follows the corpus, not the draw): cqs_hip_index_pca with 2 components (1 where dim == 1: y = 0), the
+ * default passes and `seed`; cqs_hip_index_pca_project of all rows; then umap-learn's noisy_scale_coords on the host in
+ * f32, each operation rounded once:
+ *     coord = proj * (10 / max|proj|) + jitter,  jitter = (float(hash(seed, 0, i, 1, c) >> 8) * 2^-24 - 0.5) * 2e-4
+ * (max over both coordinates of all rows; the jitter keeps duplicated rows from starting coincident, where the layout
+ * gives them zero force), set as the layout's coordinates before its first epoch.  Where max|proj| is 0 (or so small
+ * that the quotient overflows) or a projection is not finite the hashed uniform coordinates stay.  Fewer than 2 rows give
+ * the origin as before.  Any other `init` is CQS_HIP_ERR_INVALID.  n_epochs > 10000 is refused before the passes, in the
+ * layout's words; a refusal of pca or pca_project ("pca: non-finite rows", a row-sharded handle) or CQS_HIP_ERR_POISONED
+ * from them is the call's, out_xy untouched.  The index is held per call of pca, pca_project and knn_graph, not across
+ * them. */
+#define CQS_HIP_UMAP_INIT_RANDOM 0
+#define CQS_HIP_UMAP_INIT_PCA    1
+int32_t cqs_hip_index_umap_project_init(cqs_hip_index* idx, uint32_t n_neighbors, uint32_t n_epochs, uint64_t seed,
+                                        uint32_t init, float* out_xy);
+
 /* ---- UMAP transform of new rows ----------------------------------------------------
  * The watch loop appends a few hundred chunks; this gives them coordinates in a layout that exists, without projecting the
  * corpus again: umap-learn's `transform`, restated in the conventions of the layout section above, departures stated.

@@ -73,6 +73,12 @@ extern "C" {
     // `cqs index --umap` on the resident corpus: the kNN graph, then the layout handle (its own opaque type on the C side;
     // this one call is all the shim needs of it), run to its end
     fn cqs_hip_index_umap_project(idx: *mut CqsHipIndex, n_neighbors: u32, n_epochs: u32, seed: u64, out_xy: *mut f32) -> i32;
+    fn cqs_hip_index_pca(idx: *mut CqsHipIndex, n_components: u32, n_passes: u32, seed: u64, out_mean: *mut f32,
+                         out_axes: *mut f32, out_variance: *mut f32, out_total_variance: *mut f32) -> i32;
+    fn cqs_hip_index_pca_project(idx: *mut CqsHipIndex, mean: *const f32, axes: *const f32, n_components: u32, first_row: u64,
+                                 m: u64, out: *mut f32) -> i32;
+    fn cqs_hip_index_umap_project_init(idx: *mut CqsHipIndex, n_neighbors: u32, n_epochs: u32, seed: u64, init: u32,
+                                       out_xy: *mut f32) -> i32;
     // ... and coordinates for rows appended since, among the stored ones, which stay where they are
     fn cqs_hip_index_umap_transform(idx: *mut CqsHipIndex, n_anchors: u64, anchors_xy: *const f32, vectors: *const f32, m: u64,
                                     n_neighbors: u32, n_epochs: u32, seed: u64, out_xy: *mut f32) -> i32;
@@ -662,6 +668,49 @@ impl HipIndex {
             return None;
         }
         Some((0..n).map(|i| (self.id_map[i].to_string(), xy[2 * i], xy[2 * i + 1])).collect())
+    }
+
+    /// `umap_project` with a choice of initial coordinates: `pca_init` starts the layout from the scaled PCA projection of
+    /// the resident rows (umap-learn's init="pca"), so where the clusters end up relative to each other follows the corpus
+    /// and not the draw; `false` gives exactly `umap_project`'s bytes.
+    pub fn umap_project_init(&self, n_neighbors: usize, n_epochs: usize, seed: u64, pca_init: bool) -> Option<Vec<(String, f32, f32)>> {
+        let n = self.id_map.len();
+        let mut xy = vec![0f32; 2 * n.max(1)];
+        let rc = unsafe {
+            cqs_hip_index_umap_project_init(self.handle, n_neighbors.min(u32::MAX as usize) as u32,
+                                            n_epochs.min(u32::MAX as usize) as u32, seed, if pca_init { 1 } else { 0 },
+                                            xy.as_mut_ptr())
+        };
+        if rc != CQS_HIP_OK {
+            tracing::warn!(error = %self.last_error(), rc, "HIP UMAP projection failed");
+            return None;
+        }
+        Some((0..n).map(|i| (self.id_map[i].to_string(), xy[2 * i], xy[2 * i + 1])).collect())
+    }
+
+    /// The top `n_components` (1 to 4) principal axes of the resident rows in `n_passes` streaming passes (0: 16):
+    /// (mean [dim], axes [n_components * dim], variance [n_components], total variance).  With `project`, also every
+    /// resident row's coordinates along the axes, `n_components` floats each in `id_map` order - a first picture of the
+    /// corpus long before a UMAP projection is ready.  `None` = refused (fewer than 2 rows, a row-sharded handle) or failed.
+    pub fn pca(&self, n_components: usize, n_passes: usize, seed: u64, project: bool)
+               -> Option<(Vec<f32>, Vec<f32>, Vec<f32>, f32, Vec<f32>)> {
+        let dim = self.dim;
+        let nc = n_components.min(5);   // CQS_HIP_PCA_MAX_COMPONENTS + 1: the buffers stay small, the library refuses it
+        let (mut mean, mut axes, mut var, mut total) = (vec![0f32; dim.max(1)], vec![0f32; (nc * dim).max(1)], vec![0f32; nc.max(1)], 0f32);
+        let mut rc = unsafe {
+            cqs_hip_index_pca(self.handle, nc as u32, n_passes.min(u32::MAX as usize) as u32, seed, mean.as_mut_ptr(),
+                              axes.as_mut_ptr(), var.as_mut_ptr(), &mut total)
+        };
+        let n = self.id_map.len();
+        let mut proj = vec![0f32; if project { (n * nc).max(1) } else { 1 }];
+        if rc == CQS_HIP_OK && project {
+            rc = unsafe { cqs_hip_index_pca_project(self.handle, mean.as_ptr(), axes.as_ptr(), nc as u32, 0, n as u64, proj.as_mut_ptr()) };
+        }
+        if rc != CQS_HIP_OK {
+            tracing::warn!(error = %self.last_error(), rc, "HIP PCA failed");
+            return None;
+        }
+        Some((mean, axes, var, total, proj))
     }
 
     /// Coordinates for new chunks in a projection that exists, without projecting the corpus again: `anchors_xy` holds the
