@@ -212,6 +212,7 @@ void read_combine_env(cqs_hip_index* x);
 int32_t shadow_auto(cqs_hip_index* x);
 int32_t shadow_extend(cqs_hip_index* x, uint64_t n_old);
 void shadow_free(cqs_hip_index* x);
+void shadow_sweep_reset(cqs_hip_index* x);   // after extend / remove / update: the int8 scan's next sweep runs forwards
 // The shadow's per-row buffers, which remove compacts beside d_rows (index_remove.hip); null: that copy is off.
 struct ShadowBuffers { uint16_t* bf16; int8_t* i8; float* i8_scale; };
 ShadowBuffers shadow_buffers(const cqs_hip_index* x);

@@ -109,6 +109,7 @@ int32_t remove_locked(cqs_hip_index* x, const std::vector<uint64_t>& removed, co
         return fail(x, CQS_HIP_ERR_DEVICE, "remove: injected device failure (test hook)");
     HIP_TRY(x, hipSetDevice(x->device));
     HIP_TRY(x, quiesce(x));   // a search enqueued on a caller stream may still read the rows
+    shadow_sweep_reset(x);
     const uint64_t n_new = x->n - removed.size();
     if (!runs.empty()) {
         const ShadowBuffers sb = shadow_buffers(x);

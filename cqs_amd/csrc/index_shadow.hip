@@ -8,6 +8,7 @@
 #include "index_internal.h"
 #include "scan_bf16.h"
 #include "scan_fallback.h"
+#include "i8_sweep.h"
 #include "scan_i8.h"
 #include "tail_plan.h"
 
@@ -59,6 +60,14 @@ struct Shadow {
     uint8_t i8_groups = 2;                // CQS_HIP_I8_GROUPS, read when the shadow is built: 0 = the int8 scan publishes one maximum per
                                           // task, as the other scans do (the A/B arm and the tests' reference); 1 = one per workgroup of
                                           // four tasks in every int8 block; unset = where that pays (shadow_group_tasks).  Same answers
+    bool i8_serpentine = true;            // CQS_HIP_I8_SERPENTINE, read when the shadow is built: 0 = every int8 scan sweeps the copy forwards
+                                          // and a streamed one loads nontemporally throughout (the A/B arm and the tests' reference;
+                                          // same answers); w:<bytes> = on, with that plain-load window at any corpus size (tests)
+    bool i8_force_window = false;         // (the w:<bytes> form: the int8 scan takes its nontemporal instantiation at any size)
+    uint64_t i8_plain_bytes = cqs::kI8PlainBytes;   // bytes at each end of a streamed int8 copy that are loaded plainly (i8_sweep.h)
+    uint32_t sweep_rev = 0;               // parity of the next int8 scan's sweep: flipped by shadow_pass after each one it
+                                          // enqueues (host state, under the lock that serialises enqueues); extend, remove
+                                          // and update put it back to 0 (shadow_sweep_reset)
     uint32_t* h_cert = nullptr;           // pinned [kShadowMaxQ]
     uint32_t* h_cert_dev = nullptr;       // its device-visible address (null: not mappable)
 };
@@ -98,6 +107,11 @@ void shadow_free(cqs_hip_index* x) {
     hipHostFree(s->h_cert);
     delete s;
     x->shadow = nullptr;
+}
+
+// The rows have changed (extend, remove, update): the next int8 scan sweeps forwards again.
+void shadow_sweep_reset(cqs_hip_index* x) {
+    if (x->shadow) x->shadow->sweep_rev = 0u;
 }
 
 ShadowBuffers shadow_buffers(const cqs_hip_index* x) {
@@ -142,6 +156,7 @@ static int32_t i8_convert(cqs_hip_index* x, uint64_t row0) {
 
 int32_t shadow_update_begin(cqs_hip_index* x, unsigned long long** stats, unsigned long long** stats8) {
     Shadow* s = x->shadow;
+    shadow_sweep_reset(x);
     HIP_TRY(x, hipMemsetAsync(s->d_stats + 2, 0, sizeof(unsigned long long), x->stream));
     *stats = s->d_stats;
     *stats8 = s->d_stats + kStatI8;
@@ -197,6 +212,7 @@ static int32_t i8_enable(cqs_hip_index* x, bool* built) {
 int32_t shadow_extend(cqs_hip_index* x, uint64_t n_old) {
     Shadow* s = x->shadow;
     if (!s) return CQS_HIP_OK;
+    shadow_sweep_reset(x);
     if (x->cap_rows > s->cap) {
         uint16_t* nd = nullptr;
         if (hipMalloc(&nd, (size_t)x->cap_rows * x->dim * sizeof(uint16_t)) != hipSuccess) {
@@ -275,6 +291,12 @@ static int32_t shadow_enable(cqs_hip_index* x, const char* what) {
     s->tail_first = tf_env && tf_env[0] == '0' ? 0 : (tf_env && tf_env[0] == '1' ? 1 : 2);
     const char* ig_env = getenv("CQS_HIP_I8_GROUPS");
     s->i8_groups = ig_env && ig_env[0] == '0' ? 0 : (ig_env && ig_env[0] == '1' ? 1 : 2);
+    const char* sp_env = getenv("CQS_HIP_I8_SERPENTINE");
+    s->i8_serpentine = !(sp_env && sp_env[0] == '0');
+    if (sp_env && sp_env[0] == 'w' && sp_env[1] == ':') {
+        s->i8_force_window = true;
+        s->i8_plain_bytes = strtoull(sp_env + 2, nullptr, 10);
+    }
     if ((e = hipMalloc(&s->d_fb_lists, cqs::f32_topk_fallback_words(x->n_cu) * sizeof(uint64_t))) != hipSuccess) return oom(e);
     if ((e = hipMalloc(&s->d_fb_tickets, (size_t)cqs::kMaxGemvQ * sizeof(uint32_t))) != hipSuccess) return oom(e);
     if ((e = hipMemsetAsync(s->d_fb_tickets, 0, (size_t)cqs::kMaxGemvQ * sizeof(uint32_t), x->stream)) != hipSuccess) return oom(e);
@@ -388,6 +410,16 @@ static uint32_t shadow_group_tasks(const cqs_hip_index* x, bool i8, uint32_t kp)
     return 4u * kk * kk <= pad_rows(x->n) ? cqs::kMaxGroupTasks : 1u;
 }
 
+// The sweep of the int8 scan about to be enqueued with `a`: it starts where the last one stopped (the parity flips here, once
+// per scan), and the ends of a streamed copy load plainly.  Caller holds mu.
+static void sweep_args(Shadow* s, cqs::ScanArgs& a) {
+    if (!s->i8_serpentine) return;
+    a.sweep_rev = s->sweep_rev;
+    s->sweep_rev ^= 1u;
+    a.plain_bytes = s->i8_plain_bytes;
+    if (s->i8_force_window) a.nontemporal = true;
+}
+
 // The shadow half of a gemv block on `st`: shadow scan -> one tail launch (select k' + 1, B_q, rescore, certify) into
 // out_keys / out_counts.  PIPELINE searches alone launch the bound kernel first: only their scan reads B_q (its drop rule).
 // device_gate (device-API searches): `st` is ordered after the last search here, certify counts outcomes on the device,
@@ -398,7 +430,7 @@ static uint32_t shadow_group_tasks(const cqs_hip_index* x, bool i8, uint32_t kp)
 int32_t shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k, const uint32_t* d_keep, uint32_t mode,
                     float threshold, uint64_t* out_keys, uint32_t* out_counts, hipStream_t st, const uint32_t** device_gate,
                     const KeepTab* tab) {
-    const Shadow* s = x->shadow;
+    Shadow* s = x->shadow;
     uint32_t* const cert = device_gate || !s->h_cert_dev ? s->d_cert : s->h_cert_dev;
     if (device_gate) *device_gate = cert;
     if (device_gate) HIP_TRY(x, order_after_last(x, st));
@@ -416,6 +448,7 @@ int32_t shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k,
     // index from kGauxMinK on whatever CQS_HIP_SELECT_AUX says (that A/B hook is the f32 select's)
     cqs::ScanArgs a = scan_args(x, d_q, nb, kp + 1u, d_keep, mode, threshold, i8 ? sizeof(int8_t) : sizeof(uint16_t), true, nullptr, nullptr, tab);
     a.group_tasks = shadow_group_tasks(x, i8, kp);   // (the scan publishes, the tail kernel's select walks: one maximum per that many tasks)
+    if (i8) sweep_args(s, a);
     const ShadowRows rows{i8 ? nullptr : s->d_bf16, i8 ? s->d_i8 : nullptr, s->d_i8_scale, s->d_bq};
     const int32_t rc = scan_select(x, a, st, &rows, nullptr, nullptr);   // (the scan alone: the tail kernel selects)
     if (rc == CQS_HIP_OK)
@@ -665,7 +698,7 @@ int32_t cqs_hip_debug_shadow_scores(cqs_hip_index* x, uint32_t copy, const float
     if (k == 0 || k > cqs::kMaxK) return CQS_HIP_ERR_INVALID;
     std::lock_guard<std::mutex> g(x->mu);
     if (x->poisoned.load(std::memory_order_acquire)) return CQS_HIP_ERR_POISONED;
-    const Shadow* s = x->shadow;
+    Shadow* s = x->shadow;
     if (!s || x->n == 0 || b > cqs::kMaxGemvQ || !shadow_takes(x, b, k, /*gemv_only=*/false)) return CQS_HIP_ERR_INVALID;
     if (copy == 2u && !(s->d_i8 && b <= cqs::kI8MaxQ && cqs::i8_k_ok(k))) return CQS_HIP_ERR_INVALID;
     HIP_TRY(x, hipSetDevice(x->device));
@@ -690,6 +723,7 @@ int32_t cqs_hip_debug_shadow_scores(cqs_hip_index* x, uint32_t copy, const float
     } else {
         cqs::ScanArgs a = scan_args(x, x->d_q, b, k_scan, d_keep, mode, threshold, i8 ? sizeof(int8_t) : sizeof(uint16_t), true, nullptr, nullptr);
         a.group_tasks = shadow_group_tasks(x, i8, kp);
+        if (i8) sweep_args(s, a);   // (as shadow_pass: this scan takes the handle's parity and flips it)
         if (i8) HIP_TRY(x, cqs::launch_scan_i8(a, s->d_i8, s->d_i8_scale, s->d_bq, st));
         else HIP_TRY(x, cqs::launch_scan_bf16(a, s->d_bf16, s->d_bq, st));
     }

@@ -10,6 +10,7 @@
 //
 // Wave = 64 lanes.  gfx950 only.
 #include "scan_i8.h"
+#include "i8_sweep.h"
 #include "launch_util.h"
 #include "scan_gemv_device.h"
 #include "shadow_build_device.h"
@@ -77,6 +78,9 @@ struct I8ScanParams {
     uint8_t slot[kMaxGemvQ];// ... and query b of the pass is filtered by row slot[b] (ScanArgs::keep_tab)
     uint32_t group_tasks;   // 1: gmax / gaux hold one entry per task.  kI8BlockWaves: one per workgroup = group of that many
     uint32_t n_groups;      // consecutive tasks (GroupMap{tiers, group_tasks}), and this is their per-query stride
+    uint32_t rev;           // 1: workgroup blockIdx.x takes the tasks of workgroup n_wg - 1 - blockIdx.x: the sweep runs
+    uint32_t n_wg;          // backwards (i8_sweep.h).  n_wg = ceil(n_tasks / kI8BlockWaves) workgroups
+    uint32_t plain_lo, plain_hi;   // NT: workgroups (after the mapping) below plain_lo or from plain_hi on load plainly
 };
 
 constexpr uint32_t kI8BlockWaves = 4;   // waves = consecutive tasks of a workgroup (= kMaxGroupTasks: the grouped form's G)
@@ -93,8 +97,10 @@ static_assert(kI8BlockWaves == kMaxGroupTasks, "a workgroup of the int8 scan is 
 // group_tasks = 4 (a uniform branch on the kernarg; 1 keeps the per-task stores as they were): each wave leaves its triple
 // per query in LDS and adds one to an arrival counter (workgroup scope, acq_rel); the wave whose add completes the count -
 // min(4, n_tasks - 4 blockIdx.x): waves past the last task leave at entry - combines the slots (combine_triples) and stores
-// the group's gmax / gaux entry.  Nobody waits at the end; the counter is zeroed behind the one barrier at entry, which
-// stands before the early return.  The stores are plain: their reader is the next launch.
+// the group's gmax / gaux entry.  Which group a workgroup is, and so every index below, comes from sweep_group (i8_sweep.h):
+// a reversed sweep writes the same values to the same places in another order in time.  Nobody waits at the end; the
+// counter is zeroed behind the one barrier at entry, which stands before the early return.  The stores are plain: their
+// reader is the next launch.
 template <int NCH, int BQ, int RI, bool NT, bool FULL, bool PQ>
 __global__ __launch_bounds__(256) void scan_i8_kernel(const I8ScanParams p) {
     constexpr int NV = RI * BQ;
@@ -132,11 +138,12 @@ __global__ __launch_bounds__(256) void scan_i8_kernel(const I8ScanParams p) {
     const uint32_t n_tasks = p.n_tasks;
     const uint32_t wpb = blockDim.x >> 6;
     const uint32_t wib = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t cur = (uint32_t)__builtin_amdgcn_readfirstlane((int)(blockIdx.x * wpb + (threadIdx.x >> 6)));
+    const uint32_t wg = sweep_group(blockIdx.x, p.n_wg, p.rev);   // (uniform: the workgroup whose tasks this one takes)
+    const uint32_t cur = (uint32_t)__builtin_amdgcn_readfirstlane((int)(wg * wpb + (threadIdx.x >> 6)));
     if (cur >= n_tasks) return;
 
     const char* const rows_b = (const char*)p.rows;
-    auto load_rows = [&](uint32_t base, int j, u4 (&x)[RI][NCH]) {
+    auto load_rows = [&](auto nt_c, uint32_t base, int j, u4 (&x)[RI][NCH]) {
 #pragma unroll
         for (int r = 0; r < RI; ++r) {
             uint32_t row = base + (uint32_t)(RI * j + r);
@@ -145,7 +152,7 @@ __global__ __launch_bounds__(256) void scan_i8_kernel(const I8ScanParams p) {
 #pragma unroll
             for (int c = 0; c < NCH; ++c) {
                 const u4* src = (const u4*)(rp + coff[c]);
-                if (NT) x[r][c] = __builtin_nontemporal_load(src);
+                if (decltype(nt_c)::value) x[r][c] = __builtin_nontemporal_load(src);
                 else x[r][c] = *src;
             }
         }
@@ -221,7 +228,7 @@ __global__ __launch_bounds__(256) void scan_i8_kernel(const I8ScanParams p) {
         if (!grouped) return;
         // the hand-off: lane 0 has stored this wave's slots; its acq_rel add releases them and, for the wave that completes
         // the count, acquires every other wave's
-        const uint32_t g = blockIdx.x;   // (= cur / kI8BlockWaves: the launch puts consecutive tasks into a workgroup)
+        const uint32_t g = wg;   // (= cur / kI8BlockWaves: the launch puts consecutive tasks into a workgroup)
         uint32_t gr;
         const uint32_t gbase = p.tiers.locate(g * kI8BlockWaves, gr);
         uint32_t t = 0u;
@@ -294,11 +301,22 @@ __global__ __launch_bounds__(256) void scan_i8_kernel(const I8ScanParams p) {
 #pragma unroll
     for (int b = 0; b < BQ; ++b) sc[b] = -INFINITY;
     const int nb = (int)(trows / (uint32_t)RI);
-    for (int j = 0; j < nb; ++j) {
-        const uint32_t m = (uint32_t)(mask >> (RI * j)) & ((1u << RI) - 1u);
-        if (m == 0u) continue;   // all RI rows filtered out / past the end: skip their reads
-        load_rows(base, j, x);
-        reduce_rows(j, x, sc);
+    // NT: the load policy is the workgroup's (uniform).  The ends of the copy, where one search stops and the next one
+    // starts, load plainly and so are found in the Infinity Cache; the rest streams.  Each arm is the whole batch loop.
+    if (NT && wg >= p.plain_lo && wg < p.plain_hi) {
+        for (int j = 0; j < nb; ++j) {
+            const uint32_t m = (uint32_t)(mask >> (RI * j)) & ((1u << RI) - 1u);
+            if (m == 0u) continue;   // all RI rows filtered out / past the end: skip their reads
+            load_rows(std::true_type{}, base, j, x);
+            reduce_rows(j, x, sc);
+        }
+    } else {
+        for (int j = 0; j < nb; ++j) {
+            const uint32_t m = (uint32_t)(mask >> (RI * j)) & ((1u << RI) - 1u);
+            if (m == 0u) continue;
+            load_rows(std::false_type{}, base, j, x);
+            reduce_rows(j, x, sc);
+        }
     }
     epilogue(cur, base, trows, mask, scale, sc);
 }
@@ -320,6 +338,10 @@ static hipError_t launch_i8(const ScanArgs& a, const int8_t* codes, const float*
     }
     const uint32_t wpb = kI8BlockWaves;
     const dim3 grid((p.n_tasks + wpb - 1u) / wpb), block(64u * wpb);
+    p.n_wg = grid.x;
+    p.rev = a.sweep_rev;
+    const PlainWindow pw = a.nontemporal ? plain_window(GroupMap{p.tiers, kI8BlockWaves}, p.n, p.dim, a.plain_bytes) : PlainWindow{0u, p.n_wg};
+    p.plain_lo = pw.lo; p.plain_hi = pw.hi;
     const bool full = (a.dim == (uint32_t)NCH * 1024u);
     for_nt_full(a.nontemporal, full, [&](auto nt_c, auto full_c) {
         hipLaunchKernelGGL((scan_i8_kernel<NCH, BQ, RI, decltype(nt_c)::value, decltype(full_c)::value, PQ>), grid, block, 0, st, p);

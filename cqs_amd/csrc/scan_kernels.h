@@ -49,6 +49,8 @@ struct ScanArgs {
     TaskTiers tiers;        // plan_tiers(n_pad, n_cu, uniform_groups(b, dim))
     uint32_t group_tasks = 1;   // tasks per entry of gmax / gaux (GroupMap::G): 1, or 4 for the int8 scan, whose workgroup
                             // publishes one triple for its four tasks; gmax / gaux are then [b, ceil(tiers.total() / 4)]
+    uint32_t sweep_rev = 0; // int8 scan only: 1 = its workgroups take the tasks in reverse order (i8_sweep.h; same outputs)
+    uint64_t plain_bytes = 0;   // int8 scan only, nontemporal: bytes at each end of the copy that are loaded plainly
     uint32_t* work;         // [kWorkWords] work-queue heads (zero on entry)
     uint32_t n_cu;          // compute units of the device
     bool gemv_only = false; // never the matrix-core kernel, whatever b: blocks of > 8 queries run as passes of <= 8
