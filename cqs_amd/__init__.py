@@ -4,7 +4,7 @@ Product code lives here and in cqs_amd/csrc (HIP kernels + C ABI, include/cqs_hi
 It never imports anything from oracle/ (test infrastructure).
 """
 from .index import (BackendContext, DiffEntry, DiffResult, DistanceMetric, DriftEntry, DriftResult, HipBackend, HipError,
-                    HipIndex, IndexResult, VectorIndex, merge_keys, prepare_index_data, tag_filter, unpack_keys)
+                    HipIndex, IndexResult, MovedEntry, VectorIndex, merge_keys, prepare_index_data, tag_filter, unpack_keys)
 
 __all__ = ["BackendContext", "DiffEntry", "DiffResult", "DistanceMetric", "DriftEntry", "DriftResult", "HipBackend", "HipError",
-           "HipIndex", "IndexResult", "VectorIndex", "merge_keys", "prepare_index_data", "tag_filter", "unpack_keys"]
+           "HipIndex", "IndexResult", "MovedEntry", "VectorIndex", "merge_keys", "prepare_index_data", "tag_filter", "unpack_keys"]

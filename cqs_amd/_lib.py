@@ -32,6 +32,7 @@ PCA_MAX_COMPONENTS = 4
 UMAP_INIT_RANDOM = 0
 UMAP_INIT_PCA = 1
 MMR_MAX = 1024
+MATCH_MAX = 65536
 
 _c_idx = C.c_void_p
 _pp = C.POINTER
@@ -121,6 +122,8 @@ SIGNATURES = [
      [_c_idx, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_void_p]),
     ("cqs_hip_index_diff", C.c_int32,
      [_c_idx, C.c_void_p, _c_idx, C.c_void_p, C.c_uint64, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    ("cqs_hip_index_match", C.c_int32,
+     [_c_idx, C.c_void_p, C.c_uint32, _c_idx, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     ("cqs_hip_index_pairwise", C.c_int32, [_c_idx, C.c_void_p, C.c_uint32, C.c_void_p]),
     ("cqs_hip_index_mmr", C.c_int32,
      [_c_idx, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.c_float, C.c_void_p, _pp(C.c_uint32)]),

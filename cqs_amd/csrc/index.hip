@@ -397,6 +397,7 @@ void cqs_hip_index_destroy(cqs_hip_index* x) CQS_ABI_TRY {
     update_free(x);
     knn_free(x);
     diff_free(x);
+    match_free(x);
     hipFree(x->d_keep);
     free_keep_tab(x);
     hipFree(x->d_dbg);

@@ -1,6 +1,6 @@
 // index_internal.h — the index handle and the host helpers shared by the index's translation units (index.hip,
 // index_persist.hip, index_combine.hip, index_shadow.hip, index_remove.hip, index_update.hip, index_knn.hip, index_diff.hip,
-// mmr.hip, sharded.hip).
+// index_match.hip, mmr.hip, sharded.hip).
 // Internal to libcqs_hip.so (the public boundary is include/cqs_hip.h).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -132,6 +132,13 @@ struct cqs_hip_index {
     void* diff_d = nullptr;
     uint64_t diff_pairs = 0;
 
+    // Staging of cqs_hip_index_match (index_match.hip; null until the first such call with this handle as `a`): the two
+    // local row lists and the packed bests of both sides in one block on the device and its pinned twin, sized for
+    // match_rows rows of the two lists together (the largest call seen).  Kept between calls, freed at destroy.
+    void* match_h = nullptr;
+    void* match_d = nullptr;
+    uint64_t match_rows = 0;
+
     // bf16 shadow (index_shadow.hip; null = off).  Its certified / fallback counts outlive it: they live on the handle.
     cqs_idx::Shadow* shadow = nullptr;
     std::atomic<uint64_t> stat_certified{0}, stat_fallbacks{0};
@@ -228,6 +235,7 @@ int32_t update_entries(cqs_hip_index* x, const uint32_t* local, uint64_t local_o
 void update_free(cqs_hip_index* x);
 void knn_free(cqs_hip_index* x);   // the staging of cqs_hip_index_knn_graph (index_knn.hip)
 void diff_free(cqs_hip_index* x);  // the staging of cqs_hip_index_diff (index_diff.hip)
+void match_free(cqs_hip_index* x); // the staging of cqs_hip_index_match (index_match.hip)
 bool shadow_takes(const cqs_hip_index* x, uint32_t b, uint32_t k, bool gemv_only);
 bool shadow_uses_i8(const cqs_hip_index* x, uint32_t b, uint32_t k);   // of a block shadow_takes: the int8 copy serves it
 int32_t shadow_pass(cqs_hip_index* x, const float* d_q, uint32_t nb, uint32_t k, const uint32_t* d_keep, uint32_t mode,

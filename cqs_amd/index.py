@@ -19,7 +19,7 @@ from __future__ import annotations
 import ctypes as C
 import enum
 import logging
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import Callable, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -65,13 +65,24 @@ class DiffEntry:
 
 
 @dataclass
+class MovedEntry:
+    """A chunk the source holds under one key and the target under another (moved to another file, renamed): the two
+    ids and the f32 dot of the two stored rows (the cosine on cosine indexes).  The reference has no such entry."""
+
+    source_id: str
+    target_id: str
+    similarity: float
+
+
+@dataclass
 class DiffResult:
-    """`DiffResult` (src/diff.rs:238-245)."""
+    """`DiffResult` (src/diff.rs:238-245); `moved` is this library's (`semantic_diff(..., moved_threshold=...)`)."""
 
     added: List[DiffEntry]
     removed: List[DiffEntry]
     modified: List[DiffEntry]
     unchanged_count: int
+    moved: List[MovedEntry] = field(default_factory=list)
 
 
 @dataclass
@@ -117,6 +128,44 @@ def sort_modified(entries: Sequence[DiffEntry]) -> List[DiffEntry]:
     """src/diff.rs:226-236: most changed first (similarity ascending under the f32 total order), entries without a
     similarity behind every entry with one, ties by id."""
     return sorted(entries, key=lambda e: (e.similarity is None, 0 if e.similarity is None else _total_order_key(e.similarity), e.id))
+
+
+def sort_moved(entries: Sequence[MovedEntry]) -> List[MovedEntry]:
+    """Like `sort_modified`: least similar first (the f32 total order), ties by the target's id."""
+    return sorted(entries, key=lambda e: (_total_order_key(e.similarity), e.target_id))
+
+
+MATCH_NONE = 0xFFFFFFFFFFFFFFFF   # `best` of a row without a finite entry (its score is 0.0)
+
+
+def _order_keys(scores: np.ndarray) -> np.ndarray:
+    """f32 array -> u32 array in the order of `f32::total_cmp`."""
+    b = np.ascontiguousarray(scores, dtype=np.float32).view(np.uint32)
+    return np.where(b >> np.uint32(31), ~b, b ^ np.uint32(0x80000000)).astype(np.uint32)
+
+
+def merge_best(best: np.ndarray, score: np.ndarray, other_best: np.ndarray, other_score: np.ndarray) -> None:
+    """`cqs_match::merge_best` (match_host.h) over whole arrays, in place: (best, score) are answers over some blocks of the
+    other side's list, (other_best, other_score) over another, positions global in that list.  The greater score under
+    the f32 total order wins, then the lower position; MATCH_NONE loses to everything."""
+    none = np.uint64(MATCH_NONE)
+    mine, theirs = _order_keys(score), _order_keys(other_score)
+    keep = (best != none) & ((mine > theirs) | ((mine == theirs) & (best <= other_best)))
+    take = (other_best != none) & ~keep
+    best[take] = other_best[take]
+    score[take] = other_score[take]
+
+
+def mutual_pairs(best_a: np.ndarray, score_a: np.ndarray, best_b: np.ndarray, threshold: float) -> List[Tuple[int, int]]:
+    """`cqs_match::mutual_pairs`: the (i, j) with best_a[i] == j, best_b[j] == i and score_a[i] >= threshold (an f32
+    compare), in ascending i."""
+    thr = np.float32(threshold)
+    out = []
+    for i in range(len(best_a)):
+        j = int(best_a[i])
+        if j != MATCH_NONE and j < len(best_b) and int(best_b[j]) == i and np.float32(score_a[i]) >= thr:
+            out.append((i, j))
+    return out
 
 
 def drift_entries(modified: Sequence[DiffEntry], min_drift: float) -> List[DriftEntry]:
@@ -923,22 +972,77 @@ class HipIndex(VectorIndex):
     def _row_base(self) -> int:
         return int(self._lib.cqs_hip_index_row_base(self._h))
 
-    def semantic_diff(self, other: "HipIndex", threshold: float, key: Optional[Callable[[str], object]] = None) -> "DiffResult":
+    def _match_block(self, other: "HipIndex", rows_a: np.ndarray, rows_b: np.ndarray):
+        """One `cqs_hip_index_match` call: at most MATCH_MAX rows per side, positions local to the two blocks.  The one
+        place `match_rows` touches the device (the CPU tests put a numpy stand-in here)."""
+        m_a, m_b = rows_a.shape[0], rows_b.shape[0]
+        best_a, score_a = np.full((m_a,), MATCH_NONE, dtype=np.uint64), np.zeros((m_a,), dtype=np.float32)
+        best_b, score_b = np.full((m_b,), MATCH_NONE, dtype=np.uint64), np.zeros((m_b,), dtype=np.float32)
+        rc = self._lib.cqs_hip_index_match(self._h, _ptr(rows_a) if m_a else None, m_a, other._h, _ptr(rows_b) if m_b else None, m_b,
+                                           _ptr(best_a) if m_a else None, _ptr(score_a) if m_a else None,
+                                           _ptr(best_b) if m_b else None, _ptr(score_b) if m_b else None)
+        if rc != _lib.OK:
+            raise HipError(rc, self.last_error())
+        return best_a, score_a, best_b, score_b
+
+    def match_rows(self, other: "HipIndex", rows_a, rows_b, block: int = _lib.MATCH_MAX):
+        """`cqs_hip_index_match`: for the stored rows `rows_a` of this index and `rows_b` of `other` (global row ids, any
+        order, repeats allowed) the best partner of every row on the other side by the f32 dot of the two stored rows.
+        Returns (best_a u64 [m_a]: the position in rows_b, ties to the lowest, MATCH_NONE where there is no finite entry;
+        score_a f32 [m_a]; best_b u64 [m_b]; score_b f32 [m_b]).  Lists longer than `block` (<= MATCH_MAX) are cut into
+        blocks on both sides and the blocks' answers merged by `merge_best`, so any length works; a smaller `block` holds
+        the two handles for a shorter time per call."""
+        ra = np.ascontiguousarray(rows_a, dtype=np.uint64).reshape(-1)
+        rb = np.ascontiguousarray(rows_b, dtype=np.uint64).reshape(-1)
+        block = int(block)
+        if not 1 <= block <= _lib.MATCH_MAX:
+            raise ValueError(f"block must be in 1 .. {_lib.MATCH_MAX}")
+        m_a, m_b = ra.shape[0], rb.shape[0]
+        best_a, score_a = np.full((m_a,), MATCH_NONE, dtype=np.uint64), np.zeros((m_a,), dtype=np.float32)
+        best_b, score_b = np.full((m_b,), MATCH_NONE, dtype=np.uint64), np.zeros((m_b,), dtype=np.float32)
+        none = np.uint64(MATCH_NONE)
+        for i0 in range(0, max(m_a, 1), block):
+            for j0 in range(0, max(m_b, 1), block):
+                ba, sa, bb, sb = self._match_block(other, ra[i0:i0 + block], rb[j0:j0 + block])
+                ba[ba != none] += np.uint64(j0)
+                bb[bb != none] += np.uint64(i0)
+                merge_best(best_a[i0:i0 + block], score_a[i0:i0 + block], ba, sa)
+                merge_best(best_b[j0:j0 + block], score_b[j0:j0 + block], bb, sb)
+        return best_a, score_a, best_b, score_b
+
+    def semantic_diff(self, other: "HipIndex", threshold: float, key: Optional[Callable[[str], object]] = None,
+                      moved_threshold: Optional[float] = None) -> "DiffResult":
         """`semantic_diff(source_store, target_store, .., threshold, ..)` (src/diff.rs:99-246) with this index as the source
         and `other` as the target.  Ids are matched by `key(id)` (default: the id itself; the reference's ChunkKey is
         (file, name, chunk_type) without the line); of several ids with one key the last wins (:130-137).  `added`: in
         the target only; `removed`: in the source only; matched pairs go through `diff_rows`: `modified` holds the
         target's id and the similarity of those below the threshold, sorted by (similarity under the f32 total order
         ascending, entries without a similarity last, id) (:226-236); `unchanged_count` the rest.  Matching and sorting
-        are string work and stay on the host; the cosines are computed where the rows lie."""
+        are string work and stay on the host; the cosines are computed where the rows lie.
+        `moved_threshold` (default None: the result above, `moved` empty): the source's removed rows are matched against
+        the target's added rows by `match_rows`; a removed and an added chunk that are each other's best partner with a
+        similarity (the dot of the stored rows: the cosine on cosine indexes) at or above it become one `moved` entry
+        and leave `added` and `removed`.  `moved` is sorted like `modified`: similarity ascending, then target id.  A
+        NaN `moved_threshold` raises ValueError."""
+        if moved_threshold is not None and moved_threshold != moved_threshold:
+            raise ValueError("moved_threshold is NaN")
         src, tgt = self._all_ids(), other._all_ids()
         added, removed, matched = match_ids(src, tgt, key)
         ra = np.asarray([s for s, _ in matched], dtype=np.uint64) + np.uint64(self._row_base())
         rb = np.asarray([t for _, t in matched], dtype=np.uint64) + np.uint64(other._row_base())
         mod_pairs, mod_sims, counts = self.diff_rows(other, ra, rb, threshold)[:3]
         modified = [DiffEntry(tgt[matched[int(p)][1]], float(s)) for p, s in zip(mod_pairs, mod_sims)]
+        moved: List[MovedEntry] = []
+        if moved_threshold is not None and added and removed:
+            best_a, score_a, best_b, _ = self.match_rows(other, np.asarray(removed, dtype=np.uint64) + np.uint64(self._row_base()),
+                                                         np.asarray(added, dtype=np.uint64) + np.uint64(other._row_base()))
+            pairs = mutual_pairs(best_a, score_a, best_b, moved_threshold)
+            moved = sort_moved([MovedEntry(src[removed[i]], tgt[added[j]], float(score_a[i])) for i, j in pairs])
+            gone_a, gone_b = {i for i, _ in pairs}, {j for _, j in pairs}
+            removed = [s for i, s in enumerate(removed) if i not in gone_a]
+            added = [t for j, t in enumerate(added) if j not in gone_b]
         return DiffResult([DiffEntry(tgt[t], None) for t in added], [DiffEntry(src[s], None) for s in removed],
-                          sort_modified(modified), int(counts[1]))
+                          sort_modified(modified), int(counts[1]), moved)
 
     def detect_drift(self, other: "HipIndex", threshold: float, min_drift: float) -> "DriftResult":
         """`detect_drift(ref_store, project_store, .., threshold, min_drift, ..)` (src/drift.rs:51-120) with this index as the

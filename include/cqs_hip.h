@@ -550,6 +550,44 @@ int32_t cqs_hip_index_diff(cqs_hip_index* a, const uint64_t* rows_a, cqs_hip_ind
                            uint64_t m, float threshold, float* out_sims, uint64_t* out_mod_pairs, float* out_mod_sims,
                            uint64_t* out_counts);
 
+/* ---- best partners between two row lists of two resident indexes -------------------
+ * `semantic_diff` matches chunks by key - (file, name, chunk_type) in the reference (src/diff.rs:43-53) - so a function
+ * moved to another file, or renamed, leaves one `removed` and one unrelated `added` entry; the comment at :45-47 admits
+ * it for line moves and stops there, the host having no cheap way to compare every removed chunk with every added one.
+ * With both corpora resident that is the cross similarity of two row lists, reduced on the device to the best partner
+ * of every row on either side; the [m_a, m_b] matrix is never stored and only the bests cross the bus.
+ * rows_a [m_a], rows_b [m_b]  GLOBAL row ids of `a` and of `b` (row_base included, as diff / neighbors / remove take
+ *            them), host.  Any order; a row may be listed more than once.  `a == b` is allowed, and so are borrowing
+ *            handles (rows are only read).
+ * S[i][j]    the f32 dot of stored row rows_a[i] of `a` and stored row rows_b[j] of `b` - the cosine on COSINE indexes -
+ *            accumulated as cqs_hip_index_pairwise accumulates: one fma chain over k in the order 32 it + 8 u + c,
+ *            32 it + 8 u + 4 + c (it = 0 .., u = 0..3, c = 0..3).  It is bit for bit the entry cqs_hip_index_pairwise
+ *            gives for the same two rows where they live in one index: a function of the two rows and dim only, not of
+ *            m_a, m_b, the positions, the tiling or the grid; (a, b) and (b, a) give the same bits.
+ * out_best_a [m_a] u64, out_score_a [m_a] f32, host: out_best_a[i] = the POSITION j in rows_b with the greatest S[i][j]
+ *            under the f32 total order, the lowest j among equals; out_score_a[i] = that entry.  Only finite entries are
+ *            considered (a non-finite entry never wins, as no search of this library emits one); without a finite entry -
+ *            which includes m_b == 0 - out_best_a[i] = UINT64_MAX and out_score_a[i] = 0.0f.
+ * out_best_b [m_b], out_score_b [m_b]  the same with the roles exchanged: the best i per j, the lowest i among equals.
+ *            Ties going to the lowest position on both sides, the pairs with out_best_a[i] == j && out_best_b[j] == i are
+ *            a one-to-one matching.
+ * m_a == 0 && m_b == 0 returns CQS_HIP_OK and touches nothing.
+ * Refused with CQS_HIP_ERR_INVALID, every output untouched, neither handle poisoned and the reason in `a`'s last_error,
+ * in this order: a NULL a or b; (both lists empty returns CQS_HIP_OK here, whatever the other arguments); NULL rows_a with
+ * m_a > 0 or NULL rows_b with m_b > 0; a NULL output of a side with m > 0; m_a or m_b above CQS_HIP_MATCH_MAX; either
+ * handle row-sharded; the handles on different devices; dim(a) != dim(b); any row outside its index (the text names the
+ * side and the first offending position, side a first).  A poisoned handle on either side -> CQS_HIP_ERR_POISONED.  A
+ * device failure poisons `a` only.
+ * The call holds BOTH handles' mutexes for its whole length (taken in address order, once when a == b) and orders its
+ * launches after the last search of each.  A first call makes a staging block of 12 bytes per listed row (both lists
+ * together) of the largest call seen, pinned and on the device, which `a` keeps until destroy; a handle that never calls
+ * match pays nothing.  One copy back and one wait per call.  Longer lists: cut either into blocks of at most
+ * CQS_HIP_MATCH_MAX and keep, per row, the greater score under the total order, then the lower position. */
+#define CQS_HIP_MATCH_MAX 65536u         /* rows per side of one call */
+int32_t cqs_hip_index_match(cqs_hip_index* a, const uint64_t* rows_a, uint32_t m_a, cqs_hip_index* b,
+                            const uint64_t* rows_b, uint32_t m_b, uint64_t* out_best_a, float* out_score_a,
+                            uint64_t* out_best_b, float* out_score_b);
+
 /* ---- cosine MMR re-rank of a candidate pool ------------------------------------
  * The reference diversifies its top-K pool with `mmr_rerank` (src/search/mmr.rs:59-126) over a surface-feature
  * similarity, because it drops the embeddings after scoring: "embedding-MMR is a follow-up" (mmr.rs:30-37,
